@@ -3,19 +3,23 @@
 
 A "step" is one fused (eval_g, eval_jac_g) launch over one batch of B distinct NLP iterates x_k (new_x = true for each)
 already resident in HBM; R iterates are kept resident and cycled so that the outputs do not live in the Infinity Cache.
-The K steps are captured in one hipGraph.  ONE timed region = exactly K steps bracketed by barrier + synchronize; the
-region is repeated until at least 0.25 s have been timed and `value` / `ms_per_step` come from the MEDIAN region (p10 / p90
-beside it) — a single 20-step region is 2 ms and scatters by 15 %.  Per-rank times are reduced with MAX over ranks.
+The K steps are captured in one hipGraph.  After W warm-up steps and one untimed replay of the graph (its upload), ONE
+timed region = exactly K steps bracketed by barrier + synchronize; `value` / `ms_per_step` come from its wall time, reduced
+with MAX over ranks.  --dump-outputs DIR writes what the last timed step computed (a fixed, seeded sample: dump_outputs).
+
+A plain run does only that.  Everything else below (and the check of the timed results against a single evaluation, and
+the measured store ceiling of the roofline) runs with --full; the other sections time regions repeated for >= 0.25 s and
+report the median one.
 
 At --gpus N > 1 `value` is the instance-sharded (weak-scaling) rate of that workload: every rank evaluates its own
-stream of iterates, no data-path collective.  The SAME invocation also measures, with all N ranks on the data path:
+stream of iterates, no data-path collective.  With --full the SAME invocation also measures, with all N ranks on the data path:
   strong_scaling   mesh intervals of ONE config-3 / config-4 problem sharded over the ranks, ONE packed RCCL all-gather of
                    the g + Jacobian segments per step, pack / all-gather / unpack captured in the step's hipGraph;
   host_consumer    the same sharding with a host-side consumer (Ipopt's position): every rank stores its runs of g / values
                    into one shared page-locked host array over its own PCIe link, no GPU-to-GPU traffic;
   config5          the 1024-instance quadrotor sweep sharded by instance.
 
-Extra first-class sections on rank 0 at N = 1 (what a TNLP caller can consume):
+Extra first-class sections on rank 0 at N = 1 with --full (what a TNLP caller can consume):
   sequential       B = 1 device-resident pairs/s (a sequential solver loop on the device)
   host_pointer     PCIe-inclusive pairs/s through rpm_eval_g / rpm_eval_jac_g / rpm_eval_pair on caller-owned arrays
   ms_per_ipopt_iter  eval_f + eval_grad_f + eval_g + eval_jac_g at ONE iterate, device-resident and host-pointer
@@ -37,6 +41,9 @@ sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak, /opt/skills/guides/MI355X_MICROARCH.md
 MIN_TIMED_S = 0.25
+# --dump-outputs: at most 8 of a step's iterates and 60 MB of values in all (8 iterates of the metric problem: 56.6 MB)
+DUMP_MAX_ITERATES = 8
+DUMP_MAX_BYTES = 60_000_000
 
 
 def d_tile_doubles(eng):
@@ -168,10 +175,10 @@ class Ctx:
         return [float(v) for v in t.cpu()]
 
 
-def timed_regions(ctx, step, K, warmup, use_graph=True, min_s=None, max_regions=4000):
+def timed_regions(ctx, step, K, warmup, use_graph=True, min_s=None, max_regions=4000, regions=None):
     """W warm-up steps, then regions of EXACTLY K steps each (one hipGraph replay when the steps can be captured), each
-    bracketed by barrier + synchronize, repeated until min_s seconds have been timed.  Returns wall seconds and device
-    milliseconds per region (MAX over ranks), and how the steps were launched."""
+    bracketed by barrier + synchronize, repeated until min_s seconds have been timed, or exactly `regions` of them when that is
+    given.  Returns wall seconds and device milliseconds per region (MAX over ranks), and how the steps were launched."""
     torch = ctx.torch
     min_s = MIN_TIMED_S if min_s is None else min_s
     for k in range(warmup):
@@ -214,14 +221,17 @@ def timed_regions(ctx, step, K, warmup, use_graph=True, min_s=None, max_regions=
         el = time.perf_counter() - t0
         return el, ev0.elapsed_time(ev1)
 
-    first = region()
-    second = region()
-    # the first region runs slower than the steady state (it set the count too low for min_s in round 1's first cut): the count
-    # comes from the faster of the first two, with a margin
-    n = int(min(max_regions, max(5, math.ceil(1.15 * min_s / max(min(first[0], second[0]), 1e-6)))))
-    n = int(ctx.max_over_ranks([float(n)])[0])   # the same count on every rank
-    wall, dev = [first[0], second[0]], [first[1], second[1]]
-    for _ in range(n - 2):
+    if regions is not None:
+        n, wall, dev = regions, [], []
+    else:
+        first = region()
+        second = region()
+        # the first region runs slower than the steady state (it set the count too low for min_s in round 1's first cut): the
+        # count comes from the faster of the first two, with a margin
+        n = int(min(max_regions, max(5, math.ceil(1.15 * min_s / max(min(first[0], second[0]), 1e-6)))))
+        n = int(ctx.max_over_ranks([float(n)])[0])   # the same count on every rank
+        wall, dev = [first[0], second[0]], [first[1], second[1]]
+    while len(wall) < n:
         a, b = region()
         wall.append(a)
         dev.append(b)
@@ -252,7 +262,7 @@ def make_iterates(problems, eng, count, seed0, mode="perturb"):
 
 
 def device_workload(ctx, args, prob, B, R, K, warmup, sharded, seed0, mode="perturb", align=16, use_graph=True,
-                    role_loop=-1, pipeline=-1, dx_mode=0, tile_nodes=0, unfused=False, keep=False, persistent=False):
+                    role_loop=-1, pipeline=-1, dx_mode=0, tile_nodes=0, unfused=False, keep=False, persistent=False, regions=None):
     """The fused pair kernel over R resident iterates, B per step; with `sharded` the mesh intervals of every iterate are split
     over the ranks and the results exchanged with ONE packed all-gather per step."""
     import numpy as np
@@ -291,9 +301,9 @@ def device_workload(ctx, args, prob, B, R, K, warmup, sharded, seed0, mode="pert
         if xch is not None:
             xch.exchange(d_g[r], d_v[r])
 
-    regions = timed_regions(ctx, step, K, warmup, use_graph=use_graph)
-    regions.pop("graph", None)
-    out = summarize(regions, K, B)
+    timed = timed_regions(ctx, step, K, warmup, use_graph=use_graph, regions=regions)
+    timed.pop("graph", None)
+    out = summarize(timed, K, B)
     out.update({"iterates_per_step": B, "resident_iterates": R, "n": eng.n, "m": eng.m, "nnz_jac": eng.nnz_jac,
                 "kernel": ("rpm_tile_pl_kernel" if eng.get_option("pipeline_active") else
                            "rpm_tile_rl_kernel" if eng.get_option("role_loop") else "rpm_tile_kernel"),
@@ -321,6 +331,33 @@ def check_against_single_evaluation(ctx, args, prob, eng, d_x, d_g, d_v, R):
         torch.cuda.synchronize()
         assert torch.equal(chk_g, d_g[r, :eng.m]) and torch.equal(chk_v, d_v[r, :eng.nnz_jac]) and bool(torch.isfinite(chk_v).all())
     one.close()
+
+
+def dump_sample(B, m, nnz, max_bytes=DUMP_MAX_BYTES, max_iterates=DUMP_MAX_ITERATES):
+    """Which outputs --dump-outputs writes: a fixed, seeded choice of at most `max_iterates` of a step's B iterates (positions
+    in the batch), and of each the entries of g and of the Jacobian values (all of them unless that exceeds `max_bytes`)."""
+    import numpy as np
+    rng = np.random.RandomState(0)
+    rows = np.sort(rng.choice(B, min(B, max_iterates), replace=False))
+    per_row = max(2, max_bytes // (8 * len(rows)))
+    if m + nnz <= per_row:
+        return rows, np.arange(m), np.arange(nnz)
+    kg = max(1, min(m, per_row * m // (m + nnz)))
+    return rows, np.sort(rng.choice(m, kg, replace=False)), np.sort(rng.choice(nnz, per_row - kg, replace=False))
+
+
+def dump_outputs(dirname, d_g, d_v, r, B, m, nnz):
+    """What the last timed step handed its caller: g (m entries) and the Jacobian values (nnz_jac entries) of its B iterates,
+    rows r .. r + B - 1 of the resident arrays; the sample of dump_sample(), float64, as <dirname>/g.npy and
+    <dirname>/jac_values.npy, one row per sampled iterate."""
+    import numpy as np
+    import torch
+    rows, gcols, vcols = dump_sample(B, m, nnz)
+    idx = torch.from_numpy(r + rows).to(d_g.device)
+    os.makedirs(dirname, exist_ok=True)
+    for name, d, cols in (("g", d_g, gcols), ("jac_values", d_v, vcols)):
+        a = d.index_select(0, idx).index_select(1, torch.from_numpy(cols).to(d.device))
+        np.save(os.path.join(dirname, name + ".npy"), a.cpu().numpy().astype(np.float64))
 
 
 def sequential_section(ctx, args, prob, xs):
@@ -661,8 +698,15 @@ def sweep_group_part(devices, B=1024):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=500)
+    ap.add_argument("--steps", type=int, default=500, help="timed steps: ONE timed region of exactly this many steps")
     ap.add_argument("--warmup", type=int, default=50)
+    ap.add_argument("--full", action="store_true",
+                    help="also the checks and every other section (result check against a single evaluation, measured store\n"
+                         "ceiling, sequential, host_pointer, persistent_values, device_ipm, strong_scaling, config 5,\n"
+                         "host_consumer, single_process_group, cpu_baseline); a plain run measures the headline figure only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed (g and the Jacobian values of a fixed, seeded\n"
+                         "sample of its iterates) as DIR/g.npy and DIR/jac_values.npy, float64, rank 0")
     ap.add_argument("--iterates", type=int, default=384,
                     help="distinct NLP iterates resident in HBM: 384 x 7.1 MB = 2.7 GB of outputs, ten times the 256 MiB Infinity "
                          "Cache (with 64 resident iterates and 16 per launch the Jacobian blocks of a cycle fit it and the kernel "
@@ -673,10 +717,10 @@ def main():
                     help="what `value` measures at --gpus N > 1 (the other split is reported in its own section either way)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--only-main", action="store_true", help="skip every section but the main metric")
+    ap.add_argument("--only-main", action="store_true", help="with --full: skip every section but the main metric and its checks")
     ap.add_argument("--profile", action="store_true",
-                    help="profiling run: only the warm-up and ONE timed region (no extra checks/sections), so that\n"
-                         "rocprofv3 --stats averages exactly the launches bench.py times")
+                    help="profiling run: only the warm-up and ONE timed region (no extra checks/sections, even with --full),\n"
+                         "so that rocprofv3 --stats averages exactly the launches bench.py times")
     ap.add_argument("--dx-mode", type=int, default=0, help="0: scalar D.X in the reference's order, 1: FP64 MFMA tiles")
     ap.add_argument("--tile-nodes", type=int, default=0)
     ap.add_argument("--role-loop", type=int, default=-1, help="-1 auto, 0 one role per thread, 1 role-looped 64-node tiles")
@@ -713,10 +757,8 @@ def main():
     from lpopc_amd import problems
     ctx = Ctx(args)
     rank, world = ctx.rank, ctx.world
-    global MIN_TIMED_S
-    if args.profile:
-        MIN_TIMED_S = 0.0
     errors = {}
+    full = args.full and not args.profile
 
     prob = problems.launch(args.intervals, args.nodes)
     sharded = args.shard == "intervals" and world > 1
@@ -726,9 +768,11 @@ def main():
     main_res, eng, xs, d_x, d_g, d_v = device_workload(
         ctx, args, prob, B, args.iterates, args.steps, args.warmup, sharded, seed0, align=args.instance_align,
         use_graph=not args.no_graph, role_loop=args.role_loop, pipeline=args.pipeline, dx_mode=args.dx_mode,
-        tile_nodes=args.tile_nodes, unfused=args.unfused, keep=True, persistent=args.persistent)
+        tile_nodes=args.tile_nodes, unfused=args.unfused, keep=True, persistent=args.persistent, regions=1)
     R = main_res["resident_iterates"]
-    if not sharded and not os.environ.get("RPM_DIAG_MASK") and not args.profile:
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, d_g, d_v, ((args.steps - 1) * B) % R, B, eng.m, eng.nnz_jac)
+    if full and not sharded and not os.environ.get("RPM_DIAG_MASK"):
         check_against_single_evaluation(ctx, args, prob, eng, d_x, d_g, d_v, R)
 
     out = None
@@ -775,8 +819,8 @@ def main():
                 "pair": ("unfused: eval_g kernel + eval_jac_g kernel" if args.unfused else
                          "fused: one tile-kernel launch writes g and all Jacobian values of the step's iterates") +
                         (" EXCEPT the constant Doffdiag block (--persistent: not the TNLP contract, not comparable with `value` of a default run)" if args.persistent else ""),
-                "timing": "each timed region = exactly `steps` steps between barrier+synchronize; regions repeated until >= %.2f s; "
-                          "value and ms_per_step are the median region (max over ranks per region)" % MIN_TIMED_S,
+                "timing": "ONE timed region of exactly `steps` steps between barrier+synchronize, after `warmup` steps (and, with a "
+                          "hipGraph, one untimed replay of it); value and ms_per_step come from its wall time (max over ranks)",
                 "launch": main_res["launch"],
                 "tile_nodes": main_res["tile_nodes"],
                 "thread_layout": ("persistent workgroups of two halves, each 4 compute waves + 2 DMA waves (rpm_tile_pl_kernel)" if main_res["kernel"] == "rpm_tile_pl_kernel"
@@ -803,7 +847,7 @@ def main():
     eng.close()
     del d_x, d_g, d_v
     ctx.torch.cuda.empty_cache()
-    if rank == 0 and not args.profile and not args.persistent:
+    if full and rank == 0 and not args.persistent:
         try:   # normalise by what this box's write path delivers to the same store pattern, measured now
             sc = store_ceiling(ctx)
             out["roofline"]["measured_store_ceiling"] = sc
@@ -816,7 +860,7 @@ def main():
         except Exception as ex:
             errors["store_ceiling"] = repr(ex)
 
-    extras = not args.profile and not args.only_main
+    extras = full and not args.only_main
     # ---- rank 0 alone, N = 1: what a TNLP caller can consume --------------------------------------------------------
     if extras and world == 1 and rank == 0:
         try:

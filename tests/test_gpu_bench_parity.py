@@ -134,3 +134,37 @@ def test_hip_path_reproduces_the_golden_fixtures(built, name, layout):
     assert abs(eng.eval_f(x) - fx["f"][0]) <= 1e-12 * max(1.0, abs(fx["f"][0]))
     assert rel_err(eng.eval_grad_f(x), fx["grad_f"]) <= JFD_TOL
     eng.close()
+
+
+def test_plain_bench_run_dumps_what_its_last_step_computed(built, tmp_path):
+    """`bench.py --dump-outputs DIR` without --full: exactly `steps` timed steps, none of the --full sections, and DIR holds g
+    and the Jacobian values of the last timed step's iterates (bench.dump_sample's seeded choice), equal to a single
+    evaluation of the same seeded iterates as bench.py --full checks them."""
+    import json
+    import subprocess
+    import sys
+    import torch
+    import bench
+    steps, B, R = 5, 4, 8
+    r = subprocess.run([sys.executable, os.path.join(os.path.dirname(HERE), "bench.py"), "--gpus", "1", "--steps", str(steps),
+                        "--warmup", "2", "--batch", str(B), "--iterates", str(R), "--dump-outputs", str(tmp_path)],
+                       capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = json.loads(r.stdout.strip().splitlines()[-1])
+    assert line["steps"] == steps and line["timed_regions"] == 1 and line["ms_per_step"] > 0 and line["value"] > 0
+    assert line["cpu_baseline"] is None and "sequential" not in line and "device_ipm" not in line and "errors" not in line
+    prob = problems.launch(64, 16)
+    eng = NLPEngine(prob, device=0)
+    xs = bench.make_iterates(problems, eng, R, 3)
+    first = ((steps - 1) * B) % R
+    rows, gcols, vcols = bench.dump_sample(B, eng.m, eng.nnz_jac)
+    g, v = np.load(tmp_path / "g.npy"), np.load(tmp_path / "jac_values.npy")
+    assert g.dtype == v.dtype == np.float64 and g.shape == (len(rows), len(gcols)) and v.shape == (len(rows), len(vcols))
+    assert g.nbytes + v.nbytes <= bench.DUMP_MAX_BYTES
+    d_g = torch.empty(eng.m, dtype=torch.float64, device="cuda")
+    d_v = torch.empty(eng.nnz_jac, dtype=torch.float64, device="cuda")
+    for k, i in enumerate(rows):
+        eng.eval_pair_dev(torch.from_numpy(xs[first + i]).cuda(), d_g, d_v)
+        torch.cuda.synchronize()
+        assert np.array_equal(g[k], d_g.cpu().numpy()[gcols]) and np.array_equal(v[k], d_v.cpu().numpy()[vcols])
+    eng.close()

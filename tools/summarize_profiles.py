@@ -1,6 +1,6 @@
-"""Copies the rocprofv3 summaries collected by tools/collect_profiles.sh from gpurun_out/ (scratch)
-into profiles/ (tracked): the kernel-stats CSV, a PMC summary and profiles/pmc_traffic.json, which
-bench.py reports as roofline.traffic."""
+"""Copies the rocprofv3 summaries that `tools/collect_profiles.sh TAG OUTDIR` left in OUTDIR into profiles/ (tracked): the
+kernel-stats CSV, a PMC summary and profiles/pmc_traffic.json, which bench.py reports as roofline.traffic.
+python tools/summarize_profiles.py TAG OUTDIR"""
 import collections
 import csv
 import glob
@@ -11,12 +11,13 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 tag = sys.argv[1] if len(sys.argv) > 1 else "r01"
+src = os.path.abspath(sys.argv[2])
 out = os.path.join(ROOT, "profiles")
 os.makedirs(out, exist_ok=True)
 
 
 def one(pattern):
-    fs = sorted(glob.glob(os.path.join(ROOT, "gpurun_out", pattern)), key=os.path.getmtime)
+    fs = sorted(glob.glob(os.path.join(src, pattern)), key=os.path.getmtime)
     return fs[-1] if fs else None
 
 
@@ -53,7 +54,7 @@ if "FETCH_SIZE" in pmc and "WRITE_SIZE" in pmc:
     json.dump({"tag": tag, "hbm_bytes_per_launch": fetch + write, "fetch_bytes": fetch, "write_bytes": write,
                "note": "FETCH_SIZE " + summary["hbm_read_correction"] + ", WRITE_SIZE exact"},
               open(os.path.join(out, "pmc_traffic.json"), "w"), indent=1)
-bj = os.path.join(ROOT, "gpurun_out", "%s_bench.json" % tag)
+bj = os.path.join(src, "%s_bench.json" % tag)
 if os.path.exists(bj):
     line = [l for l in open(bj) if l.startswith("{")]
     if line:
