@@ -309,7 +309,6 @@ int device_init(Engine& e, int device_id) {
   k.tasks = d->d_tasks;
   k.n_tasks = (!sharded || e.shard_rank == 0) ? int(e.tasks.size()) : 0;  // rank 0 owns the endpoint rows
   k.skip_const = 0;
-  k.diag_mask = 0;
   k.trace = nullptr;
   k.chk = nullptr;
 #ifdef RPM_DIAG
@@ -319,7 +318,6 @@ int device_init(Engine& e, int device_id) {
     if (hipMalloc(reinterpret_cast<void**>(&k.trace), words * 8) == hipSuccess) (void)hipMemset(k.trace, 0, words * 8);
     d->trace_words = words;
   }
-  if (const char* dm = getenv("RPM_DIAG_MASK")) k.diag_mask = atoi(dm);
 #endif
   ProblemDims pd;
   problem_dims(e.problem_id, &pd);

@@ -43,7 +43,6 @@ struct KParams {
   int max_span, max_drow;
   int max_cshare;                       // largest constant-block share of a tile (c_cnt)
   int skip_const;                       // 1: this launch leaves the constant Doffdiag block of `values` alone (persistent arrays, dev_eval_cons)
-  int diag_mask;                        // ablation mask, only honoured by the -DRPM_DIAG diagnostic build
   unsigned long long* trace;            // per-workgroup timestamps (diagnostic build with RPM_DIAG_TRACE set), else NULL
   int* chk;                             // host-pointer path: two host-visible words ORed with "a stored g / Jacobian value is NaN/Inf"; else NULL
 };

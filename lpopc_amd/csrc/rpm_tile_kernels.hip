@@ -17,7 +17,6 @@
 // dynamics, role 1+v the dynamics with variable v perturbed (v = states, controls, time) — the
 // reference's (2+nx+nu) whole-vector user calls become (2+nx+nu) roles evaluated concurrently.
 // State roles also compute their state's D.X row from the LDS-staged D rows and X tile.
-#include <cstdlib>
 #include "rpm_device_internal.hpp"
 
 namespace rpm {
@@ -197,6 +196,74 @@ __device__ void endpoint_block(const KParams& K, const TaskDev task, const doubl
 }
 
 // ------------------------------------------------------------------------------------------
+// The per-node role arithmetic of the three tile layouts (rpm_tile_kernel, rpm_tile_rl_kernel, rpm_tile_pl_kernel).  One
+// copy, so that the layouts stay bit-identical; each layout keeps its own thread layout, loads, staging, synchronisation and
+// store address form.  A thread works on node k of its tile (lane kk of the [..][T] LDS rows) for one role: role 0 is the
+// unperturbed dynamics, role 1 + v the dynamics with variable v = [states, controls, time, static parameters] perturbed.
+// CHK: the one-role kernel notes NaN/Inf among the values it stores (host-pointer path); the others pass false.
+
+// The dynamics of a role at (tk, xs, us = [controls, static parameters]): f and c, or with AN column v of the node
+// Jacobian for roles >= 1.  STG (has_stage functors): from the sub-expressions of the node's unperturbed point, recomputing
+// only what the perturbed variable enters (same operations, same bits as the whole dae()).
+template <class Prob, bool WJ, bool AN, bool STG = false, class CP>
+__device__ __forceinline__ void role_dynamics(int phase_num, int role, double tk, const double* xs, const double* us, CP c,
+                                              double* f, double* cp,
+                                              const typename stage_of<Prob>::type* base_stage = nullptr) {
+  const int v = role - 1;
+  if constexpr (STG) {
+    Prob::dae_from(phase_num, tk, xs, us, c, *base_stage, (WJ && role >= 1) ? v : -1, f, cp);
+  } else if (!AN || role == 0) {
+    pf_dae<Prob>(phase_num, tk, xs, us, us + Prob::NU, c, f, cp);
+  } else if constexpr (AN) {
+    pf_dae_jac_col<Prob>(phase_num, v, tk, xs, us, us + Prob::NU, c, f, cp);  // f, cp now hold column v of the Jacobian
+  }
+}
+
+// Finite-difference step of a wave-uniform role: h = tol (1+|v|), v+h  (LpFiniteDifferenceDerive.cpp:208-214).  The caller
+// fetches the one perturbed variable pv by its (scalar) row; h and pv + h are formed once and the sum is put back where the
+// variable belongs — instead of forming them for every variable and selecting.  Returns h.
+template <int NX, int NU, int NQ>
+__device__ __forceinline__ double perturb_uniform(int v, double pv, double tol, double* xs, double* us, double& tk) {
+  const double h = tol * (1 + fabs(pv));
+  const double pp = pv + h;
+#pragma unroll
+  for (int i = 0; i < NX; ++i) xs[i] = (v == i) ? pp : xs[i];
+#pragma unroll
+  for (int j = 0; j < NU; ++j) us[j] = (v == NX + j) ? pp : us[j];
+  tk = (v == NX + NU) ? pp : tk;
+#pragma unroll
+  for (int j = 0; j < NQ; ++j) us[NU + j] = (v == NX + NU + 1 + j) ? pp : us[NU + j];
+  return h;
+}
+
+// Role 0 publishes the unperturbed outputs: f and c into Fb ([NO][T]) for the other roles' differences, and c into the path
+// rows of g (LpNLPWrapper.cpp:138-164).
+template <class Prob, int T, bool WG, bool CHK>
+__device__ __forceinline__ void publish_base(const double* f, const double* cp, double* Fb, int kk, double* g, int g0, int N,
+                                             int k, bool& bad_g) {
+  constexpr int NX = Prob::NX, NC = Prob::NC;
+#pragma unroll
+  for (int i = 0; i < NX; ++i) Fb[i * T + kk] = f[i];
+#pragma unroll
+  for (int j = 0; j < NC; ++j) {
+    Fb[(NX + j) * T + kk] = cp[j];
+    if (WG) {
+      g[g0 + (NX + j) * N + k] = cp[j];
+      if (CHK) chk_note(bad_g, cp[j]);
+    }
+  }
+}
+
+// The defect of state sv at node k: D.X - (dt/2) f  (LpNLPWrapper.cpp:113,122).
+template <int T, bool CHK>
+__device__ __forceinline__ void store_defect(int sv, double dx, double tspan, const double* Fb, int kk, double* g, int g0,
+                                             int N, int k, bool& bad_g) {
+  const double dfc = dx - Fb[sv * T + kk] * (tspan / 2.0);
+  g[g0 + sv * N + k] = dfc;
+  if (CHK) chk_note(bad_g, dfc);
+}
+
+// ------------------------------------------------------------------------------------------
 template <class Prob, int T, bool WG, bool WJ, bool AN, bool DXM = false>
 __global__ void rpm_tile_kernel(const KParams K, const double* __restrict__ xall,
                                 double* __restrict__ gall, double* __restrict__ vall) {
@@ -211,10 +278,6 @@ __global__ void rpm_tile_kernel(const KParams K, const double* __restrict__ xall
   const double* __restrict__ x = xall + size_t(blockIdx.y) * K.n;
   double* __restrict__ g = gall + size_t(blockIdx.y) * K.sg;
   double* __restrict__ vals = vall + size_t(blockIdx.y) * K.sv;
-#ifdef RPM_DIAG
-  if (K.diag_mask & 32) return;
-  if ((K.diag_mask & 1) && int(blockIdx.x) >= K.n_my_tiles) return;
-#endif
   if (int(blockIdx.x) >= K.n_my_tiles) {  // the launch's trailing workgroups: endpoint work items
     endpoint_block<Prob, WG, WJ, AN>(K, K.tasks[int(blockIdx.x) - K.n_my_tiles], x, g, vals, lds, int(blockIdx.y));
     return;
@@ -226,9 +289,6 @@ __global__ void rpm_tile_kernel(const KParams K, const double* __restrict__ xall
   const int tix = xcd * per + (xcd < rem ? xcd : rem) + slot;
   const TileDev tl = K.tiles[tix];
   const TileDev& ph = tl;   // the phase fields the kernel needs are replicated in the tile record
-#ifdef RPM_DIAG
-  if (K.diag_mask & 64) { if (tl.cnt < 0) vals[0] = 0; return; }
-#endif
   const auto c = (const __attribute__((address_space(4))) double*)(K.consts + size_t(blockIdx.y) * K.consts_stride);   // constant address space: scalar loads
   double* Xs = lds;                          // [NX][max_span]  state-matrix rows the tile's D rows touch
   double* Us = Xs + NX * K.max_span;         // [NU][T]
@@ -256,9 +316,6 @@ __global__ void rpm_tile_kernel(const KParams K, const double* __restrict__ xall
     }
   }
 
-#ifdef RPM_DIAG
-  if (K.diag_mask & 128) { if (tau + cpre[0] + cpre[5] + ddiag + nd.dlen == 1e300) vals[0] = 0; return; }
-#endif
   // ---- stage X tile, U tile and D rows in LDS (coalesced: every run below is contiguous in HBM) ----
   for (int q = tid; q < NX * tl.span_len; q += nthr) {
     const int i = q / tl.span_len, r = q - i * tl.span_len;
@@ -271,14 +328,8 @@ __global__ void rpm_tile_kernel(const KParams K, const double* __restrict__ xall
   if (WG)
     for (int q = tid; q < tl.drow_len; q += nthr) Ds[q] = K.dvals[tl.drow0 + q];
   const double t0 = x[ph.x_t0], tf = x[ph.x_t0 + 1];
-#ifdef RPM_DIAG
-  if (K.diag_mask & 256) { if (t0 == 1e300) vals[0] = 0; return; }
-#endif
   __syncthreads();
 
-#ifdef RPM_DIAG
-  if (K.diag_mask & 16) return;
-#endif
   const bool act = kk < tl.cnt && role < R;
   const double tspan = tf - t0;
   double tk = (tau + 1) * (tspan / 2.0) + t0;      // LpNLPWrapper.cpp:80
@@ -336,7 +387,8 @@ __global__ void rpm_tile_kernel(const KParams K, const double* __restrict__ xall
     }
   }
 
-  // ---- perturb this role's variable: h = tol (1+|v|), v+h  (LpFiniteDifferenceDerive.cpp:208-214) ----
+  // ---- perturb this role's variable (the step of perturb_uniform; the role is not wave-uniform here: formed for every
+  //      variable and selected) ----
   double h = 1.0;
   const int v = role - 1;
   if (WJ && !AN && role >= 1) {
@@ -352,38 +404,13 @@ __global__ void rpm_tile_kernel(const KParams K, const double* __restrict__ xall
       if (v == NX + NU + 1 + j) { h = K.tol * (1 + fabs(us[NU + j])); us[NU + j] += h; }
   }
   double f[NX > 0 ? NX : 1], cp[NCs];
-#ifdef RPM_DIAG
-  if (K.diag_mask & 2) {
-    for (int i = 0; i < NX; ++i) f[i] = xs[i] * tk;
-    for (int j = 0; j < NCs; ++j) cp[j] = us[0];
-  } else
-#endif
-  if (!AN || role == 0) {
-    pf_dae<Prob>(ph.phase_num, tk, xs, us, us + NU, c, f, cp);
-  } else if constexpr (AN) {
-    pf_dae_jac_col<Prob>(ph.phase_num, v, tk, xs, us, us + NU, c, f, cp);  // f, cp now hold column v of the Jacobian
-  }
-  if (role == 0 && act) {
-#pragma unroll
-    for (int i = 0; i < NX; ++i) Fb[i * T + kk] = f[i];
-#pragma unroll
-    for (int j = 0; j < NC; ++j) {
-      Fb[(NX + j) * T + kk] = cp[j];
-      if (WG) { g[ph.g0 + (NX + j) * ph.N + k] = cp[j]; chk_note(bad_g, cp[j]); }          // path rows, :138-164
-    }
-  }
+  role_dynamics<Prob, WJ, AN>(ph.phase_num, role, tk, xs, us, c, f, cp);
+  if (role == 0 && act) publish_base<Prob, T, WG, true>(f, cp, Fb, kk, g, ph.g0, ph.N, k, bad_g);
   __syncthreads();
 
   if (act) {
     const int N = ph.N;
-    if (WG && sv >= 0 && sv < NX) {
-      const double dfc = (DXM ? DXs[sv * T + kk] : dx) - Fb[sv * T + kk] * (tspan / 2.0);   // defects, :113,122
-      g[ph.g0 + sv * N + k] = dfc;
-      chk_note(bad_g, dfc);
-    }
-#ifdef RPM_DIAG
-    if (!(K.diag_mask & 8))
-#endif
+    if (WG && sv >= 0 && sv < NX) store_defect<T, true>(sv, DXM ? DXs[sv * T + kk] : dx, tspan, Fb, kk, g, ph.g0, N, k, bad_g);
     if (WJ && role >= 1) {
       double J[NO];
 #pragma unroll
@@ -436,9 +463,6 @@ __global__ void rpm_tile_kernel(const KParams K, const double* __restrict__ xall
   // ---- this workgroup's share of the constant Doffdiag block (LpNLPWrapper.cpp:715-718): the block is
   //      nx back-to-back copies of the phase's off-diagonal value list; read each source value once,
   //      store it into every state's copy (all runs contiguous across lanes) ----
-#ifdef RPM_DIAG
-  if (!(K.diag_mask & 4))
-#endif
   if (WJ && !K.skip_const) {
     const double* __restrict__ src = K.doff_vals + tl.c_src0;
     double* __restrict__ dst = vals + tl.c_dst0;
@@ -505,22 +529,17 @@ __global__ __launch_bounds__(T* RG) void rpm_tile_rl_kernel(const KParams K, con
   const double tau = K.points[nidx];
   const NodeDev nd = K.nodes[nidx];
   const double ddiag = WJ ? K.diag[nidx] : 0.0;
-#ifdef RPM_DIAG
-  const bool diag_noload = K.diag_mask & 2;
-#else
-  constexpr bool diag_noload = false;
-#endif
   for (int q = tid; q < NX * tl.span_len; q += NTHR) {
     const int i = q / tl.span_len, r = q - i * tl.span_len;
-    Xs[i * K.max_span + r] = diag_noload ? 1.0e6 + q : x[ph.x_state0 + i * (ph.N + 1) + tl.span0 + r];
+    Xs[i * K.max_span + r] = x[ph.x_state0 + i * (ph.N + 1) + tl.span0 + r];
   }
   for (int q = tid; q < NU * tl.cnt; q += NTHR) {
     const int j = q / tl.cnt, r = q - j * tl.cnt;
-    Us[j * T + r] = diag_noload ? 0.5 : x[ph.x_control0 + j * ph.N + tl.k0 + r];
+    Us[j * T + r] = x[ph.x_control0 + j * ph.N + tl.k0 + r];
   }
   if (WG)
-    for (int q = tid; q < tl.drow_len; q += NTHR) Ds[q] = diag_noload ? 0.25 : K.dvals[tl.drow0 + q];
-  const double t0 = diag_noload ? 0.0 : x[ph.x_t0], tf = diag_noload ? 100.0 : x[ph.x_t0 + 1];
+    for (int q = tid; q < tl.drow_len; q += NTHR) Ds[q] = K.dvals[tl.drow0 + q];
+  const double t0 = x[ph.x_t0], tf = x[ph.x_t0 + 1];
   RPM_TRC(1);
   __syncthreads();
   RPM_TRC(2);
@@ -529,7 +548,7 @@ __global__ __launch_bounds__(T* RG) void rpm_tile_rl_kernel(const KParams K, con
   const double tspan = tf - t0;
   const double tk0 = (tau + 1) * (tspan / 2.0) + t0;      // LpNLPWrapper.cpp:80
   const int N = ph.N;
-  bool first = true;
+  bool first = true, no_chk = false;   // no_chk: the NaN/Inf bookkeeping is the one-role kernel's (CHK = false)
   for (int role = grp; role < R || first; role += RG) {
     const bool act = node_ok && role < R;
     double xs[NX > 0 ? NX : 1], us[NU + NQ > 0 ? NU + NQ : 1];   // us = [controls, static parameters]
@@ -549,58 +568,25 @@ __global__ __launch_bounds__(T* RG) void rpm_tile_rl_kernel(const KParams K, con
     }
     double h = 1.0;
     const int v = role - 1;
-    if (WJ && !AN && role >= 1) {     // h = tol (1+|v|), v+h  (LpFiniteDifferenceDerive.cpp:208-214)
-      // the role is wave-uniform: fetch the one perturbed variable by its (scalar) row, form h and v+h once
+    if (WJ && !AN && role >= 1) {   // the role is wave-uniform: fetch the one perturbed variable by its (scalar) row
       double pv;
       if (v < NX) pv = Xs[v * K.max_span + (k - tl.span0)];
       else if (v < NX + NU) pv = Us[(v - NX) * T + kc];
       else if (v == NX + NU) pv = tk;
       else pv = x[ph.x_t0 + 1 + (v - NX - NU)];   // static parameter v - NX - NU - 1
-      h = K.tol * (1 + fabs(pv));
-      const double pp = pv + h;
-#pragma unroll
-      for (int i = 0; i < NX; ++i) xs[i] = (v == i) ? pp : xs[i];
-#pragma unroll
-      for (int j = 0; j < NU; ++j) us[j] = (v == NX + j) ? pp : us[j];
-      tk = (v == NX + NU) ? pp : tk;
-#pragma unroll
-      for (int j = 0; j < NQ; ++j) us[NU + j] = (v == NX + NU + 1 + j) ? pp : us[NU + j];
+      h = perturb_uniform<NX, NU, NQ>(v, pv, K.tol, xs, us, tk);
     }
     double f[NX > 0 ? NX : 1], cp[NCs];
-#ifdef RPM_DIAG
-    if ((K.diag_mask & 1) && role >= 4) {
-#pragma unroll
-      for (int i = 0; i < NX; ++i) f[i] = Fb[i * T + kk] + h;
-#pragma unroll
-      for (int j = 0; j < NC; ++j) cp[j] = Fb[(NX + j) * T + kk] + h;
-    } else
-#endif
-    if (!AN || role == 0) {
-      pf_dae<Prob>(ph.phase_num, tk, xs, us, us + NU, c, f, cp);
-    } else if constexpr (AN) {
-      pf_dae_jac_col<Prob>(ph.phase_num, v, tk, xs, us, us + NU, c, f, cp);
-    }
+    role_dynamics<Prob, WJ, AN>(ph.phase_num, role, tk, xs, us, c, f, cp);
     if (first) {   // wave-uniform: the first pass publishes the unperturbed outputs before anyone forms a difference
-      if (role == 0 && act) {
-#pragma unroll
-        for (int i = 0; i < NX; ++i) Fb[i * T + kk] = f[i];
-#pragma unroll
-        for (int j = 0; j < NC; ++j) {
-          Fb[(NX + j) * T + kk] = cp[j];
-          if (WG) g[ph.g0 + (NX + j) * N + k] = cp[j];           // path rows, :138-164
-        }
-      }
+      if (role == 0 && act) publish_base<Prob, T, WG, false>(f, cp, Fb, kk, g, ph.g0, N, k, no_chk);
       __syncthreads();
       RPM_TRC(3);
       first = false;
     }
     if (act) {
-      if (WG && sv >= 0 && sv < NX) g[ph.g0 + sv * N + k] = dx - Fb[sv * T + kk] * (tspan / 2.0);   // defects, :113,122
-#ifdef RPM_DIAG
-      if (WJ && role >= 1 && !(K.diag_mask & 8)) {
-#else
+      if (WG && sv >= 0 && sv < NX) store_defect<T, false>(sv, dx, tspan, Fb, kk, g, ph.g0, N, k, no_chk);
       if (WJ && role >= 1) {
-#endif
         double J[NO];
 #pragma unroll
         for (int o = 0; o < NO; ++o) {
@@ -643,11 +629,7 @@ __global__ __launch_bounds__(T* RG) void rpm_tile_rl_kernel(const KParams K, con
     }
   }
   RPM_TRC(4);
-#ifdef RPM_DIAG
-  if (WJ && !K.skip_const && !(K.diag_mask & 4)) {
-#else
   if (WJ && !K.skip_const) {
-#endif
     // this tile's share of the constant Doffdiag block (LpNLPWrapper.cpp:715-718)
     const double* __restrict__ src = K.doff_vals + tl.c_src0;
     double* __restrict__ dst = vals + tl.c_dst0;
@@ -955,11 +937,6 @@ __global__ __launch_bounds__(NH * 64 * (RG + NDMA), 1) void rpm_tile_pl_kernel(
     return;
   }
 
-#ifdef RPM_DIAG
-#define RPM_JSTORE(dst, val) if (!(K.diag_mask & 8) || (val) == 1e300) dst = (val)
-#else
-#define RPM_JSTORE(dst, val) dst = (val)
-#endif
   // ---------------- compute waves: the role loop of rpm_tile_rl_kernel out of the staged buffer ----------------
   const int kk = tid % T, grp = __builtin_amdgcn_readfirstlane(tid / T);   // a wave is one role group: roles are wave-uniform (scalar branches, scalar block offsets)
   for (int jt = 0; jt < n_iter_wg; ++jt) {
@@ -989,9 +966,8 @@ __global__ __launch_bounds__(NH * 64 * (RG + NDMA), 1) void rpm_tile_pl_kernel(
     const int kc = kk < cnt ? kk : cnt - 1;
     const int k = k0 + kc;
     const bool node_ok = kk < cnt;
-    bool first = true;
-    // STG (has_stage functors): the sub-expressions of the dynamics at the node's unperturbed point, once per wave and tile; a
-    // role then recomputes only what its one perturbed variable enters (same operations, same bits as the whole dae())
+    bool first = true, no_chk = false;
+    // STG: the sub-expressions of the dynamics at the node's unperturbed point, once per wave and tile (role_dynamics)
     typename stage_of<Prob>::type base_stage;
     if constexpr (STG) {
       static_assert(NQ == 0 && !AN, "staged evaluation: finite differences, no static parameters");
@@ -1046,45 +1022,21 @@ __global__ __launch_bounds__(NH * 64 * (RG + NDMA), 1) void rpm_tile_pl_kernel(
 #endif
       double h = 1.0;
       const int v = role - 1;
-      if (WJ && !AN && role >= 1) {     // h = tol (1+|v|), v+h  (LpFiniteDifferenceDerive.cpp:208-214)
-        // the role is wave-uniform: fetch the one perturbed variable by its (scalar) row, form h and v+h once, and
-        // put the sum back where it belongs — instead of forming them for every variable and selecting
+      if (WJ && !AN && role >= 1) {   // the role is wave-uniform: fetch the one perturbed variable by its (scalar) row
         double pv;
         if (v < NX) pv = Xs[v * K.max_span + (k - span0)];
         else if (v < NX + NU) pv = Us[(v - NX) * T + kc];
         else if (v == NX + NU) pv = tk;
         else pv = cur[S_TT + 1 + (v - NX - NU)];   // static parameter v - NX - NU - 1
-        h = K.tol * (1 + fabs(pv));
-        const double pp = pv + h;
-#pragma unroll
-        for (int i = 0; i < NX; ++i) xs[i] = (v == i) ? pp : xs[i];
-#pragma unroll
-        for (int j = 0; j < NU; ++j) us[j] = (v == NX + j) ? pp : us[j];
-        tk = (v == NX + NU) ? pp : tk;
-#pragma unroll
-        for (int j = 0; j < NQ; ++j) us[NU + j] = (v == NX + NU + 1 + j) ? pp : us[NU + j];
+        h = perturb_uniform<NX, NU, NQ>(v, pv, K.tol, xs, us, tk);
       }
       double f[NXs], cp[NCs];
-      if constexpr (STG) {
-        Prob::dae_from(phase_num, tk, xs, us, c4, base_stage, (WJ && role >= 1) ? v : -1, f, cp);
-      } else if (!AN || role == 0) {
-        pf_dae<Prob>(phase_num, tk, xs, us, us + NU, c4, f, cp);
-      } else if constexpr (AN) {
-        pf_dae_jac_col<Prob>(phase_num, v, tk, xs, us, us + NU, c4, f, cp);
-      }
+      role_dynamics<Prob, WJ, AN, STG>(phase_num, role, tk, xs, us, c4, f, cp, &base_stage);
 #ifdef RPM_DIAG
       if (trc) { if (f[0] == 1e300) cp[0] = 0; RPM_PTRC(jt, 26); }
 #endif
       if (first) {   // wave-uniform: the first pass publishes the unperturbed outputs before anyone forms a difference
-        if (role == 0 && act) {
-#pragma unroll
-          for (int i = 0; i < NX; ++i) Fb[i * T + kk] = f[i];
-#pragma unroll
-          for (int j = 0; j < NC; ++j) {
-            Fb[(NX + j) * T + kk] = cp[j];
-            if (WG) g[g0 + (NX + j) * N + k] = cp[j];           // path rows, :138-164
-          }
-        }
+        if (role == 0 && act) publish_base<Prob, T, WG, false>(f, cp, Fb, kk, g, g0, N, k, no_chk);
         if (grp < 4) { RPM_PTRC(jt, grp * 4 + 1); }
         // F: the other compute waves wait for role 0's outputs.  A flag in LDS, not s_barrier: the DMA waves stay out
         // of it (they are busy with the constant block and the next tile), and the role-0 wave never waits.
@@ -1105,7 +1057,7 @@ __global__ __launch_bounds__(NH * 64 * (RG + NDMA), 1) void rpm_tile_pl_kernel(
             while (__hip_atomic_load(dx_ready, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) < NDMA * (jt + 1)) __builtin_amdgcn_s_sleep(1);
             dx = DXs[sv * T + kk];
           }
-          g[g0 + sv * N + k] = dx - Fb[sv * T + kk] * ((tf - t0) / 2.0);   // defects, :113,122
+          store_defect<T, false>(sv, dx, tf - t0, Fb, kk, g, g0, N, k, no_chk);
         }
         if (WJ && role >= 1) {
           double J[NO];
@@ -1126,7 +1078,7 @@ __global__ __launch_bounds__(NH * 64 * (RG + NDMA), 1) void rpm_tile_pl_kernel(
               } else {
                 val = J[o];
               }
-              RPM_JSTORE((vb + size_t(o * NB + bv) * N)[k], val);
+              (vb + size_t(o * NB + bv) * N)[k] = val;
             }
           } else {                       // d/dt0 and d/dtf blocks (:748-760, :801-811); B-5 sign kept
             const double a0 = -(tau * 0.5) + 0.5, af = (tau * 0.5) + 0.5;
@@ -1142,8 +1094,8 @@ __global__ __launch_bounds__(NH * 64 * (RG + NDMA), 1) void rpm_tile_pl_kernel(
                 v0 = a0 * J[o];
                 vf = af * J[o];
               }
-              RPM_JSTORE((vb + size_t(o * NB + NX + NU) * N)[k], v0);
-              RPM_JSTORE((vb + size_t(o * NB + NX + NU + 1) * N)[k], vf);
+              (vb + size_t(o * NB + NX + NU) * N)[k] = v0;
+              (vb + size_t(o * NB + NX + NU + 1) * N)[k] = vf;
             }
           }
         }
@@ -1185,37 +1137,23 @@ void tile_pipeline_setup(Engine& e, Device* d, const ProblemDims& pd, int device
 }
 
 // ------------------------------------------------------------------------------------------
-template <class Prob, int T, bool WG, bool WJ, bool AN, bool DXM = false>
-static hipError_t launch_tile_inst(const Engine& e, const KParams& kp, const double* dx, double* dg, double* dv, hipStream_t st) {
-  constexpr int R = WJ ? Prob::NX + Prob::NU + 2 + prob_nq<Prob>::value : (Prob::NX > 0 ? Prob::NX : 1);
-  int threads = T * R;
-  threads = (threads + 63) / 64 * 64;
-  if (threads < 64) threads = 64;
+// a kernel's dynamic LDS beyond the default 64 KB
+template <class Kern>
+static hipError_t allow_lds(Kern kern, size_t bytes) {
+  if (bytes <= 64 * 1024) return hipSuccess;
+  return hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, int(bytes));
+}
+
+// the one-role and the role-looped kernel: one workgroup per tile and per endpoint work item, grid.y = instances
+template <class Kern>
+static hipError_t launch_tiles(const Engine& e, Kern kern, int threads, const KParams& kp, const double* dx, double* dg,
+                               double* dv, hipStream_t st) {
   const Device& d = *e.dev;
-  auto kern = rpm_tile_kernel<Prob, T, WG, WJ, AN, DXM>;
-  if (d.lds_bytes > 64 * 1024) {
-    hipError_t s = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, int(d.lds_bytes));
-    if (s != hipSuccess) return s;
-  }
+  hipError_t s = allow_lds(kern, d.lds_bytes);
+  if (s != hipSuccess) return s;
   dim3 grid(unsigned(d.kp.n_my_tiles + d.kp.n_tasks), unsigned(e.n_instances));
   if (grid.x == 0) return hipSuccess;   // an interval-sharded rank that owns no tile of this (small) mesh
   hipLaunchKernelGGL(kern, grid, dim3(threads), d.lds_bytes, st, kp, dx, dg, dv);
-  return hipGetLastError();
-}
-
-template <class Prob, int T, int RG, bool WG, bool WJ, bool AN>
-static hipError_t launch_tile_rl(const Engine& e, const KParams& kp, const double* dx, double* dg, double* dv, hipStream_t st) {
-  const Device& d = *e.dev;
-  auto kern = rpm_tile_rl_kernel<Prob, T, RG, WG, WJ, AN>;
-  if (d.lds_bytes > 64 * 1024) {
-    hipError_t s = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       int(d.lds_bytes));
-    if (s != hipSuccess) return s;
-  }
-  dim3 grid(unsigned(d.kp.n_my_tiles + d.kp.n_tasks), unsigned(e.n_instances));
-  if (grid.x == 0) return hipSuccess;   // an interval-sharded rank that owns no tile of this (small) mesh
-  hipLaunchKernelGGL(kern, grid, dim3(T * RG), d.lds_bytes, st, kp, dx, dg, dv);
   return hipGetLastError();
 }
 
@@ -1230,25 +1168,22 @@ static bool pl_dxm_ok(const Engine& e) {
   return e.first_derive != RPM_DERIVE_ANALYTIC && e.dev->pl_lds + pl_dxm_extra(e) <= 160 * 1024;
 }
 
-template <class Prob, bool WG, bool WJ, bool AN, bool DXM = false, bool STG = false>
+template <class Prob, bool WG, bool WJ, bool AN, bool DXM, bool STG = false>
 static hipError_t launch_tile_pl(const Engine& e, const KParams& kp, const double* dx, double* dg, double* dv, hipStream_t st) {
   if constexpr (!STG && !AN && has_stage<Prob>::value) {
     // engine option "stage_roles": 1 the functor's staged dynamics, 0 whole-function evaluations, -1 (default) staged when the
     // launch is bound by the dynamics and not by its stores — persistent `values` (kp.skip_const).  Measured on the metric
     // problem, 64 iterates per launch: 75.3 -> 69.5 us with the constant block skipped, but 99.2 -> 106.6 us with all stores (21
     // more registers in a kernel that waits for its stores); same bits either way
-    static const bool env_off = std::getenv("RPM_STAGE_ROLES") && std::atoi(std::getenv("RPM_STAGE_ROLES")) == 0;   // measurements
-    if (!env_off && (e.opt_stage_roles == 1 || (e.opt_stage_roles < 0 && (kp.skip_const || stage_always<Prob>::value))))
+    if (e.opt_stage_roles == 1 || (e.opt_stage_roles < 0 && (kp.skip_const || stage_always<Prob>::value)))
       return launch_tile_pl<Prob, WG, WJ, AN, DXM, true>(e, kp, dx, dg, dv, st);
   }
   const Device& d = *e.dev;
   constexpr PlShape S = pl_shape(Prob::NX + Prob::NU + 2 + prob_nq<Prob>::value);
   auto kern = rpm_tile_pl_kernel<Prob, S.NH, S.RG, S.NDMA, WG, WJ, AN, DXM, STG>;
   const size_t lds = d.pl_lds + (DXM ? size_t(S.NH) * Prob::NX * 64 * sizeof(double) : 0);
-  if (lds > 64 * 1024) {
-    hipError_t s = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds));
-    if (s != hipSuccess) return s;
-  }
+  hipError_t s = allow_lds(kern, lds);
+  if (s != hipSuccess) return s;
   const long long W = (long long)d.kp.n_my_tiles * e.n_instances;
   const long long halves = W < d.pl_slots ? W : d.pl_slots;   // pl_slots: resident halves (occupancy query)
   hipLaunchKernelGGL(kern, dim3(unsigned((halves + S.NH - 1) / S.NH)), dim3(S.NH * 64 * (S.RG + S.NDMA)), lds, st, kp,
@@ -1268,8 +1203,8 @@ static bool use_pipeline(const Engine& e) {
   return W >= 2LL * d.pl_slots || (W <= d.pl_slots && 4 * W >= 3LL * d.pl_slots);
 }
 
-// true when the next constraint launch is rpm_tile_kernel (one role per thread), the layout that carries the fused NaN/Inf check
-// which of the three layouts the next constraint launch uses: 2 pipelined, 1 role-looped, 0 one role per thread
+// which of the three layouts the next constraint launch uses: 2 pipelined, 1 role-looped, 0 one role per thread (the layout
+// that carries the fused NaN/Inf check)
 static int cons_layout(const Engine& e) {
   if (!(e.role_looped && e.tile_nodes == 64)) return 0;
   if (e.opt_dx_mode == 0) return use_pipeline(e) ? 2 : 1;
@@ -1279,53 +1214,42 @@ bool dev_cons_is_one_role(const Engine& e) { return !e.dev || cons_layout(e) == 
 
 int dev_pipeline_active(const Engine& e) { return e.dev && cons_layout(e) == 2 ? 1 : 0; }
 
+// The template flags of a constraint launch, the same for all three layouts: WG / WJ what the launch writes (a launch that
+// writes neither runs the g kernel); AN the analytic node Jacobian (engine option first_derive, functors that have one,
+// launches with a Jacobian); DXM D.X on the matrix cores (dx_mode 1, finite differences, launches with g).  `launch` is
+// called with the flags as a TileFlags value; these are all the combinations that are instantiated.
+template <bool WG_, bool WJ_, bool AN_, bool DXM_>
+struct TileFlags { static constexpr bool WG = WG_, WJ = WJ_, AN = AN_, DXM = DXM_; };
+
+template <class Prob, class Launch>
+static hipError_t with_tile_flags(const Engine& e, bool wg, bool wj, Launch&& launch) {
+  if constexpr (Prob::HAS_ANALYTIC) {
+    if (wj && e.first_derive == RPM_DERIVE_ANALYTIC)
+      return wg ? launch(TileFlags<true, true, true, false>{}) : launch(TileFlags<false, true, true, false>{});
+  }
+  if (wg && e.opt_dx_mode == 1)
+    return wj ? launch(TileFlags<true, true, false, true>{}) : launch(TileFlags<true, false, false, true>{});
+  if (wg && wj) return launch(TileFlags<true, true, false, false>{});
+  if (wj) return launch(TileFlags<false, true, false, false>{});
+  return launch(TileFlags<true, false, false, false>{});
+}
+
 template <class Prob, int T>
 static hipError_t launch_tile_T(const Engine& e, const KParams& kp, bool wg, bool wj, const double* dx, double* dg,
                                 double* dv, hipStream_t st) {
   const int layout = T == 64 ? cons_layout(e) : 0;
-  if (layout == 2 && e.opt_dx_mode == 1) {   // D.X on the matrix cores, by the DMA waves (finite-difference mode)
-    if (wg && wj) return launch_tile_pl<Prob, true, true, false, true>(e, kp, dx, dg, dv, st);
-    if (wg) return launch_tile_pl<Prob, true, false, false, true>(e, kp, dx, dg, dv, st);
-    return launch_tile_pl<Prob, false, true, false>(e, kp, dx, dg, dv, st);   // Jacobian only: no D.X in it
-  }
-  if (layout == 2) {
-    const bool an_pl = e.first_derive == RPM_DERIVE_ANALYTIC;
-    if constexpr (Prob::HAS_ANALYTIC) {
-      if (an_pl) {
-        if (wg && wj) return launch_tile_pl<Prob, true, true, true>(e, kp, dx, dg, dv, st);
-        if (wj) return launch_tile_pl<Prob, false, true, true>(e, kp, dx, dg, dv, st);
+  return with_tile_flags<Prob>(e, wg, wj, [&](auto flags) -> hipError_t {
+    using F = decltype(flags);
+    if constexpr (T == 64) {
+      if (layout == 2) return launch_tile_pl<Prob, F::WG, F::WJ, F::AN, F::DXM>(e, kp, dx, dg, dv, st);
+      if constexpr (!F::DXM) {   // cons_layout: the role-looped kernel only with dx_mode 0
+        if (layout == 1) return launch_tiles(e, rpm_tile_rl_kernel<Prob, 64, 4, F::WG, F::WJ, F::AN>, 64 * 4, kp, dx, dg, dv, st);
       }
     }
-    if (wg && wj) return launch_tile_pl<Prob, true, true, false>(e, kp, dx, dg, dv, st);
-    if (wj) return launch_tile_pl<Prob, false, true, false>(e, kp, dx, dg, dv, st);
-    return launch_tile_pl<Prob, true, false, false>(e, kp, dx, dg, dv, st);
-  }
-  if (layout == 1) {   // throughput layout (see rpm_tile_rl_kernel)
-    const bool an_rl = e.first_derive == RPM_DERIVE_ANALYTIC;
-    if constexpr (Prob::HAS_ANALYTIC) {
-      if (an_rl) {
-        if (wg && wj) return launch_tile_rl<Prob, 64, 4, true, true, true>(e, kp, dx, dg, dv, st);
-        if (wj) return launch_tile_rl<Prob, 64, 4, false, true, true>(e, kp, dx, dg, dv, st);
-      }
-    }
-    if (wg && wj) return launch_tile_rl<Prob, 64, 4, true, true, false>(e, kp, dx, dg, dv, st);
-    if (wj) return launch_tile_rl<Prob, 64, 4, false, true, false>(e, kp, dx, dg, dv, st);
-    return launch_tile_rl<Prob, 64, 4, true, false, false>(e, kp, dx, dg, dv, st);
-  }
-  const bool an = e.first_derive == RPM_DERIVE_ANALYTIC;
-  if constexpr (Prob::HAS_ANALYTIC) {
-    if (an) {
-      if (wg && wj) return launch_tile_inst<Prob, T, true, true, true>(e, kp, dx, dg, dv, st);
-      if (wj) return launch_tile_inst<Prob, T, false, true, true>(e, kp, dx, dg, dv, st);
-    }
-  }
-  if (e.opt_dx_mode == 1) {   // MFMA D.X (finite-difference derivative mode)
-    if (wg && wj) return launch_tile_inst<Prob, T, true, true, false, true>(e, kp, dx, dg, dv, st);
-    if (wg) return launch_tile_inst<Prob, T, true, false, false, true>(e, kp, dx, dg, dv, st);
-  }
-  if (wg && wj) return launch_tile_inst<Prob, T, true, true, false>(e, kp, dx, dg, dv, st);
-  if (wj) return launch_tile_inst<Prob, T, false, true, false>(e, kp, dx, dg, dv, st);
-  return launch_tile_inst<Prob, T, true, false, false>(e, kp, dx, dg, dv, st);
+    constexpr int R = F::WJ ? Prob::NX + Prob::NU + 2 + prob_nq<Prob>::value : (Prob::NX > 0 ? Prob::NX : 1);
+    constexpr int threads = (T * R + 63) / 64 * 64;
+    return launch_tiles(e, rpm_tile_kernel<Prob, T, F::WG, F::WJ, F::AN, F::DXM>, threads, kp, dx, dg, dv, st);
+  });
 }
 
 // flags: bit0 = g, bit1 = jacobian values

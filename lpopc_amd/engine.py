@@ -14,7 +14,7 @@ from . import _abi
 from .problem import LpopcException
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-# RPM_HIP_LIB lets profiling sessions load the -DRPM_DIAG ablation build; it is never a different backend
+# RPM_HIP_LIB lets profiling sessions load the -DRPM_DIAG timestamp-trace build; it is never a different backend
 _SO = os.environ.get("RPM_HIP_LIB") or os.path.join(_HERE, "csrc", "librpm_hip.so")
 _LIB = None
 
