@@ -782,11 +782,18 @@ __global__ __launch_bounds__(NH * 64 * (RG + NDMA), 1) void rpm_tile_pl_kernel(
   // the halves of a workgroup are independent (own tiles, own LDS); they only share the barriers
   const int half = NH > 1 ? __builtin_amdgcn_readfirstlane(int(threadIdx.x) / HT) : 0;   // wave-uniform
   const int tid = int(threadIdx.x) - half * HT;
-  const int G = NH * int(gridDim.x), w = NH * int(blockIdx.x) + half;
+  // XCD-aware order (as in rpm_tile_kernel): workgroups b, b+8, b+16, ... are dealt to the same XCD, so give each XCD a
+  // contiguous run of halves; the tiles a round of the launch works on (w + j G over all w) then leave each XCD's L2 as
+  // contiguous pieces of every Jacobian block instead of 2-tile pieces interleaved with the other seven XCDs', and the
+  // halves end their last tiles together (102.3 against 108.9 us per 64-iterate step; correctness
+  // does not depend on placement)
+  const int nb = int(gridDim.x), xcd = int(blockIdx.x) & 7, per = nb >> 3, rem = nb & 7;
+  const int wg = xcd * per + (xcd < rem ? xcd : rem) + (int(blockIdx.x) >> 3);   // this workgroup's place in the tile order
+  const int G = NH * nb, w = NH * wg + half;
   const int nt = K.n_my_tiles;
   const int W = nt * n_inst;
   const int n_iter = w < W ? (W - w + G - 1) / G : 0;                 // tiles w, w + G, ... of this half
-  const int n_iter_wg = (W - NH * int(blockIdx.x) + G - 1) / G;       // of half 0: the barrier count of the workgroup
+  const int n_iter_wg = (W - NH * wg + G - 1) / G;                    // of half 0: the barrier count of the workgroup
   // one staging buffer (doubles): record, next tile's record | t0 tf | X rows | U rows | D rows | tau | diag | node
   // records | const share
   const int S_TT = PL_REC, S_X = S_TT + 2 + NQE, S_U = S_X + NX * K.max_span, S_D = S_U + NU * T;
@@ -800,8 +807,16 @@ __global__ __launch_bounds__(NH * 64 * (RG + NDMA), 1) void rpm_tile_pl_kernel(
 #ifdef RPM_DIAG
 #define RPM_PTRC(j, slot)                                                           \
   if (K.trace && (threadIdx.x & 63) == 0 && (j) < 2) K.trace[size_t(w) * 64 + (j)*32 + (slot)] = wall_clock64()
+// a half's launch-edge stamps (words 22, 23 of its first row): the last tile's barrier A, the end of the last tile's last pass
+// (latest compute wave)
+#define RPM_PEDGE(slot) \
+  if (K.trace && (threadIdx.x & 63) == 0) K.trace[size_t(w) * 64 + (slot)] = wall_clock64()
+#define RPM_PEDGE_MAX(slot) \
+  if (K.trace && (threadIdx.x & 63) == 0) atomicMax(K.trace + size_t(w) * 64 + (slot), (unsigned long long)wall_clock64())
 #else
 #define RPM_PTRC(j, slot)
+#define RPM_PEDGE(slot)
+#define RPM_PEDGE_MAX(slot)
 #endif
   if (tid == 0) { RPM_PTRC(0, 31); }
 
@@ -863,10 +878,21 @@ __global__ __launch_bounds__(NH * 64 * (RG + NDMA), 1) void rpm_tile_pl_kernel(
       if (n_iter > 0) stage(std::integral_constant<int, NDMA>{}, dw, lane, w, lds, r0);
       RPM_PTRC(0, 20);
     }
+#ifdef RPM_DIAG
+    unsigned long long wait_sum = 0, wait_max = 0;   // this wave's s_waitcnt in front of barrier A, over all tiles
+#endif
     for (int j = 0; j < n_iter_wg; ++j) {
       const double* cur = lds + (j & 1) * S_SIZE;
       double* nxt = lds + ((j + 1) & 1) * S_SIZE;
+#ifdef RPM_DIAG
+      const unsigned long long tw0 = wall_clock64();
+#endif
       __builtin_amdgcn_s_waitcnt(0);   // the staged loads (and the constant stores before them) have landed
+#ifdef RPM_DIAG
+      const unsigned long long tw = wall_clock64() - tw0;
+      wait_sum += tw;
+      wait_max = tw > wait_max ? tw : wait_max;
+#endif
       __syncthreads();                 // A: buffer `cur` is complete
       RPM_PTRC(j, 16);
       if constexpr (DXM && WG) {
@@ -927,6 +953,12 @@ __global__ __launch_bounds__(NH * 64 * (RG + NDMA), 1) void rpm_tile_pl_kernel(
       }
       RPM_PTRC(j, 18);
     }
+#ifdef RPM_DIAG
+    if (K.trace && lane == 0 && n_iter > 0) {
+      K.trace[size_t(w) * 64 + 28 + dw] = wait_sum;
+      K.trace[size_t(w) * 64 + 32 + 28 + dw] = wait_max;
+    }
+#endif
     // endpoint work items of this workgroup, one wave each
     const int n_end = K.n_tasks * n_inst;
     for (int it = NDMA * w + dw; it < n_end; it += NDMA * G) {
@@ -947,6 +979,7 @@ __global__ __launch_bounds__(NH * 64 * (RG + NDMA), 1) void rpm_tile_pl_kernel(
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
     if (jt >= n_iter) continue;   // the other half still has a tile: keep the barrier count
     if (grp < 4) { RPM_PTRC(jt, grp * 4 + 0); }
+    if (grp == 0 && jt == n_iter - 1) { RPM_PEDGE(22); }
     const int* rec = reinterpret_cast<const int*>(cur);
     const int k0 = __builtin_amdgcn_readfirstlane(rec[offsetof(TileDev, k0) / 4]);
     const int cnt = __builtin_amdgcn_readfirstlane(rec[offsetof(TileDev, cnt) / 4]);
@@ -1105,6 +1138,7 @@ __global__ __launch_bounds__(NH * 64 * (RG + NDMA), 1) void rpm_tile_pl_kernel(
 #endif
     }
     if (grp < 4) { RPM_PTRC(jt, grp * 4 + 3); }
+    if (jt == n_iter - 1) { RPM_PEDGE_MAX(23); }
   }
 }
 

@@ -1,11 +1,12 @@
-"""Timeline of rpm_tile_pl_kernel's first two tiles per workgroup (diagnostic build, perf exploration only).
-Run on the GPU box:  python tools/trace_pipeline.py [instances [launch|quadrotor]]"""
+"""Timeline of rpm_tile_pl_kernel's first two tiles per workgroup and of its launch edges (diagnostic build, perf
+exploration only).  Run on the GPU box:  python tools/trace_pipeline.py [instances [launch|quadrotor]]
+(64 launch is the bench shape; RPM_DIAG_LIB=<path> traces another diagnostic build of the library)."""
 import os
 import sys
 
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, root)
-os.environ["RPM_HIP_LIB"] = os.path.join(root, "lpopc_amd", "csrc", "librpm_hip_diag.so")
+os.environ["RPM_HIP_LIB"] = os.environ.get("RPM_DIAG_LIB") or os.path.join(root, "lpopc_amd", "csrc", "librpm_hip_diag.so")
 os.environ["RPM_DIAG_TRACE"] = out = os.path.join(root, "gpurun_out", "trace_pl.bin")
 os.makedirs(os.path.dirname(out), exist_ok=True)
 import numpy as np
@@ -61,3 +62,18 @@ for j in (0, 1):
     stat("tile %d: LDS reads + D.X" % j, t[:, j, 25] - t[:, j, 24])
     stat("tile %d: perturb + dynamics" % j, t[:, j, 26] - t[:, j, 25])
     stat("tile %d: J, transform, g + J stores" % j, t[:, j, 27] - t[:, j, 26])
+
+# launch edges, every half (words of a half's first row: 22 the last tile's barrier A, 23 the end of the last tile's last
+# pass; 28 + d the DMA wave d's s_waitcnt in front of barrier A summed over the half's tiles, the same word of the second
+# row the longest single one)
+print("launch edges (%d halves):" % G)
+first = np.minimum(t[:, 0, 17], t[:, 0, 1])   # tile 0: the DMA waves' constant stores issued / role 0's g stores
+stat("first store issued (rel. first start)", first - t00)
+stat("first store issued (rel. own start)", first - t[:, 0, 31])
+stat("last tile: barrier A (rel. first start)", t[:, 0, 22] - t00)
+stat("last tile: A -> end of its last pass", t[:, 0, 23] - t[:, 0, 22])
+stat("last tile: end of its last pass (rel. first start)", t[:, 0, 23] - t00)
+print("  last tile: latest A %.2f, latest end %.2f" % (t[:, 0, 22].max() - t00, t[:, 0, 23].max() - t00))
+for d in range(2):
+    stat("dma wave %d: s_waitcnt before A, sum over tiles" % d, t[:, 0, 28 + d])
+    stat("dma wave %d: s_waitcnt before A, longest" % d, t[:, 1, 28 + d])
