@@ -223,11 +223,6 @@ void device_destroy(Engine& e) {
   e.dev = nullptr;
 }
 
-static size_t tile_lds_doubles(const Engine& e, int NX, int NU, int NC) {
-  size_t n = size_t(NX) * e.max_span + size_t(NU) * e.tile_nodes + e.max_drow + size_t(NX + NC) * e.tile_nodes + size_t(NX) * e.tile_nodes;
-  return n < 64 ? 64 : n;
-}
-
 int device_init(Engine& e, int device_id) {
   if (e.dev) {
     if (e.dev->device_id == device_id) return RPM_OK;
@@ -321,7 +316,7 @@ int device_init(Engine& e, int device_id) {
 #endif
   ProblemDims pd;
   problem_dims(e.problem_id, &pd);
-  d->lds_bytes = tile_lds_doubles(e, pd.nx, pd.nu, pd.nc) * sizeof(double);
+  d->lds_bytes = size_t(std::max(TileLds(pd.nx, pd.nu, pd.nc, e.tile_nodes, e.max_span, e.max_drow).total, 64)) * sizeof(double);   // >= 64: endpoint workgroups keep their unperturbed outputs there
   if (d->lds_bytes > 160 * 1024) {
     e.err = "mesh interval too large for the LDS-staged D tile (reduce nodes per interval)";
     return RPM_E_UNSUPPORTED;

@@ -47,6 +47,28 @@ struct KParams {
   int* chk;                             // host-pointer path: two host-visible words ORed with "a stored g / Jacobian value is NaN/Inf"; else NULL
 };
 
+// Dynamic LDS of rpm_tile_kernel and rpm_tile_rl_kernel (tiles of T nodes): offsets in doubles.  The kernels carve their
+// arrays by it and device_init sizes the launch by `total`.
+struct TileLds {
+  int Xs;      // [nx][max_span]  state-matrix rows the tile's D rows touch
+  int Us;      // [nu][T]
+  int Ds;      // the tile's D rows, row-major per node (max_drow)
+  int Fb;      // [nx + nc][T] unperturbed f and c
+  int DXs;     // [nx][T] D.X of the tile (matrix-core variant of rpm_tile_kernel; always reserved)
+  int total;
+  __host__ __device__ constexpr TileLds(int nx, int nu, int nc, int T, int max_span, int max_drow)
+      : Xs(0), Us(Xs + nx * max_span), Ds(Us + nu * T), Fb(Ds + max_drow), DXs(Fb + (nx + nc) * T), total(DXs + nx * T) {}
+};
+// pins: every array starts where the one before it ends, and the total is the formula the launches have always been sized by
+constexpr bool tile_lds_pinned(int nx, int nu, int nc, int T, int span, int drow) {
+  const TileLds L(nx, nu, nc, T, span, drow);
+  return L.Xs == 0 && L.Us == L.Xs + nx * span && L.Ds == L.Us + nu * T && L.Fb == L.Ds + drow && L.DXs == L.Fb + (nx + nc) * T &&
+         L.total == L.DXs + nx * T && L.total == nx * span + nu * T + drow + (nx + nc) * T + nx * T;
+}
+static_assert(tile_lds_pinned(LaunchProblem::NX, LaunchProblem::NU, LaunchProblem::NC, 64, 73, 64 * 9) &&   // odd span: Us on an odd double
+                  tile_lds_pinned(QuadrotorProblem::NX, QuadrotorProblem::NU, QuadrotorProblem::NC, 16, 40, 16 * 41),
+              "TileLds: an array overlaps its neighbour or the total changed");
+
 struct HParams {
   const HessPairDev* pairs;
   const HessPhaseDev* phases;
@@ -85,7 +107,7 @@ struct Device {
   bool cache_valid = false;     // d_g / d_values hold the pair of the x last uploaded
   std::vector<const double*> const_filled;   // device `values` arrays whose constant block this engine has written (option "persistent_values")
   size_t lds_bytes = 0;
-  int pl_slots = 0;             // resident workgroups the pipelined kernel is launched with (2 per CU)
+  int pl_slots = 0;             // resident halves of the pipelined kernel on this device (occupancy query: per CU x CUs)
   size_t pl_lds = 0;
   bool pl_ok = false;           // the mesh fits rpm_tile_pl_kernel's register staging
   // exact-Hessian tables

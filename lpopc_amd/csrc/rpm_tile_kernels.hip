@@ -263,6 +263,18 @@ __device__ __forceinline__ void store_defect(int sv, double dx, double tspan, co
   if (CHK) chk_note(bad_g, dfc);
 }
 
+// XCD-aware order: workgroups b, b+8, b+16, ... are dealt to the same XCD, so workgroup b of `count` takes place
+// xcd_place(b, count) in the tile order and each XCD gets a contiguous run of tiles; neighbouring 128-byte pieces of every
+// Jacobian block then meet in one L2 and leave it as longer contiguous write-backs (speed only, correctness does not depend
+// on placement)
+__device__ __forceinline__ int xcd_place(int b, int count) {
+  const int per = count >> 3, rem = count & 7, xcd = b & 7;
+  return xcd * per + (xcd < rem ? xcd : rem) + (b >> 3);
+}
+
+// a wave-uniform field of a tile record staged as ints (in LDS or in the constant address space)
+#define RPM_REC(rec, f) __builtin_amdgcn_readfirstlane((rec)[offsetof(TileDev, f) / 4])
+
 // ------------------------------------------------------------------------------------------
 template <class Prob, int T, bool WG, bool WJ, bool AN, bool DXM = false>
 __global__ void rpm_tile_kernel(const KParams K, const double* __restrict__ xall,
@@ -282,19 +294,11 @@ __global__ void rpm_tile_kernel(const KParams K, const double* __restrict__ xall
     endpoint_block<Prob, WG, WJ, AN>(K, K.tasks[int(blockIdx.x) - K.n_my_tiles], x, g, vals, lds, int(blockIdx.y));
     return;
   }
-  // XCD-aware tile order: workgroups b, b+8, b+16, ... are dealt to the same XCD, so give each XCD a
-  // contiguous run of tiles; neighbouring 128-byte pieces of every Jacobian block then meet in one L2
-  // and leave it as longer contiguous write-backs (speed only, correctness does not depend on placement)
-  const int nt = K.n_my_tiles, per = nt >> 3, rem = nt & 7, xcd = int(blockIdx.x) & 7, slot = int(blockIdx.x) >> 3;
-  const int tix = xcd * per + (xcd < rem ? xcd : rem) + slot;
-  const TileDev tl = K.tiles[tix];
+  const TileDev tl = K.tiles[xcd_place(int(blockIdx.x), K.n_my_tiles)];
   const TileDev& ph = tl;   // the phase fields the kernel needs are replicated in the tile record
   const auto c = (const __attribute__((address_space(4))) double*)(K.consts + size_t(blockIdx.y) * K.consts_stride);   // constant address space: scalar loads
-  double* Xs = lds;                          // [NX][max_span]  state-matrix rows the tile's D rows touch
-  double* Us = Xs + NX * K.max_span;         // [NU][T]
-  double* Ds = Us + NU * T;                  // the tile's D rows, row-major per node
-  double* Fb = Ds + K.max_drow;              // [NO][T] unperturbed f and c
-  double* DXs = Fb + NO * T;                 // [NX][T] D.X of the tile (MFMA variant only)
+  const TileLds L(NX, NU, NC, T, K.max_span, K.max_drow);
+  double *Xs = lds + L.Xs, *Us = lds + L.Us, *Ds = lds + L.Ds, *Fb = lds + L.Fb, *DXs = lds + L.DXs;
 
   // ---- issue the loads nothing depends on first: this thread's node record and its share of the
   //      constant-block sources (stored at the very end) ----
@@ -514,14 +518,11 @@ __global__ __launch_bounds__(T* RG) void rpm_tile_rl_kernel(const KParams K, con
     endpoint_block<Prob, WG, WJ, AN>(K, K.tasks[int(blockIdx.x) - K.n_my_tiles], x, g, vals, lds, int(blockIdx.y));
     return;
   }
-  const int nt = K.n_my_tiles, per = nt >> 3, rem = nt & 7, xcd = int(blockIdx.x) & 7, slot = int(blockIdx.x) >> 3;
-  const TileDev tl = K.tiles[xcd * per + (xcd < rem ? xcd : rem) + slot];
+  const TileDev tl = K.tiles[xcd_place(int(blockIdx.x), K.n_my_tiles)];
   const TileDev& ph = tl;
   const auto c = (const __attribute__((address_space(4))) double*)(K.consts + size_t(blockIdx.y) * K.consts_stride);   // constant address space: scalar loads
-  double* Xs = lds;
-  double* Us = Xs + NX * K.max_span;
-  double* Ds = Us + NU * T;
-  double* Fb = Ds + K.max_drow;
+  const TileLds L(NX, NU, NC, T, K.max_span, K.max_drow);
+  double *Xs = lds + L.Xs, *Us = lds + L.Us, *Ds = lds + L.Ds, *Fb = lds + L.Fb;
   const int kk = tid % T, grp = __builtin_amdgcn_readfirstlane(tid / T);   // a wave is one role group: roles are wave-uniform (scalar branches, scalar block offsets)
   const int kc = kk < tl.cnt ? kk : tl.cnt - 1;
   const int k = tl.k0 + kc;
@@ -682,6 +683,41 @@ __global__ __launch_bounds__(T* RG) void rpm_tile_rl_kernel(const KParams K, con
 // share <= PL_CMAX doubles (it passes through registers of the DMA waves), 2 NX + 3 <= 64 (endpoint perturbations
 // fit one wave).
 constexpr int PL_CMAX = 1280, PL_REC = 32;   // a tile's constant share: at most PL_CMAX doubles
+static_assert(sizeof(TileDev) / sizeof(int) < PL_REC, "tile record plus the instance index must fit the staged record");
+static_assert(sizeof(TileDev) % 8 == 0, "the tile record is copied as doubles");
+
+// Dynamic LDS of rpm_tile_pl_kernel, offsets in doubles (a tile is 64 nodes).  A half of a workgroup owns one block of
+// `half` doubles: two staging buffers of `stage` doubles each, then Fb, the two ready words and (dx_mode 1) DXs.  The kernel
+// carves its arrays by it; the host sizes the launch by pl_shape().NH x half.
+struct PlLds {
+  // one staging buffer: record (TileDev, then the instance index), record of the half's tile after this one (PL_REC ints each)
+  // | t0 tf p.. (even count) | X [nx][max_span] | U [nu][64] | D rows (max_drow) | tau [64] | diag of D [64] | node records
+  // [64] | share of the constant list (max_cshare; launches with a Jacobian); `stage` is its size
+  int rec, next, tt, X, U, D, tau, diag, nodes, cv, stage;
+  // a half's block: 2 staging buffers | Fb [nx + nc][64] | fb_ready, dx_ready (ints) | dx_mode 1: DXs [nx][64]; `half` is its size
+  int Fb, ready, DXs, half;
+  __host__ __device__ constexpr PlLds(int nx, int nu, int nc, int nq, int max_span, int max_drow, int max_cshare, bool with_jac,
+                                      bool dxm)
+      : rec(0), next(PL_REC / 2), tt(PL_REC), X(tt + 2 + ((nq + 1) & ~1)), U(X + nx * max_span), D(U + nu * 64),
+        tau(D + max_drow), diag(tau + 64), nodes(diag + 64), cv(nodes + 2 * 64), stage(cv + (with_jac ? max_cshare : 0)),
+        Fb(2 * stage), ready(Fb + (nx + nc) * 64), DXs(ready + 2), half(DXs + (dxm ? nx * 64 : 0)) {}
+};
+// pins: every array starts where the one before it ends, and the two sizes are the formulas the launches have always been
+// sized by
+constexpr bool pl_lds_pinned(int nx, int nu, int nc, int nq, int span, int drow, int cshare, bool wj, bool dxm) {
+  const PlLds L(nx, nu, nc, nq, span, drow, cshare, wj, dxm);
+  const int nqe = (nq + 1) & ~1;
+  return L.rec == 0 && L.next == L.rec + PL_REC / 2 && L.tt == L.next + PL_REC / 2 && L.X == L.tt + 2 + nqe &&
+         L.U == L.X + nx * span && L.D == L.U + nu * 64 && L.tau == L.D + drow && L.diag == L.tau + 64 &&
+         L.nodes == L.diag + 64 && L.cv == L.nodes + 2 * 64 && L.stage == L.cv + (wj ? cshare : 0) && L.Fb == 2 * L.stage &&
+         L.ready == L.Fb + (nx + nc) * 64 && L.DXs == L.ready + 2 && L.half == L.DXs + (dxm ? nx * 64 : 0) &&
+         L.stage == PL_REC + 2 + nqe + nx * span + nu * 64 + drow + 4 * 64 + (wj ? cshare : 0) &&
+         L.half == 2 * L.stage + (nx + nc) * 64 + 2 + (dxm ? nx * 64 : 0);
+}
+static_assert(pl_lds_pinned(LaunchProblem::NX, LaunchProblem::NU, LaunchProblem::NC, 0, 73, 64 * 9, 1024, true, false) &&   // odd span: U on an odd double
+                  pl_lds_pinned(LaunchProblem::NX, LaunchProblem::NU, LaunchProblem::NC, 1, 80, 64 * 17, 1280, true, true) &&
+                  pl_lds_pinned(QuadrotorProblem::NX, QuadrotorProblem::NU, QuadrotorProblem::NC, 0, 65, 64 * 65, 640, false, true),
+              "PlLds: an array overlaps its neighbour or a size changed");
 typedef double d2u __attribute__((ext_vector_type(2), aligned(8)));   // a pair of doubles at 8-byte alignment
 #define RPM_GPTR(p) ((const __attribute__((address_space(1))) void*)(p))
 #define RPM_LPTR(p) ((__attribute__((address_space(3))) void*)(p))
@@ -701,8 +737,8 @@ __device__ __forceinline__ void pl_dma_run(const double* gsrc, double* ldst, int
 }
 
 
-// A tile's share of the constant Doffdiag block (LpNLPWrapper.cpp:715-718) out of the staged buffer `cur` (record at its
-// start, the share at cv): NX copies, c_stride apart, into the instance's values array; the share is dealt in 128-double
+// A tile's share of the constant Doffdiag block (LpNLPWrapper.cpp:715-718) out of the staged buffer (record at `cur`, the
+// share at cv_src): NX copies, c_stride apart, into the instance's values array; the share is dealt in 128-double
 // chunks to NPART waves (this one is `part`).
 // 16-byte stores that start on 128-byte lines of the destination: misaligned by 32 B the same stream reaches 3.6 instead
 // of 5.4 TB/s, by 64 B 5.1 (tools/ubench/store_pattern.py).  `head` elements bring the first copy to a line boundary (the
@@ -713,10 +749,10 @@ __device__ __forceinline__ void pl_const_stores(const double* cur, const double*
                                                 long long sv, int lane, int part) {
   constexpr int CCH = (PL_CMAX / 128 + NPART - 1) / NPART;   // 128-double chunks per wave
   const int* rec = reinterpret_cast<const int*>(cur);
-  const int c_dst0 = __builtin_amdgcn_readfirstlane(rec[offsetof(TileDev, c_dst0) / 4]);
+  const int c_dst0 = RPM_REC(rec, c_dst0);
   const int inst = __builtin_amdgcn_readfirstlane(rec[inst_word]);
-  const int c_cnt = __builtin_amdgcn_readfirstlane(rec[offsetof(TileDev, c_cnt) / 4]);
-  const int c_stride = __builtin_amdgcn_readfirstlane(rec[offsetof(TileDev, c_stride) / 4]);
+  const int c_cnt = RPM_REC(rec, c_cnt);
+  const int c_stride = RPM_REC(rec, c_stride);
   double* __restrict__ cdst = vall + size_t(inst) * sv + c_dst0;
   const int head = min(int((16 - ((reinterpret_cast<size_t>(cdst) >> 3) & 15)) & 15), c_cnt);   // to a 128-byte line
   d2u cv[CCH];
@@ -771,39 +807,31 @@ __global__ __launch_bounds__(NH * 64 * (RG + NDMA), 1) void rpm_tile_pl_kernel(
   constexpr int HT = 64 * (RG + NDMA);   // threads of one half
   constexpr int NX = Prob::NX, NU = Prob::NU, NC = Prob::NC, NQ = prob_nq<Prob>::value;
   constexpr int NXs = NX > 0 ? NX : 1, NUs = NU + NQ > 0 ? NU + NQ : 1;
-  constexpr int NQE = (NQ + 1) & ~1;   // the staged [t0 tf p..] run, padded to an even count
   constexpr int NO = NX + NC, NV = NX + NU + 1 + NQ, NB = NX + NU + 2 + NQ;
   constexpr int R = WJ ? NV + 1 : (NX > 0 ? NX : 1);
   constexpr int NCs = NC > 0 ? NC : 1;
   constexpr int NTHR = T * RG;
   constexpr int NREC = int(sizeof(TileDev) / sizeof(int));
-  static_assert(NREC < PL_REC, "tile record plus the instance index must fit the staged record");
   extern __shared__ double lds_all[];
   // the halves of a workgroup are independent (own tiles, own LDS); they only share the barriers
   const int half = NH > 1 ? __builtin_amdgcn_readfirstlane(int(threadIdx.x) / HT) : 0;   // wave-uniform
   const int tid = int(threadIdx.x) - half * HT;
-  // XCD-aware order (as in rpm_tile_kernel): workgroups b, b+8, b+16, ... are dealt to the same XCD, so give each XCD a
-  // contiguous run of halves; the tiles a round of the launch works on (w + j G over all w) then leave each XCD's L2 as
-  // contiguous pieces of every Jacobian block instead of 2-tile pieces interleaved with the other seven XCDs', and the
-  // halves end their last tiles together (102.3 against 108.9 us per 64-iterate step; correctness
-  // does not depend on placement)
-  const int nb = int(gridDim.x), xcd = int(blockIdx.x) & 7, per = nb >> 3, rem = nb & 7;
-  const int wg = xcd * per + (xcd < rem ? xcd : rem) + (int(blockIdx.x) >> 3);   // this workgroup's place in the tile order
+  // XCD-aware order (xcd_place), here of halves: the tiles a round of the launch works on (w + j G over all w) leave each
+  // XCD's L2 as contiguous pieces of every Jacobian block instead of 2-tile pieces interleaved with the other seven XCDs',
+  // and the halves end their last tiles together (102.3 against 108.9 us per 64-iterate step)
+  const int nb = int(gridDim.x), wg = xcd_place(int(blockIdx.x), nb);   // this workgroup's place in the tile order
   const int G = NH * nb, w = NH * wg + half;
   const int nt = K.n_my_tiles;
   const int W = nt * n_inst;
   const int n_iter = w < W ? (W - w + G - 1) / G : 0;                 // tiles w, w + G, ... of this half
   const int n_iter_wg = (W - NH * wg + G - 1) / G;                    // of half 0: the barrier count of the workgroup
-  // one staging buffer (doubles): record, next tile's record | t0 tf | X rows | U rows | D rows | tau | diag | node
-  // records | const share
-  const int S_TT = PL_REC, S_X = S_TT + 2 + NQE, S_U = S_X + NX * K.max_span, S_D = S_U + NU * T;
-  const int S_TAU = S_D + K.max_drow, S_DG = S_TAU + T, S_ND = S_DG + T, S_CV = S_ND + 2 * T;
-  const int S_SIZE = S_CV + (WJ ? K.max_cshare : 0);
-  double* lds = lds_all + half * (2 * S_SIZE + (NX + NC) * T + 2 + (DXM ? NX * T : 0));
-  double* Fb = lds + 2 * S_SIZE;             // [NO][T] unperturbed f and c of the current tile
-  int* fb_ready = reinterpret_cast<int*>(Fb + (NX + NC) * T);   // tile count for which Fb holds the unperturbed dynamics
-  int* dx_ready = fb_ready + 1;                                 // dx_mode 1: DMA waves that have published their rows of D.X, summed over tiles
-  double* DXs = Fb + (NX + NC) * T + 2;                         // dx_mode 1: [NX][T] D.X of the current tile (matrix cores)
+  const PlLds L(NX, NU, NC, NQ, K.max_span, K.max_drow, K.max_cshare, WJ, DXM);
+  // (const locals for what the lambdas and the tile loops use: read as L.x there, 22 instantiations allocate registers differently)
+  const int S_TT = L.tt, S_X = L.X, S_U = L.U, S_D = L.D, S_TAU = L.tau, S_DG = L.diag, S_ND = L.nodes, S_CV = L.cv, S_SIZE = L.stage;
+  double* lds = lds_all + half * L.half;
+  double *Fb = lds + L.Fb, *DXs = lds + L.DXs;
+  int* fb_ready = reinterpret_cast<int*>(lds + L.ready);   // tile count for which Fb holds the unperturbed dynamics
+  int* dx_ready = fb_ready + 1;                            // dx_mode 1: DMA waves that have published their rows of D.X, summed over tiles
 #ifdef RPM_DIAG
 #define RPM_PTRC(j, slot)                                                           \
   if (K.trace && (threadIdx.x & 63) == 0 && (j) < 2) K.trace[size_t(w) * 64 + (j)*32 + (slot)] = wall_clock64()
@@ -828,27 +856,23 @@ __global__ __launch_bounds__(NH * 64 * (RG + NDMA), 1) void rpm_tile_pl_kernel(
   // for global memory; only the first tile of a workgroup reads its record from HBM.
   struct TileRuns { int k0, cnt, span0, span_len, drow0, drow_len, N, x_state0, x_control0, x_t0, node0, c_src0, c_cnt; };
   auto runs_of = [&](auto p) {   // p: the record as ints, in LDS or (first tile) in the constant address space
-    TileRuns r;
-#define RPM_RF(f) r.f = __builtin_amdgcn_readfirstlane(p[offsetof(TileDev, f) / 4])
-    RPM_RF(k0); RPM_RF(cnt); RPM_RF(span0); RPM_RF(span_len); RPM_RF(drow0); RPM_RF(drow_len); RPM_RF(N);
-    RPM_RF(x_state0); RPM_RF(x_control0); RPM_RF(x_t0); RPM_RF(node0); RPM_RF(c_src0); RPM_RF(c_cnt);
-#undef RPM_RF
-    return r;
+    return TileRuns{RPM_REC(p, k0), RPM_REC(p, cnt), RPM_REC(p, span0), RPM_REC(p, span_len), RPM_REC(p, drow0),
+                    RPM_REC(p, drow_len), RPM_REC(p, N), RPM_REC(p, x_state0), RPM_REC(p, x_control0), RPM_REC(p, x_t0),
+                    RPM_REC(p, node0), RPM_REC(p, c_src0), RPM_REC(p, c_cnt)};
   };
   auto stage = [&](auto np_c, int part, int lane, int item, double* buf, const TileRuns tl) {
     constexpr int NP = decltype(np_c)::value;
     const int inst = item / nt, tidx = item - inst * nt;
     const double* __restrict__ x = xall + size_t(inst) * K.n;
-    static_assert(NREC % 2 == 0 && sizeof(TileDev) % 8 == 0, "the tile record is copied as doubles");
     int rot = 0;
     auto run = [&](const double* gsrc, double* ldst, int len) {
       pl_dma_run<NP>(gsrc, ldst, len, lane, (part + NP - (rot++ % NP)) % NP);
     };
-    if (part == 0 && lane == 0) reinterpret_cast<int*>(buf)[NREC] = inst;   // before the direct loads: an LDS write after them waits for them
-    run(reinterpret_cast<const double*>(K.tiles + tidx), buf, NREC / 2);
+    if (part == 0 && lane == 0) reinterpret_cast<int*>(buf + L.rec)[NREC] = inst;   // before the direct loads: an LDS write after them waits for them
+    run(reinterpret_cast<const double*>(K.tiles + tidx), buf + L.rec, NREC / 2);
     if (item + G < W) {   // the record of this workgroup's tile after this one
       const int item2 = item + G, inst2 = item2 / nt;
-      run(reinterpret_cast<const double*>(K.tiles + (item2 - inst2 * nt)), buf + PL_REC / 2, NREC / 2);
+      run(reinterpret_cast<const double*>(K.tiles + (item2 - inst2 * nt)), buf + L.next, NREC / 2);
     }
     run(x + tl.x_t0, buf + S_TT, 2 + NQ);   // t0, tf and the static parameters behind them
 #pragma unroll
@@ -905,10 +929,10 @@ __global__ __launch_bounds__(NH * 64 * (RG + NDMA), 1) void rpm_tile_pl_kernel(
         // (and the fused multiply-add) differ from the reference's ascending-column loop: agreement to rounding only.
         if (j < n_iter) {
           typedef double d4 __attribute__((ext_vector_type(4)));
-          const int* rec = reinterpret_cast<const int*>(cur);
-          const int cnt = __builtin_amdgcn_readfirstlane(rec[offsetof(TileDev, cnt) / 4]);
-          const int span0 = __builtin_amdgcn_readfirstlane(rec[offsetof(TileDev, span0) / 4]);
-          const int drow0 = __builtin_amdgcn_readfirstlane(rec[offsetof(TileDev, drow0) / 4]);
+          const int* rec = reinterpret_cast<const int*>(cur + L.rec);
+          const int cnt = RPM_REC(rec, cnt);
+          const int span0 = RPM_REC(rec, span0);
+          const int drow0 = RPM_REC(rec, drow0);
           const NodeDev* ND = reinterpret_cast<const NodeDev*>(cur + S_ND);
           const double* Ds = cur + S_D;
           const double* Xs = cur + S_X;
@@ -946,10 +970,10 @@ __global__ __launch_bounds__(NH * 64 * (RG + NDMA), 1) void rpm_tile_pl_kernel(
       // in their first pass and store nothing; then the next tile's loads.  (The order matters twice: an LDS read of
       // this wave after the direct-to-LDS loads would wait for them, and the Jacobian stores of the later passes
       // should not meet these in the memory system.)
-      if (WJ && !K.skip_const && j < n_iter) pl_const_stores<NX, NDMA>(cur, cur + S_CV, NREC, vall, K.sv, lane, dw);
+      if (WJ && !K.skip_const && j < n_iter) pl_const_stores<NX, NDMA>(cur + L.rec, cur + S_CV, NREC, vall, K.sv, lane, dw);
       RPM_PTRC(j, 17);
       if (j + 1 < n_iter) {
-        stage(std::integral_constant<int, NDMA>{}, dw, lane, w + (j + 1) * G, nxt, runs_of(reinterpret_cast<const int*>(cur) + PL_REC));
+        stage(std::integral_constant<int, NDMA>{}, dw, lane, w + (j + 1) * G, nxt, runs_of(reinterpret_cast<const int*>(cur + L.next)));
       }
       RPM_PTRC(j, 18);
     }
@@ -980,15 +1004,15 @@ __global__ __launch_bounds__(NH * 64 * (RG + NDMA), 1) void rpm_tile_pl_kernel(
     if (jt >= n_iter) continue;   // the other half still has a tile: keep the barrier count
     if (grp < 4) { RPM_PTRC(jt, grp * 4 + 0); }
     if (grp == 0 && jt == n_iter - 1) { RPM_PEDGE(22); }
-    const int* rec = reinterpret_cast<const int*>(cur);
-    const int k0 = __builtin_amdgcn_readfirstlane(rec[offsetof(TileDev, k0) / 4]);
-    const int cnt = __builtin_amdgcn_readfirstlane(rec[offsetof(TileDev, cnt) / 4]);
-    const int span0 = __builtin_amdgcn_readfirstlane(rec[offsetof(TileDev, span0) / 4]);
-    const int drow0 = __builtin_amdgcn_readfirstlane(rec[offsetof(TileDev, drow0) / 4]);
-    const int N = __builtin_amdgcn_readfirstlane(rec[offsetof(TileDev, N) / 4]);
-    const int phase_num = __builtin_amdgcn_readfirstlane(rec[offsetof(TileDev, phase_num) / 4]);
-    const int g0 = __builtin_amdgcn_readfirstlane(rec[offsetof(TileDev, g0) / 4]);
-    const int v_nl0 = __builtin_amdgcn_readfirstlane(rec[offsetof(TileDev, v_nl0) / 4]);
+    const int* rec = reinterpret_cast<const int*>(cur + L.rec);
+    const int k0 = RPM_REC(rec, k0);
+    const int cnt = RPM_REC(rec, cnt);
+    const int span0 = RPM_REC(rec, span0);
+    const int drow0 = RPM_REC(rec, drow0);
+    const int N = RPM_REC(rec, N);
+    const int phase_num = RPM_REC(rec, phase_num);
+    const int g0 = RPM_REC(rec, g0);
+    const int v_nl0 = RPM_REC(rec, v_nl0);
     const int inst = __builtin_amdgcn_readfirstlane(rec[NREC]);
     double* __restrict__ g = gall + size_t(inst) * K.sg;
     double* __restrict__ vals = vall + size_t(inst) * K.sv;
@@ -1142,6 +1166,13 @@ __global__ __launch_bounds__(NH * 64 * (RG + NDMA), 1) void rpm_tile_pl_kernel(
   }
 }
 
+// Dynamic LDS of a pipelined launch, in bytes.  The constant share is reserved in every launch, also those without a
+// Jacobian (the occupancy query of tile_pipeline_setup was made with it).
+static size_t pl_lds_bytes(int nx, int nu, int nc, int nq, const KParams& kp, bool dxm) {
+  const PlLds L(nx, nu, nc, nq, kp.max_span, kp.max_drow, kp.max_cshare, true, dxm);
+  return size_t(pl_shape(nx + nu + 2 + nq).NH) * L.half * sizeof(double);
+}
+
 // Occupancy, LDS size and eligibility of the pipelined kernel for this engine; called by device_init.
 void tile_pipeline_setup(Engine& e, Device* d, const ProblemDims& pd, int device_id) {
   // rpm_tile_pl_kernel: persistent workgroups of RG compute + 2 DMA waves; as many per CU as the occupancy
@@ -1149,12 +1180,11 @@ void tile_pipeline_setup(Engine& e, Device* d, const ProblemDims& pd, int device
     int ncu = 0;
     if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device_id) != hipSuccess || ncu <= 0) ncu = 256;
     const int max_c = d->kp.max_cshare;
-    const size_t stage = size_t(PL_REC + 2 + ((pd.nq + 1) & ~1)) + size_t(pd.nx) * e.max_span + size_t(pd.nu) * 64 + e.max_drow + 4 * 64 + max_c;
     int per_cu = 0;
     with_problem(e.problem_id, [&](auto prob) {
       using P = decltype(prob);
       constexpr PlShape S = pl_shape(P::NX + P::NU + 2 + prob_nq<P>::value);
-      d->pl_lds = S.NH * (2 * stage + size_t(pd.nx + pd.nc) * 64 + 2) * sizeof(double);
+      d->pl_lds = pl_lds_bytes(pd.nx, pd.nu, pd.nc, pd.nq, d->kp, false);
       if (d->pl_lds > 160 * 1024) return;
       auto kern = rpm_tile_pl_kernel<P, S.NH, S.RG, S.NDMA, true, true, false>;
       if (d->pl_lds > 64 * 1024)
@@ -1191,15 +1221,11 @@ static hipError_t launch_tiles(const Engine& e, Kern kern, int threads, const KP
   return hipGetLastError();
 }
 
-// extra LDS of the dx_mode 1 variant: one [NX][64] D.X buffer per half
-static size_t pl_dxm_extra(const Engine& e) {
+// dx_mode 1 on the pipelined kernel: finite-difference mode only (as in the one-role kernel), and the D.X buffers must fit
+static bool pl_dxm_ok(const Engine& e) {
   ProblemDims pd;
   problem_dims(e.problem_id, &pd);
-  return size_t(pd.nx + pd.nu + 2 + pd.nq <= 12 ? 2 : 1) * size_t(pd.nx) * 64 * sizeof(double);
-}
-// dx_mode 1 on the pipelined kernel: finite-difference mode only (as in the one-role kernel), and the extra buffer must fit
-static bool pl_dxm_ok(const Engine& e) {
-  return e.first_derive != RPM_DERIVE_ANALYTIC && e.dev->pl_lds + pl_dxm_extra(e) <= 160 * 1024;
+  return e.first_derive != RPM_DERIVE_ANALYTIC && pl_lds_bytes(pd.nx, pd.nu, pd.nc, pd.nq, e.dev->kp, true) <= 160 * 1024;
 }
 
 template <class Prob, bool WG, bool WJ, bool AN, bool DXM, bool STG = false>
@@ -1215,7 +1241,7 @@ static hipError_t launch_tile_pl(const Engine& e, const KParams& kp, const doubl
   const Device& d = *e.dev;
   constexpr PlShape S = pl_shape(Prob::NX + Prob::NU + 2 + prob_nq<Prob>::value);
   auto kern = rpm_tile_pl_kernel<Prob, S.NH, S.RG, S.NDMA, WG, WJ, AN, DXM, STG>;
-  const size_t lds = d.pl_lds + (DXM ? size_t(S.NH) * Prob::NX * 64 * sizeof(double) : 0);
+  const size_t lds = pl_lds_bytes(Prob::NX, Prob::NU, Prob::NC, prob_nq<Prob>::value, d.kp, DXM);
   hipError_t s = allow_lds(kern, lds);
   if (s != hipSuccess) return s;
   const long long W = (long long)d.kp.n_my_tiles * e.n_instances;
