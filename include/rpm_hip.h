@@ -204,6 +204,32 @@ int rpm_ph_refine_from_error(rpm_engine* e, int phase, const double* rel_err, do
                              int capacity, double* new_mesh_points, int* new_nodes_per_interval,
                              int* new_n_intervals, double* interval_error, int* no_more_refine);
 
+/* The estimate for a whole sweep: all phases and all n_instances instances of the engine at once, every instance with its
+ * own constants (rpm_set_instance_constants) and static parameters.  Per instance the arithmetic is rpm_solution_error's,
+ * sum by sum in the same order, so the results are the same bits.  Sizes (host only, no device needed): KT = sum over the
+ * phases of K_p, RT = sum over the phases of (N_p + K_p + 1) * nx_p.  A block of RT doubles holds the phases' relative_error
+ * matrices one after the other, each (N_p + K_p + 1) x nx_p column-major, as rpm_solution_error returns them and
+ * rpm_hpliu_refine takes them.  Results (any may be NULL):
+ *   interval_error  n_instances x KT, instance-major, phase after phase: the per-interval maxima, equal to rpm_ph_refine_mesh's;
+ *   rel_err_max     RT: element-wise maximum over the instances that instance_mask includes (NULL mask = all; a NaN stays).
+ *                   The instances of a sweep share one transcription, so they share the next mesh: the one the worst
+ *                   instance asks for, rpm_ph_refine_from_error(e, p, rel_err_max + offset of phase p, ...);
+ *   rel_err         n_instances x RT, every instance's block;
+ *   nonfinite       n_instances: 1 when the instance's block holds a NaN or Inf (instances that ended with status 3 or 5).
+ * An excluded instance (mask 0) is still estimated and reported; it only stays out of rel_err_max.
+ * The _dev form takes device arrays (x packed n_instances x n) and queues three launches (four above 64 instances) on `stream` (a hipStream_t, NULL =
+ * the legacy default stream).  The first call on an engine uploads the tables and allocates the workspace; every later call
+ * allocates nothing, copies nothing and never synchronises, so it can follow rpm_ipm_solve_dev on the caller's stream and be
+ * captured into a graph.  It cannot see its mask: with every instance excluded rel_err_max is all zeros.  The host-pointer
+ * form stages its arrays like the other host-pointer calls, blocks, and answers RPM_E_INVALID when rel_err_max is asked for
+ * and the mask excludes every instance.  Interval-sharded engines: RPM_E_UNSUPPORTED.  The calling thread's current device
+ * is restored.  Option "mesh_err_tile" (0 = automatic, 1, 2, 4, 8, 16): instances per workgroup. */
+int rpm_solution_error_batch_sizes(rpm_engine* e, int* n_intervals_total, long long* rel_doubles_total);
+int rpm_solution_error_batch_dev(rpm_engine* e, const double* d_x, const int* d_instance_mask, double* d_interval_error,
+                                 double* d_rel_err_max, double* d_rel_err, int* d_nonfinite, void* stream);
+int rpm_solution_error_batch(rpm_engine* e, const double* x, const int* instance_mask, double* interval_error,
+                             double* rel_err_max, double* rel_err, int* nonfinite);
+
 /* hp-Liu refinement: LiuHpMeshRefineAlg::RefineMesh, Core/LpLiuHpMeshRefineAlg.cpp:12-260 (with Reducing_N :438-481,
  * Increasing_N :379-436, Dividing_mesh :321-377, CanWeIncreaseN :606-681; Merging_mesh's verdict is unused by the
  * reference, equal-N satisfied neighbours always merge).  The object keeps the reference's histories (meshes with their
@@ -508,6 +534,12 @@ int rpm_sweep_share(const rpm_sweep* s, int share, int* first_instance, int* n_i
 int rpm_sweep_set_option(rpm_sweep* s, const char* key, double value);
 int rpm_sweep_set_bounds(rpm_sweep* s, int instance, const double* x_l, const double* x_u);   /* instance: 0 .. B - 1 */
 int rpm_sweep_solve(rpm_sweep* s, double* x, double* lambda, double* obj, int* status, int* iterations, double* kkt_error);
+/* rpm_solution_error_batch over all shares side by side (x: B x n, instance_mask: B or NULL, results as there with B for
+ * n_instances).  The shares' rel_err_max blocks are combined by element-wise maximum on the host, so the result is what one
+ * engine holding all B instances returns, bit for bit; a share whose instances are all excluded contributes nothing and is no
+ * error as long as one instance of the sweep is included. */
+int rpm_sweep_solution_error(rpm_sweep* s, const double* x, const int* instance_mask, double* interval_error,
+                             double* rel_err_max, double* rel_err, int* nonfinite);
 int rpm_sweep_get_stats(rpm_sweep* s, int* iterations, int* factorizations, int* trial_points);
 
 #ifdef __cplusplus

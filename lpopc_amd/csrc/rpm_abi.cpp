@@ -341,6 +341,40 @@ int rpm_ph_refine_mesh(rpm_engine* h, int phase, const double* x, double tol, in
   RPM_GUARD_END(e)
 }
 
+// ---- the estimate for every phase and every instance of the engine (a sweep), rpm_post_kernels.hip ----------------
+int rpm_solution_error_batch_sizes(rpm_engine* h, int* n_intervals_total, long long* rel_doubles_total) {
+  if (!h) return RPM_E_INVALID;
+  rpm::solution_error_batch_sizes(h->e, n_intervals_total, rel_doubles_total);
+  return RPM_OK;
+}
+
+int rpm_solution_error_batch_dev(rpm_engine* h, const double* d_x, const int* d_instance_mask, double* d_interval_error,
+                                 double* d_rel_err_max, double* d_rel_err, int* d_nonfinite, void* stream) {
+  if (!h) return RPM_E_INVALID;
+  Engine& e = h->e;
+  RPM_GUARD_BEGIN
+  if (!d_x) return fail(e, RPM_E_INVALID, "solution_error_batch_dev: d_x is NULL");
+  if (e.shard_mode == RPM_SHARD_INTERVALS && e.shard_world > 1) return fail(e, RPM_E_UNSUPPORTED, "solution_error_batch: not with interval sharding");
+  return rpm::dev_solution_error_batch(e, d_x, d_instance_mask, d_interval_error, d_rel_err_max, d_rel_err, d_nonfinite, stream);
+  RPM_GUARD_END(e)
+}
+
+int rpm_solution_error_batch(rpm_engine* h, const double* x, const int* instance_mask, double* interval_error,
+                             double* rel_err_max, double* rel_err, int* nonfinite) {
+  if (!h) return RPM_E_INVALID;
+  Engine& e = h->e;
+  RPM_GUARD_BEGIN
+  if (!x) return fail(e, RPM_E_INVALID, "solution_error_batch: x is NULL");
+  if (e.shard_mode == RPM_SHARD_INTERVALS && e.shard_world > 1) return fail(e, RPM_E_UNSUPPORTED, "solution_error_batch: not with interval sharding");
+  if (instance_mask && rel_err_max) {
+    bool any = false;
+    for (int b = 0; b < e.n_instances; ++b) any = any || instance_mask[b] != 0;
+    if (!any) return fail(e, RPM_E_INVALID, "solution_error_batch: rel_err_max asked for, but instance_mask excludes every instance");
+  }
+  return rpm::host_solution_error_batch(e, x, instance_mask, interval_error, rel_err_max, rel_err, nonfinite);
+  RPM_GUARD_END(e)
+}
+
 // ---- hp-Liu mesh refinement (second method) ------------------------------------
 struct rpm_hpliu {
   rpm::HpLiu h;
@@ -571,6 +605,9 @@ int rpm_set_option(rpm_engine* h, const char* key, int value) {
   } else if (k == "zero_copy") {
     if (value != 0 && value != 1) return fail(e, RPM_E_INVALID, "zero_copy must be 0 or 1");
     e.opt_zero_copy = value;
+  } else if (k == "mesh_err_tile") {
+    if (value != 0 && value != 1 && value != 2 && value != 4 && value != 8 && value != 16) return fail(e, RPM_E_INVALID, "mesh_err_tile must be 0 (auto), 1, 2, 4, 8 or 16");
+    e.opt_mesh_err_tile = value;
   } else if (k == "pipeline") {
     if (value < -1 || value > 1) return fail(e, RPM_E_INVALID, "pipeline must be -1 (auto), 0 or 1");
     e.opt_pipeline = value;
@@ -605,6 +642,7 @@ int rpm_get_option(rpm_engine* h, const char* key, int* value) {
   else if (k == "n_tiles") *value = int(e.tiles.size());
   else if (k == "role_loop") *value = e.role_looped ? 1 : 0;
   else if (k == "pipeline") *value = e.opt_pipeline;
+  else if (k == "mesh_err_tile") *value = e.opt_mesh_err_tile;
   else if (k == "stage_roles") *value = e.opt_stage_roles;
   else if (k == "const_once") *value = e.opt_const_once;
   else if (k == "instance_align") *value = e.opt_instance_align;

@@ -213,6 +213,7 @@ void device_destroy(Engine& e) {
   if (d->h_flags2) (void)hipHostFree(d->h_flags2);   // d_flags2 is its device alias
   host_path_destroy(d);
   exchange_destroy(d);
+  mesh_batch_destroy(d);
   rpm_pin_release_owner(&e);   // this engine's holds; pages another engine still addresses stay registered
   dev_stage_destroy(d);
   for (auto& row : d->segtab)

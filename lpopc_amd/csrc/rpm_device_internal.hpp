@@ -122,6 +122,7 @@ struct Device {
   int hess_threads = 0;
   void* host_path = nullptr;    // state of the host-pointer delivery (rpm_host_path.hip)
   void* exchange = nullptr;     // pack / unpack tables of the interval-sharded exchange (rpm_peer.hip)
+  void* mesh_batch = nullptr;   // tables and workspace of the batched mesh-error estimate (rpm_post_kernels.hip), built on first use
   struct SegTable { void* ptr = nullptr; int count = 0; int stride = -1; };
   SegTable segtab[2][2];        // [g|values][pack|unpack] run tables of the interval sharding
 };
@@ -188,6 +189,7 @@ void host_new_x(Engine& e);
 void dev_stage_synced(Engine& e);    // the engine's stream was synchronised: every staging slot may be overwritten
 std::string dev_pin_last_error();
 void exchange_destroy(Device* d);    // rpm_peer.hip
+void mesh_batch_destroy(Device* d);  // rpm_post_kernels.hip
 
 // rpm_tile_kernels.hip: occupancy, LDS size and eligibility of the pipelined kernel for this engine (device_init)
 void tile_pipeline_setup(Engine& e, Device* d, const ProblemDims& pd, int device_id);

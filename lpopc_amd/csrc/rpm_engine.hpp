@@ -181,6 +181,7 @@ struct Engine {
   int opt_ipm_nested_group = 0;  // rpm_ipm_create: positions per group when the separator system of the nested dissection is cut again; 0 = automatic (only when it is >= 512 long)
   int opt_ipm_local_border = 1;  // rpm_ipm_create: an interval block carries only the rows of the global border that its interior has entries with (0: all of them)
   int opt_ipm_nested = -1;       // rpm_ipm_create: nested dissection of the KKT matrix over the mesh intervals (rpm_ipm.hpp): -1 when the structure allows, 0 never, 1 must
+  int opt_mesh_err_tile = 0;     // batched mesh-error estimate: instances per workgroup (0: as many of 8, 4, 2, 1 as the LDS tile holds)
   int ipm_attached = 0;          // rpm_ipm solvers built on this engine: they size their buffers from stride_g/values
   // solution kept by finalize_solution (LpopcIpopt.cpp:237-243)
   std::vector<double> sol_x, sol_lambda;
@@ -230,6 +231,13 @@ void build_mesh_err_tables(const PhaseHost& p, MeshErrTables& t);
 bool ph_refine(const PhaseHost& p, const double* rel, double tol, int nmin, int nmax, std::vector<double>& mesh,
                std::vector<int>& nodes, std::vector<double>& interval_error);
 int dev_solution_error(Engine& e, int phase, const double* x, double* rel_err);
+// the estimate for all phases and all instances of the engine (rpm_post_kernels.hip).  Sizes: KT = sum K_p, RT = sum rows_p * nx_p
+void solution_error_batch_sizes(const Engine& e, int* n_intervals_total, long long* rel_doubles_total);
+constexpr double mesh_err_max(double a, double v) { return (v > a || v != v) ? v : a; }   // element-wise maximum over instances: a NaN stays
+int dev_solution_error_batch(Engine& e, const double* d_x, const int* d_mask, double* d_interval_error, double* d_rel_err_max,
+                             double* d_rel_err, int* d_nonfinite, void* stream);
+int host_solution_error_batch(Engine& e, const double* x, const int* mask, double* interval_error, double* rel_err_max,
+                              double* rel_err, int* nonfinite);
 
 // rpm_shard.cpp: rank's contiguous runs of g (which=0) or of the Jacobian values (which=1)
 std::vector<rpm_segment> shard_segments(const Engine& e, int which, int rank, int* packed_len);

@@ -358,4 +358,456 @@ int dev_solution_error(Engine& e, int phase, const double* x, double* rel_err) {
   return RPM_OK;
 }
 
+// ------------------------------------------------------------------------------------------
+// The mesh-error estimate of a whole sweep: every phase and every instance of the engine in three launches, nothing but
+// the caller's arrays crossing the call.  Per instance b the arithmetic is that of rpm_mesh_err_kernel + rpm_mesh_rel_kernel
+// on x + b * n, sum by sum in the same order (-ffp-contract=off: same order, same bits), with the dynamics reading instance
+// b's constants and static parameters.  The interpolation / integration tables of all phases sit in one device block that
+// lives as long as the engine's other tables (Device::mesh_batch).
+struct MeshIvBatch {   // one mesh interval of any phase: MeshIvDev with offsets into the engine-wide tables
+  int n, istart, r0, q0, hs, hc, a;
+  int phase, rows;     // its phase and that phase's row count N + K + 1
+  int base;            // offset of the phase's rows x nx matrix inside an instance's block of RT doubles
+  int first, last;     // first / last interval of its phase
+};
+
+// Workgroup (interval, tile of TB instances).  `stage`: the interval's tables are copied to LDS once and serve all TB
+// instances; otherwise (tables too large next to the instance arrays) they are read from global memory as the one-instance
+// kernel reads them.  Items run q-fastest, so the lanes that share (instance, state) read one x column and store a run of
+// consecutive rows.
+template <class Prob>
+__global__ void rpm_mesh_err_batch_kernel(const KParams K, int B, int TB, int stage, long long RT, const double* __restrict__ x,
+                                          const MeshIvBatch* __restrict__ ivs, const double* gHs, const double* gSs,
+                                          const int* ghit_s, const double* gHc, const double* gSc, const int* ghit_c,
+                                          const double* gA, const double* gtt, double* __restrict__ fine_state,
+                                          double* __restrict__ integ, int* __restrict__ nonfinite) {
+  constexpr int NX = Prob::NX, NU = Prob::NU, NC = Prob::NC;
+  constexpr int NXs = NX > 0 ? NX : 1, NUs = NU > 0 ? NU : 1, NCs = NC > 0 ? NC : 1;
+  extern __shared__ __align__(16) double mesh_bsm[];
+  const MeshIvBatch v = ivs[blockIdx.x];
+  const int n = v.n, n1 = n + 1;
+  const int b0 = blockIdx.y * TB;
+  const int nb = B - b0 < TB ? B - b0 : TB;
+  const double *Hs = gHs + v.hs, *Hc = gHc + v.hc, *A = gA + v.a, *Ss = gSs + v.q0, *Sc = gSc + v.q0, *tt = gtt + v.q0;
+  const int *hit_s = ghit_s + v.q0, *hit_c = ghit_c + v.q0;
+  double* inst = mesh_bsm;
+  if (stage) {
+    double* lHs = mesh_bsm;
+    double* lHc = lHs + n1 * n1;
+    double* lA = lHc + n1 * n;
+    double* lSs = lA + n1 * n1;
+    double* lSc = lSs + n1;
+    double* ltt = lSc + n1;
+    int* lhit_s = reinterpret_cast<int*>(ltt + n1);
+    int* lhit_c = lhit_s + n1;
+    inst = ltt + 2 * n1;
+    for (int i = threadIdx.x; i < n1 * n1; i += blockDim.x) {
+      lHs[i] = Hs[i];
+      lA[i] = A[i];
+    }
+    for (int i = threadIdx.x; i < n1 * n; i += blockDim.x) lHc[i] = Hc[i];
+    for (int i = threadIdx.x; i < n1; i += blockDim.x) {
+      lSs[i] = Ss[i];
+      lSc[i] = Sc[i];
+      ltt[i] = tt[i];
+      lhit_s[i] = hit_s[i];
+      lhit_c[i] = hit_c[i];
+    }
+    Hs = lHs; Hc = lHc; A = lA; Ss = lSs; Sc = lSc; tt = ltt; hit_s = lhit_s; hit_c = lhit_c;
+    __syncthreads();
+  }
+  const int per = n1 * (2 * NX + NU);   // per instance: Xs [q * NX + s], Us [q * NU + j], Fs [q * NX + s]
+  const PhaseDev ph = K.phases[v.phase];
+  const int N = ph.N, M = N + 1, rows = v.rows;
+  if (blockIdx.x == 0 && nonfinite)     // the verdicts of this call start from 0 (rpm_mesh_rel_batch_kernel ORs into them)
+    for (int bi = threadIdx.x; bi < nb; bi += blockDim.x) nonfinite[b0 + bi] = 0;
+  for (int idx = threadIdx.x; idx < nb * n1 * NX; idx += blockDim.x) {
+    const int q = idx % n1, s = (idx / n1) % NXs, bi = idx / (n1 * NXs);
+    const size_t b = size_t(b0 + bi);
+    const double* col = x + b * K.n + ph.x_state0 + s * M + v.istart;
+    const int hit = hit_s[q];
+    double val;
+    if (hit >= 0) {
+      val = col[hit];
+    } else {
+      double acc = 0.0;
+      for (int j = 0; j < n1; ++j) acc += Hs[q + j * n1] * col[j];
+      val = acc / Ss[q];
+    }
+    inst[bi * per + q * NX + s] = val;
+    fine_state[b * RT + v.base + (v.r0 + q) + size_t(s) * rows] = val;
+  }
+  for (int idx = threadIdx.x; idx < nb * n1 * NU; idx += blockDim.x) {
+    const int q = idx % n1, j = (idx / n1) % NUs, bi = idx / (n1 * NUs);
+    const double* col = x + size_t(b0 + bi) * K.n + ph.x_control0 + j * N + v.istart;
+    const int hit = hit_c[q];
+    double val;
+    if (hit >= 0) {
+      val = col[hit];
+    } else {
+      double acc = 0.0;
+      for (int c = 0; c < n; ++c) acc += Hc[q + c * n1] * col[c];
+      val = acc / Sc[q];
+    }
+    inst[bi * per + n1 * NX + q * NU + j] = val;
+  }
+  __syncthreads();
+  for (int idx = threadIdx.x; idx < nb * n1; idx += blockDim.x) {
+    const int q = idx % n1, bi = idx / n1;
+    const double* xb = x + size_t(b0 + bi) * K.n;
+    const double* Xs = inst + bi * per;
+    const double* Us = Xs + n1 * NX;
+    double* Fs = inst + bi * per + n1 * (NX + NU);
+    const double t0 = xb[ph.x_t0];
+    const double tf = (xb[ph.x_t0 + 1] - t0) * (1.0 + 1) / 2 + t0;   // result->time's last entry, Nlp2OPConverter.cpp:58
+    const double half = (tf - t0) / 2;
+    double xs[NXs], us[NUs], f[NXs], cp[NCs];
+#pragma unroll
+    for (int s = 0; s < NX; ++s) xs[s] = Xs[q * NX + s];
+#pragma unroll
+    for (int j = 0; j < NU; ++j) us[j] = Us[q * NU + j];
+    const double t = half * tt[q] + half;   // t0 is not added, LpSolutionError.cpp:124
+    pf_dae<Prob>(ph.phase_num, t, xs, us, xb + ph.x_t0 + 2, K.consts + size_t(b0 + bi) * K.consts_stride, f, cp);
+#pragma unroll
+    for (int s = 0; s < NX; ++s) Fs[q * NX + s] = f[s] * ((tf - t0) / 2.0);
+  }
+  __syncthreads();
+  for (int idx = threadIdx.x; idx < nb * n1 * NX; idx += blockDim.x) {
+    const int r = idx % n1, s = (idx / n1) % NXs, bi = idx / (n1 * NXs);
+    const double* Xs = inst + bi * per;
+    const double* Fs = Xs + n1 * (NX + NU);
+    double acc = 0.0;
+    for (int c = 0; c < n1; ++c) acc += A[r + c * n1] * Fs[c * NX + s];
+    integ[size_t(b0 + bi) * RT + v.base + (1 + v.r0 + r) + size_t(s) * rows] = (0.0 + 1.0 * Xs[s]) + acc;
+  }
+  if (v.first)
+    for (int idx = threadIdx.x; idx < nb * NX; idx += blockDim.x) {
+      const int s = idx % NXs, bi = idx / NXs;
+      integ[size_t(b0 + bi) * RT + v.base + size_t(s) * rows] = inst[bi * per + s];
+    }
+  if (v.last)
+    for (int idx = threadIdx.x; idx < nb * NX; idx += blockDim.x) {
+      const int s = idx % NXs, bi = idx / NXs;
+      const size_t b = size_t(b0 + bi);
+      fine_state[b * RT + v.base + (rows - 1) + size_t(s) * rows] = x[b * K.n + ph.x_state0 + s * M + N];
+    }
+}
+
+// Workgroup (phase, instance): the denominators 1 + max(interpolated(:, s)) (a maximum: exact in any order), the
+// relative-error matrix, the instance's NaN/Inf verdict and, one thread per interval, the std::max chain of rpm::ph_refine
+// over the interval's rows (started from its first entry, so a NaN never replaces a number).  `keep`: every phase's matrix
+// fits in LDS, the chain reads it from there.
+__global__ void rpm_mesh_rel_batch_kernel(const PhaseDev* __restrict__ phases, const MeshIvBatch* __restrict__ ivs,
+                                          const int* __restrict__ ph_iv0, long long RT, int KT, const double* __restrict__ fine_state,
+                                          const double* __restrict__ integ, double* __restrict__ rel,
+                                          double* __restrict__ interval_error, int* nonfinite, int nx_max, int keep) {
+  extern __shared__ __align__(16) double mesh_den[];   // [nx_max + 2] denominators, then (keep) the phase's matrix
+  double* kept = mesh_den + nx_max + 2;
+  const int p = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6, waves = blockDim.x >> 6;
+  const size_t b = blockIdx.y;
+  const int iv0 = ph_iv0[p], Kp = ph_iv0[p + 1] - iv0;
+  const int rows = ivs[iv0].rows, nx = phases[p].nx;
+  const double* fs = fine_state + b * RT + ivs[iv0].base;
+  const double* in = integ + b * RT + ivs[iv0].base;
+  for (int s = wave; s < nx; s += waves) {
+    const double* col = fs + size_t(s) * rows;
+    double mx = col[0];
+    for (int r = lane; r < rows; r += 64) mx = fmax(mx, col[r]);
+    for (int w = 32; w > 0; w >>= 1) mx = fmax(mx, __shfl_xor(mx, w));
+    if (lane == 0) mesh_den[s] = 1 + mx;
+  }
+  __syncthreads();
+  bool bad = false;
+  for (int idx = threadIdx.x; idx < rows * nx; idx += blockDim.x) {
+    const double val = fabs(in[idx] - fs[idx]) / mesh_den[idx / rows];
+    if (rel) rel[b * RT + ivs[iv0].base + idx] = val;
+    if (keep) kept[idx] = val;
+    bad |= !(fabs(val) <= 1.7976931348623157e308);
+  }
+  if (nonfinite && bad) atomicOr(nonfinite + b, 1);
+  if (keep) __syncthreads();
+  if (interval_error)
+    for (int k = threadIdx.x; k < Kp; k += blockDim.x) {
+      const MeshIvBatch v = ivs[iv0 + k];
+      const int istart = v.r0, ifinish = v.r0 + v.n + 1;
+      // the chain is sequential: it reads the matrix from LDS when it fits there, else recomputes the entries (same bits)
+      auto at = [&](int r, int s) {
+        return keep ? kept[r + size_t(s) * rows] : fabs(in[r + size_t(s) * rows] - fs[r + size_t(s) * rows]) / mesh_den[s];
+      };
+      double emax = at(istart, 0);
+      for (int s = 0; s < nx; ++s)
+        for (int r = istart; r <= ifinish; ++r) {
+          const double e = at(r, s);
+          emax = emax < e ? e : emax;   // std::max(emax, e)
+        }
+      interval_error[b * KT + iv0 + k] = emax;
+    }
+}
+
+// element-wise maximum of the included instances' matrices (mesh_err_max: a NaN stays).  Workgroup (16 elements, chunk y
+// of `chunk` instances) x 16 instance slices, the slices combined in slice order; has[y] tells whether the chunk held an
+// included instance.  Large sweeps run it twice, the second pass over the chunks' results with `has` as its mask; the
+// pass that writes the caller's array (has == NULL) writes zeros when no instance was included.
+__global__ void rpm_mesh_max_kernel(long long RT, int B, int chunk, const int* __restrict__ mask, const double* __restrict__ rel,
+                                    double* __restrict__ out, int* __restrict__ has_out) {
+  __shared__ double sv[256];
+  __shared__ int sh[256];
+  const int el = threadIdx.x & 15, sl = threadIdx.x >> 4;
+  const long long i = (long long)blockIdx.x * 16 + el;
+  const int b0 = blockIdx.y * chunk, b1 = b0 + chunk < B ? b0 + chunk : B;
+  double acc = 0.0;
+  int has = 0;
+  if (i < RT)
+    for (int b = b0 + sl; b < b1; b += 16) {
+      if (mask && mask[b] == 0) continue;
+      const double val = rel[size_t(b) * RT + i];
+      acc = has ? mesh_err_max(acc, val) : val;
+      has = 1;
+    }
+  sv[threadIdx.x] = acc;
+  sh[threadIdx.x] = has;
+  __syncthreads();
+  if (sl == 0 && i < RT) {
+    for (int o = 1; o < 16; ++o)
+      if (sh[o * 16 + el]) {
+        acc = has ? mesh_err_max(acc, sv[o * 16 + el]) : sv[o * 16 + el];
+        has = 1;
+      }
+    out[size_t(blockIdx.y) * RT + i] = has ? acc : 0.0;
+    if (has_out && i == 0) has_out[blockIdx.y] = has;
+  }
+}
+
+struct MeshBatch {
+  char* block = nullptr;    // tables, then the workspace
+  double *Hs, *Ss, *Hc, *Sc, *A, *tt, *fine, *integ, *rel, *part;   // part: kMaxChunks x RT, the first pass of the maximum
+  int *hit_s, *hit_c, *ph_iv0, *part_has;
+  MeshIvBatch* ivs;
+  int KT = 0, nx_max = 0;
+  long long RT = 0;
+  size_t tab_doubles = 0, inst_doubles = 0;   // LDS of the largest interval: its tables / one instance's arrays
+  size_t block_max = 0;                       // doubles of the largest phase's rows x nx matrix
+  // host-pointer form: device outputs and a page-locked block for the two int arrays (mask in, verdicts out)
+  char* out = nullptr;
+  double *o_iv, *o_max;
+  int *o_flag, *o_mask, *h_ints = nullptr;
+};
+
+void mesh_batch_destroy(Device* d) {
+  MeshBatch* mb = static_cast<MeshBatch*>(d->mesh_batch);
+  if (!mb) return;
+  if (mb->block) (void)hipFree(mb->block);
+  if (mb->out) (void)hipFree(mb->out);
+  if (mb->h_ints) (void)hipHostFree(mb->h_ints);
+  delete mb;
+  d->mesh_batch = nullptr;
+}
+
+void solution_error_batch_sizes(const Engine& e, int* n_intervals_total, long long* rel_doubles_total) {
+  int kt = 0;
+  long long rt = 0;
+  for (const PhaseHost& p : e.ph) {
+    kt += p.K;
+    rt += (long long)(p.N + p.K + 1) * p.nx;
+  }
+  if (n_intervals_total) *n_intervals_total = kt;
+  if (rel_doubles_total) *rel_doubles_total = rt;
+}
+
+namespace {
+
+constexpr size_t kMeshLdsLimit = 60 * 1024;
+constexpr int kMaxChunks = 32;   // rpm_mesh_max_kernel's first pass over a large sweep
+
+struct DeviceRestore {   // the calling thread's current device, put back on every exit path
+  int prev = -1;
+  DeviceRestore() { if (hipGetDevice(&prev) != hipSuccess) prev = -1; }
+  ~DeviceRestore() { if (prev >= 0) (void)hipSetDevice(prev); }
+};
+
+// first use on an engine: tables of all phases into one device block, workspace behind them (the only allocation and the
+// only blocking copies of the batched estimate)
+int mesh_batch_setup(Engine& e) {
+  Device& d = *e.dev;
+  if (d.mesh_batch) return RPM_OK;
+  if (e.mesh_err.size() != e.ph.size()) e.mesh_err.assign(e.ph.size(), MeshErrTables());
+  std::vector<MeshIvBatch> ivs;
+  std::vector<double> Hs, Ss, Hc, Sc, A, tt;
+  std::vector<int> hit_s, hit_c, ph_iv0;
+  MeshBatch m;
+  solution_error_batch_sizes(e, &m.KT, &m.RT);
+  long long base = 0;
+  for (size_t ip = 0; ip < e.ph.size(); ++ip) {
+    const PhaseHost& p = e.ph[ip];
+    MeshErrTables& t = e.mesh_err[ip];
+    if (t.iv.empty()) build_mesh_err_tables(p, t);
+    ph_iv0.push_back(int(ivs.size()));
+    for (size_t k = 0; k < t.iv.size(); ++k) {
+      const MeshIvDev& s = t.iv[k];
+      MeshIvBatch v;
+      v.n = s.n; v.istart = s.istart; v.r0 = s.r0;
+      v.q0 = s.q0 + int(tt.size());
+      v.hs = s.hs + int(Hs.size());
+      v.hc = s.hc + int(Hc.size());
+      v.a = s.a + int(A.size());
+      v.phase = int(ip); v.rows = t.rows; v.base = int(base);
+      v.first = k == 0; v.last = k + 1 == t.iv.size();
+      ivs.push_back(v);
+      const size_t n1 = size_t(s.n) + 1;
+      m.tab_doubles = std::max(m.tab_doubles, n1 * n1 * 2 + n1 * s.n + 4 * n1);   // Hs, A, Hc, Ss, Sc, tt, two int rows
+      m.inst_doubles = std::max(m.inst_doubles, n1 * size_t(2 * p.nx + p.nu));
+    }
+    auto app = [](auto& dst, const auto& src) { dst.insert(dst.end(), src.begin(), src.end()); };
+    app(tt, t.ttem); app(Hs, t.Hs); app(Ss, t.Ss); app(Hc, t.Hc); app(Sc, t.Sc); app(A, t.A);
+    app(hit_s, t.hit_s); app(hit_c, t.hit_c);
+    base += (long long)t.rows * p.nx;
+    m.block_max = std::max(m.block_max, size_t(t.rows) * p.nx);
+    m.nx_max = std::max(m.nx_max, p.nx);
+  }
+  ph_iv0.push_back(int(ivs.size()));
+  if (m.inst_doubles * sizeof(double) > kMeshLdsLimit) {
+    e.err = "solution_error_batch: a mesh interval has too many nodes for the estimator's LDS tile";
+    return RPM_E_UNSUPPORTED;
+  }
+  const size_t B = size_t(e.n_instances);
+  const size_t nd = tt.size() + Hs.size() + Ss.size() + Hc.size() + Sc.size() + A.size() + (3 * B + kMaxChunks) * size_t(m.RT);
+  const size_t ni = hit_s.size() + hit_c.size() + ph_iv0.size() + kMaxChunks;
+  HIP_TRY(e, hipMalloc(reinterpret_cast<void**>(&m.block), nd * sizeof(double) + ni * sizeof(int) + ivs.size() * sizeof(MeshIvBatch)));
+  double* dd = reinterpret_cast<double*>(m.block);
+  m.tt = dd; dd += tt.size();
+  m.Hs = dd; dd += Hs.size();
+  m.Ss = dd; dd += Ss.size();
+  m.Hc = dd; dd += Hc.size();
+  m.Sc = dd; dd += Sc.size();
+  m.A = dd; dd += A.size();
+  m.fine = dd; dd += B * size_t(m.RT);
+  m.integ = dd; dd += B * size_t(m.RT);
+  m.rel = dd; dd += B * size_t(m.RT);
+  m.part = dd; dd += kMaxChunks * size_t(m.RT);
+  m.hit_s = reinterpret_cast<int*>(dd);
+  m.hit_c = m.hit_s + hit_s.size();
+  m.ph_iv0 = m.hit_c + hit_c.size();
+  m.part_has = m.ph_iv0 + ph_iv0.size();
+  m.ivs = reinterpret_cast<MeshIvBatch*>(m.part_has + kMaxChunks);
+  hipError_t s = hipSuccess;
+  auto put = [&](void* dev, const void* host, size_t cnt) {
+    if (cnt && s == hipSuccess) s = hipMemcpy(dev, host, cnt, hipMemcpyHostToDevice);
+  };
+  put(m.tt, tt.data(), tt.size() * sizeof(double));
+  put(m.Hs, Hs.data(), Hs.size() * sizeof(double));
+  put(m.Ss, Ss.data(), Ss.size() * sizeof(double));
+  put(m.Hc, Hc.data(), Hc.size() * sizeof(double));
+  put(m.Sc, Sc.data(), Sc.size() * sizeof(double));
+  put(m.A, A.data(), A.size() * sizeof(double));
+  put(m.hit_s, hit_s.data(), hit_s.size() * sizeof(int));
+  put(m.hit_c, hit_c.data(), hit_c.size() * sizeof(int));
+  put(m.ph_iv0, ph_iv0.data(), ph_iv0.size() * sizeof(int));
+  put(m.ivs, ivs.data(), ivs.size() * sizeof(MeshIvBatch));
+  if (s != hipSuccess) {
+    (void)hipFree(m.block);
+    e.err = std::string("solution_error_batch: ") + hipGetErrorString(s);
+    return RPM_E_DEVICE;
+  }
+  d.mesh_batch = new MeshBatch(m);
+  return RPM_OK;
+}
+
+}  // namespace
+
+// device-resident: three or four launches on `stream`; after the first call on an engine nothing else
+int dev_solution_error_batch(Engine& e, const double* d_x, const int* d_mask, double* d_interval_error, double* d_rel_err_max,
+                             double* d_rel_err, int* d_nonfinite, void* stream) {
+  DeviceRestore restore;
+  if (!e.dev) {
+    int rc = device_init(e, 0);
+    if (rc) return rc;
+  }
+  Device& d = *e.dev;
+  HIP_TRY(e, hipSetDevice(d.device_id));
+  int rc = mesh_batch_setup(e);
+  if (rc) return rc;
+  const MeshBatch& m = *static_cast<MeshBatch*>(d.mesh_batch);
+  const int B = e.n_instances;
+  // instances per workgroup: the largest of 8, 4, 2, 1 (or the option) whose arrays fit next to the staged tables
+  int TB = e.opt_mesh_err_tile > 0 ? e.opt_mesh_err_tile : 8;
+  const int stage = (m.tab_doubles + m.inst_doubles) * sizeof(double) <= kMeshLdsLimit ? 1 : 0;
+  const size_t tab = stage ? m.tab_doubles : 0;
+  while (TB > 1 && (tab + size_t(TB) * m.inst_doubles) * sizeof(double) > kMeshLdsLimit) TB >>= 1;
+  while (TB > 1 && TB / 2 >= B) TB >>= 1;
+  const size_t lds = (tab + size_t(TB) * m.inst_doubles) * sizeof(double);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  double* rel = d_rel_err ? d_rel_err : (d_rel_err_max ? m.rel : nullptr);
+  with_problem(e.problem_id, [&](auto prob) {
+    using P = decltype(prob);
+    hipLaunchKernelGGL((rpm_mesh_err_batch_kernel<P>), dim3(unsigned(m.KT), unsigned((B + TB - 1) / TB)), dim3(256), lds, st, d.kp, B,
+                       TB, stage, m.RT, d_x, m.ivs, m.Hs, m.Ss, m.hit_s, m.Hc, m.Sc, m.hit_c, m.A, m.tt, m.fine, m.integ, d_nonfinite);
+  });
+  if (rel || d_interval_error || d_nonfinite) {
+    const size_t den = size_t(m.nx_max) + 2;
+    const int keep = d_interval_error && (den + m.block_max) * sizeof(double) <= kMeshLdsLimit ? 1 : 0;
+    hipLaunchKernelGGL(rpm_mesh_rel_batch_kernel, dim3(unsigned(e.P), unsigned(B)), dim3(256), (den + (keep ? m.block_max : 0)) * sizeof(double),
+                       st, d.d_phases, m.ivs, m.ph_iv0, m.RT, m.KT, m.fine, m.integ, rel, d_interval_error, d_nonfinite, m.nx_max, keep);
+  }
+  if (d_rel_err_max) {
+    const unsigned gx = unsigned((m.RT + 15) / 16);
+    int* const no_has = nullptr;
+    if (B <= 2 * kMaxChunks) {
+      hipLaunchKernelGGL(rpm_mesh_max_kernel, dim3(gx), dim3(256), 0, st, m.RT, B, B, d_mask, rel, d_rel_err_max, no_has);
+    } else {   // 55 workgroups cannot pull 1024 matrices in at speed: chunks first, then the chunks' results
+      const int chunk = (B + kMaxChunks - 1) / kMaxChunks, chunks = (B + chunk - 1) / chunk;
+      hipLaunchKernelGGL(rpm_mesh_max_kernel, dim3(gx, unsigned(chunks)), dim3(256), 0, st, m.RT, B, chunk, d_mask, rel, m.part, m.part_has);
+      hipLaunchKernelGGL(rpm_mesh_max_kernel, dim3(gx), dim3(256), 0, st, m.RT, chunks, chunks, m.part_has, m.part, d_rel_err_max, no_has);
+    }
+  }
+  const hipError_t s = hipGetLastError();
+  if (s != hipSuccess) {
+    e.err = std::string("solution_error_batch launch: ") + hipGetErrorString(s);
+    return RPM_E_DEVICE;
+  }
+  return RPM_OK;
+}
+
+// the same through host arrays: x (and the mask) up through the staging slots, the requested results back; blocking
+int host_solution_error_batch(Engine& e, const double* x, const int* mask, double* interval_error, double* rel_err_max,
+                              double* rel_err, int* nonfinite) {
+  DeviceRestore restore;
+  if (!e.dev) {
+    int rc = device_init(e, 0);
+    if (rc) return rc;
+  }
+  Device& d = *e.dev;
+  HIP_TRY(e, hipSetDevice(d.device_id));
+  int rc = mesh_batch_setup(e);
+  if (rc) return rc;
+  MeshBatch& m = *static_cast<MeshBatch*>(d.mesh_batch);
+  const size_t B = size_t(e.n_instances);
+  if (!m.out) {
+    HIP_TRY(e, hipMalloc(reinterpret_cast<void**>(&m.out), (B * m.KT + size_t(m.RT)) * sizeof(double) + 2 * B * sizeof(int)));
+    m.o_iv = reinterpret_cast<double*>(m.out);
+    m.o_max = m.o_iv + B * m.KT;
+    m.o_flag = reinterpret_cast<int*>(m.o_max + m.RT);
+    m.o_mask = m.o_flag + B;
+    HIP_TRY(e, hipHostMalloc(reinterpret_cast<void**>(&m.h_ints), 2 * B * sizeof(int), hipHostMallocDefault));
+  }
+  rc = dev_upload(e, d.d_x, x, B * e.n, STAGE_X);
+  if (rc) return rc;
+  if (mask) {
+    std::memcpy(m.h_ints, mask, B * sizeof(int));
+    HIP_TRY(e, hipMemcpyAsync(m.o_mask, m.h_ints, B * sizeof(int), hipMemcpyHostToDevice, d.stream));
+  }
+  rc = dev_solution_error_batch(e, d.d_x, mask ? m.o_mask : nullptr, interval_error ? m.o_iv : nullptr,
+                                rel_err_max ? m.o_max : nullptr, rel_err ? m.rel : nullptr, nonfinite ? m.o_flag : nullptr, d.stream);
+  if (rc) return rc;
+  HIP_TRY(e, hipSetDevice(d.device_id));
+  if (nonfinite) HIP_TRY(e, hipMemcpyAsync(m.h_ints + B, m.o_flag, B * sizeof(int), hipMemcpyDeviceToHost, d.stream));
+  if (interval_error) rc = dev_download(e, interval_error, m.o_iv, B * m.KT, STAGE_G);
+  if (rc == RPM_OK && rel_err_max) rc = dev_download(e, rel_err_max, m.o_max, size_t(m.RT), STAGE_V);
+  if (rc == RPM_OK && rel_err) rc = dev_download(e, rel_err, m.rel, B * size_t(m.RT), STAGE_HESS);
+  if (rc) return rc;
+  HIP_TRY(e, hipStreamSynchronize(d.stream));
+  dev_stage_synced(e);
+  if (nonfinite) std::memcpy(nonfinite, m.h_ints + B, B * sizeof(int));
+  return RPM_OK;
+}
+
 }  // namespace rpm

@@ -10,7 +10,7 @@
 #include <thread>
 #include <vector>
 
-#include "../../include/rpm_hip.h"
+#include "rpm_engine.hpp"
 
 struct rpm_sweep {
   std::vector<rpm_engine*> eng;
@@ -125,6 +125,64 @@ int rpm_sweep_solve(rpm_sweep* s, double* x, double* lambda, double* obj, int* s
   for (std::thread& t : th) t.join();
   for (size_t r = 0; r < N; ++r)
     if (rcs[r]) return sfail(s, int(r), rcs[r]);
+  return RPM_OK;
+}
+
+/* The mesh-error estimate of the whole sweep (rpm_solution_error_batch on every share, side by side).  x: B x n; instance_mask:
+ * B or NULL; any result may be NULL: interval_error B x KT, rel_err_max RT, rel_err B x RT, nonfinite B.  rel_err_max is the
+ * element-wise maximum of the shares' blocks (a maximum: what one engine holding all B instances returns, bit for bit); a share
+ * whose instances are all excluded contributes nothing to it. */
+int rpm_sweep_solution_error(rpm_sweep* s, const double* x, const int* instance_mask, double* interval_error, double* rel_err_max,
+                             double* rel_err, int* nonfinite) {
+  if (!s || !x) return RPM_E_INVALID;
+  const size_t N = s->eng.size();
+  int KT = 0;
+  long long RT = 0;
+  rpm_solution_error_batch_sizes(s->eng[0], &KT, &RT);
+  std::vector<char> included(N, 1);
+  if (instance_mask) {
+    bool any = false;
+    for (size_t r = 0; r < N; ++r) {
+      included[r] = 0;
+      for (int b = 0; b < s->count[r]; ++b) included[r] = included[r] || instance_mask[s->first[r] + b] != 0;
+      any = any || included[r];
+    }
+    if (!any && rel_err_max) {
+      s->err = "rpm_sweep_solution_error: rel_err_max asked for, but instance_mask excludes every instance";
+      return RPM_E_INVALID;
+    }
+  }
+  int prev = -1;
+  if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+  std::vector<std::vector<double>> part(N);
+  std::vector<int> rcs(N, RPM_OK);
+  auto run = [&](size_t r) {
+    (void)hipSetDevice(s->dev[r]);
+    const size_t i0 = size_t(s->first[r]);
+    const bool want_max = rel_err_max && included[r];
+    if (want_max) part[r].resize(size_t(RT));
+    rcs[r] = rpm_solution_error_batch(s->eng[r], x + i0 * s->n, instance_mask ? instance_mask + i0 : nullptr,
+                                      interval_error ? interval_error + i0 * KT : nullptr, want_max ? part[r].data() : nullptr,
+                                      rel_err ? rel_err + i0 * size_t(RT) : nullptr, nonfinite ? nonfinite + i0 : nullptr);
+  };
+  std::vector<std::thread> th;
+  for (size_t r = 1; r < N; ++r) th.emplace_back(run, r);
+  run(0);
+  for (std::thread& t : th) t.join();
+  if (prev >= 0) (void)hipSetDevice(prev);
+  for (size_t r = 0; r < N; ++r)
+    if (rcs[r]) {
+      s->err = "share " + std::to_string(r) + " (device " + std::to_string(s->dev[r]) + "): " + rpm_last_error(s->eng[r]);
+      return rcs[r];
+    }
+  if (rel_err_max) {
+    bool has = false;
+    for (size_t r = 0; r < N; ++r) {
+      if (!included[r]) continue;
+      for (long long i = 0; i < RT; ++i) rel_err_max[i] = has ? rpm::mesh_err_max(rel_err_max[i], part[r][size_t(i)]) : part[r][size_t(i)];
+      has = true;
+    }
+  }
   return RPM_OK;
 }
 

@@ -29,6 +29,7 @@ ABI_SYMBOLS = [
     "rpm_synchronize", "rpm_set_option", "rpm_get_option", "rpm_set_instance_constants", "rpm_get_phase_sizes", "rpm_get_phase_tables",
     "rpm_shard_segments", "rpm_shard_pack_dev", "rpm_shard_unpack_dev", "rpm_shard_slot_len", "rpm_shard_pack_all_dev", "rpm_shard_unpack_all_dev", "rpm_nlp2op_control", "rpm_final_result_save",
     "rpm_solution_error", "rpm_ph_refine_mesh", "rpm_ph_refine_from_error",
+    "rpm_solution_error_batch_sizes", "rpm_solution_error_batch_dev", "rpm_solution_error_batch", "rpm_sweep_solution_error",
     "rpm_hpliu_create", "rpm_hpliu_destroy", "rpm_hpliu_last_error", "rpm_hpliu_refine",
     "rpm_ipm_create", "rpm_ipm_destroy", "rpm_ipm_last_error", "rpm_ipm_set_option", "rpm_ipm_set_bounds", "rpm_ipm_set_all_bounds", "rpm_ipm_get_info",
     "rpm_group_create", "rpm_group_destroy", "rpm_group_last_error", "rpm_group_size", "rpm_group_engine", "rpm_group_device_init",
@@ -104,6 +105,10 @@ def lib(path=None):
     L.rpm_solution_error.argtypes = [vp, C.c_int, dp, dp, ip]
     L.rpm_ph_refine_mesh.argtypes = [vp, C.c_int, dp, C.c_double, C.c_int, C.c_int, C.c_int, dp, ip, ip, dp, ip]
     L.rpm_ph_refine_from_error.argtypes = [vp, C.c_int, dp, C.c_double, C.c_int, C.c_int, C.c_int, dp, ip, ip, dp, ip]
+    L.rpm_solution_error_batch_sizes.argtypes = [vp, ip, C.POINTER(C.c_longlong)]
+    L.rpm_solution_error_batch_dev.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
+    L.rpm_solution_error_batch.argtypes = [vp, dp, ip, dp, dp, dp, ip]
+    L.rpm_sweep_solution_error.argtypes = [vp, dp, ip, dp, dp, dp, ip]
     L.rpm_hpliu_create.argtypes = [C.c_int, C.c_double, C.c_int, C.c_double, C.POINTER(vp)]
     L.rpm_hpliu_destroy.argtypes = [vp]
     L.rpm_hpliu_destroy.restype = None
@@ -187,6 +192,47 @@ class RpmError(LpopcException):
     def __init__(self, code, msg):
         super().__init__("rpm error %d: %s" % (code, msg))
         self.code = code
+
+
+def _phase_shapes(L, handle, desc, n_phases, check):
+    out = []
+    for p in range(n_phases):
+        N = C.c_int()
+        check(L.rpm_get_phase_sizes(handle, p, C.byref(N), None, None))
+        K = desc.phases[p].n_intervals
+        out.append((K, N.value + K + 1, desc.phases[p].nx))
+    return out
+
+
+def _split_rel(flat, shapes):
+    out, off = [], 0
+    for _, rows, nx in shapes:
+        blk = flat[..., off:off + rows * nx]
+        out.append(blk.reshape(flat.shape[:-1] + (nx, rows)).swapaxes(-1, -2).copy())
+        off += rows * nx
+    return out
+
+
+def _batch_estimate(fn, check, handle, x, B, sizes, shapes, mask, full):
+    """Shared by NLPEngine.solution_error_batch and SweepGroup.solution_error: call, then cut the flat results per phase."""
+    KT, RT = sizes
+    mp = None
+    if mask is not None:
+        mk = np.ascontiguousarray(mask, dtype=np.int32).ravel()
+        if mk.size != B:
+            raise RpmError(RPM_E_INVALID, "mask has %d entries, expected %d" % (mk.size, B))
+        mp = _ip(mk)
+    iv, mx, flags = np.zeros((B, KT)), np.zeros(RT), np.zeros(B, dtype=np.int32)
+    rel = np.zeros((B, RT)) if full else None
+    check(fn(handle, _dp(x), mp, _dp(iv), _dp(mx), _dp(rel) if full else None, _ip(flags)))
+    out = {"interval_error": [], "rel_err_max": _split_rel(mx, shapes), "nonfinite": flags}
+    off = 0
+    for K, _, _ in shapes:
+        out["interval_error"].append(iv[:, off:off + K].copy())
+        off += K
+    if full:
+        out["rel_err"] = _split_rel(rel, shapes)
+    return out
 
 
 class NLPEngine:
@@ -435,6 +481,41 @@ class NLPEngine:
     def ph_refine_from_error(self, phase, rel_err, tol, nmin, nmax):
         rel = np.asfortranarray(rel_err, dtype=np.float64).ravel(order="F").copy()
         return self._refine(self._L.rpm_ph_refine_from_error, phase, _dp(rel), tol, nmin, nmax)
+
+    # ---- the estimate of a whole sweep: all phases, all instances (rpm_solution_error_batch*) -------------------------
+    def solution_error_batch_sizes(self):
+        """(KT, RT): sum of the phases' interval counts, doubles of one instance's relative-error block."""
+        kt, rt = C.c_int(), C.c_longlong()
+        self._check(self._L.rpm_solution_error_batch_sizes(self._h, C.byref(kt), C.byref(rt)))
+        return kt.value, rt.value
+
+    def _phase_shapes(self):
+        """Per phase (K_p, rows_p, nx_p)."""
+        return _phase_shapes(self._L, self._h, self._desc, self.n_phases, self._check)
+
+    def solution_error_batch(self, x, mask=None, full=False):
+        """The mesh-error estimate of every instance -> dict(interval_error: per phase B x K_p, rel_err_max: per phase
+        rows_p x nx_p (maximum over the instances `mask` includes), nonfinite: B ints, and with full=True rel_err: per phase
+        B x rows_p x nx_p)."""
+        return _batch_estimate(self._L.rpm_solution_error_batch, self._check, self._h, self._x(x), self.n_instances,
+                               self.solution_error_batch_sizes(), self._phase_shapes(), mask, full)
+
+    def solution_error_batch_dev(self, d_x, d_mask=None, d_interval_error=None, d_rel_err_max=None, d_rel_err=None,
+                                 d_nonfinite=None, stream=None):
+        """Device-resident form on torch CUDA tensors (float64; mask / nonfinite int32); results as flat arrays in the
+        library's layout (rpm_hip.h).  Asynchronous on `stream`."""
+        self._check(self._L.rpm_solution_error_batch_dev(self._h, self._ptr(d_x), self._ptr(d_mask), self._ptr(d_interval_error),
+                                                         self._ptr(d_rel_err_max), self._ptr(d_rel_err), self._ptr(d_nonfinite),
+                                                         self._stream(stream)))
+
+    def split_rel_err(self, flat):
+        """One block of RT doubles (or B of them) -> list per phase of rows_p x nx_p (B x rows_p x nx_p) arrays."""
+        return _split_rel(np.asarray(flat), self._phase_shapes())
+
+    def ph_refine_sweep(self, x, tol, nmin, nmax, mask=None):
+        """The next mesh of the sweep: per phase ph_refine_from_error on rel_err_max (the worst included instance decides)."""
+        est = self.solution_error_batch(x, mask)
+        return [self.ph_refine_from_error(p, est["rel_err_max"][p], tol, nmin, nmax) for p in range(self.n_phases)]
 
     # ---- tables and sharding ---------------------------------------------------------------
     def phase_tables(self, phase):

@@ -7,7 +7,7 @@ import ctypes as C
 import numpy as np
 
 from . import _abi
-from .engine import RPM_E_INVALID, RPM_OK, RpmError, _dp, _ip, lib
+from .engine import RPM_E_INVALID, RPM_OK, RpmError, _batch_estimate, _dp, _ip, _phase_shapes, lib
 
 
 class _EngineView:
@@ -135,6 +135,7 @@ class SweepGroup:
         n, m, nj, nh, st = (C.c_int() for _ in range(5))
         self._check(self._L.rpm_get_nlp_info(e0, C.byref(n), C.byref(m), C.byref(nj), C.byref(nh), C.byref(st)))
         self.n, self.m = n.value, m.value
+        self.n_phases = problem.GetPhaseNum()
         for k, v in solver_options.items():
             self.set_option(k, v)
 
@@ -180,3 +181,39 @@ class SweepGroup:
         a, b, c = C.c_int(), C.c_int(), C.c_int()
         self._check(self._L.rpm_sweep_get_stats(self._h, C.byref(a), C.byref(b), C.byref(c)))
         return {"iterations": a.value, "factorizations": b.value, "trial_points": c.value}
+
+    # ---- mesh-error estimate and ph refinement of the whole sweep ------------------------------------------------
+    def _sizes_and_shapes(self):
+        e0 = self._L.rpm_sweep_engine(self._h, 0)
+        kt, rt = C.c_int(), C.c_longlong()
+        self._check(self._L.rpm_solution_error_batch_sizes(e0, C.byref(kt), C.byref(rt)))
+        return (kt.value, rt.value), _phase_shapes(self._L, e0, self._desc, self.n_phases, self._check)
+
+    def solution_error(self, x, mask=None, full=False):
+        """rpm_sweep_solution_error: as NLPEngine.solution_error_batch, over all shares; equal to one engine holding all
+        instances bit for bit."""
+        x = np.ascontiguousarray(x, dtype=np.float64).ravel()
+        if x.size != self.n * self.n_instances:
+            raise RpmError(RPM_E_INVALID, "x has %d entries, expected %d" % (x.size, self.n * self.n_instances))
+        sizes, shapes = self._sizes_and_shapes()
+        return _batch_estimate(self._L.rpm_sweep_solution_error, self._check, self._h, x, self.n_instances, sizes, shapes,
+                               mask, full)
+
+    def ph_refine(self, x, tol, nmin, nmax, mask=None):
+        """The sweep's next mesh: per phase (no_more_refine, mesh, nodes, interval_error) from rel_err_max."""
+        est = self.solution_error(x, mask)
+        e0 = self._L.rpm_sweep_engine(self._h, 0)
+        out = []
+        for p in range(self.n_phases):
+            rel = np.asfortranarray(est["rel_err_max"][p]).ravel(order="F").copy()
+            K = self._desc.phases[p].n_intervals
+            nk, done, emax = C.c_int(), C.c_int(), np.zeros(K)
+            args = (e0, p, _dp(rel), float(tol), int(nmin), int(nmax))
+            rc = self._L.rpm_ph_refine_from_error(*args, 0, None, None, C.byref(nk), _dp(emax), C.byref(done))
+            mesh, nodes = np.zeros(nk.value + 1), np.zeros(nk.value, dtype=np.int32)
+            if rc == RPM_OK:
+                rc = self._L.rpm_ph_refine_from_error(*args, nk.value, _dp(mesh), _ip(nodes), C.byref(nk), None, None)
+            if rc != RPM_OK:
+                raise RpmError(rc, self._L.rpm_last_error(e0).decode())
+            out.append((bool(done.value), mesh, nodes, emax))
+        return out
