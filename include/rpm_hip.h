@@ -357,6 +357,12 @@ int rpm_eval_f_dev(rpm_engine* e, const double* d_x, double* d_obj, void* stream
 int rpm_eval_grad_f_dev(rpm_engine* e, const double* d_x, double* d_grad_f, void* stream);
 int rpm_eval_h_dev(rpm_engine* e, const double* d_x, double obj_factor, const double* d_lambda,
                    double* d_values, void* stream);
+/* Test hook of the exact Hessian's t0/tf reduction (rpm_hess_tt_kernel alone).  The shipped functors are autonomous, so
+ * rpm_eval_h only ever gives that kernel zeros to add.  tmp (HOST): n_instances x tmp_len doubles, tmp_len = 3 * (sum of
+ * the phases' N); phase p starts at 3 * (nodes of the phases before it) and holds N per-node terms of the t0t0 entry,
+ * then N of tftf, then N of tft0.  out (HOST): [(instance * n_phases + p) * 3 + i], i = 0 t0t0, 1 tft0, 2 tftf, read back
+ * from where rpm_eval_h stores them. */
+int rpm_debug_hess_tt(rpm_engine* e, const double* tmp, int tmp_len, double* out);
 /* block until everything queued on the engine's stream has finished */
 int rpm_synchronize(rpm_engine* e);
 
@@ -373,6 +379,7 @@ int rpm_synchronize(rpm_engine* e);
  *                    persistent pipelined kernel (4 compute waves + 1 DMA wave per workgroup; inputs of the next tile
  *                    prefetched, constant block written by the DMA wave); automatic = every resident workgroup has
  *                    at least two tiles.  get-only "pipeline_active": 1 if the next launch uses it
+ * "hess_tile_nodes"  get-only: nodes per workgroup of the exact-Hessian kernel (0 before the first eval_h)
  * "stage_roles"      -1 (default) | 0 | 1: in the pipelined kernel, problem functors that offer their dynamics in stages
  *                    (csrc/problems/problems.hpp `has_stage`: the launch vehicle, the quadrotor) are evaluated in full once per
  *                    node and per perturbation role only in what the perturbed variable enters — the same operations, the

@@ -524,6 +524,17 @@ int rpm_eval_h_dev(rpm_engine* h, const double* d_x, double obj_factor, const do
   return rpm::dev_eval_h(h->e, d_x, obj_factor, d_lambda, d_values, stream);
   RPM_GUARD_END(h->e)
 }
+int rpm_debug_hess_tt(rpm_engine* h, const double* tmp, int tmp_len, double* out) {
+  if (!h) return RPM_E_INVALID;
+  RPM_GUARD_BEGIN
+  Engine& e = h->e;
+  if (e.hessian_mode != RPM_HESSIAN_EXACT) return fail(e, RPM_E_UNSUPPORTED, "debug_hess_tt: the engine was created with hessian-approximation=limited-memory");
+  int rc = rpm::ensure_hessian(e);
+  if (rc) return rc;
+  if (!tmp || !out || tmp_len != e.hess_tmp_len) return fail(e, RPM_E_INVALID, "debug_hess_tt: tmp holds three rows of N terms per phase");
+  return rpm::dev_debug_hess_tt(e, tmp, out);
+  RPM_GUARD_END(h->e)
+}
 int rpm_synchronize(rpm_engine* h) {
   if (!h) return RPM_E_INVALID;
   return rpm::dev_sync(h->e);
@@ -670,6 +681,7 @@ int rpm_get_option(rpm_engine* h, const char* key, int* value) {
   else if (k == "stride_g") *value = int(e.stride_g());
   else if (k == "stride_values") *value = int(e.stride_values());
   else if (k == "pipeline_active") *value = rpm::dev_pipeline_active(e);
+  else if (k == "hess_tile_nodes") *value = rpm::dev_hess_tile_nodes(e);
   else return fail(e, RPM_E_INVALID, "unknown option");
   return RPM_OK;
 }

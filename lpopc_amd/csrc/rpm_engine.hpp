@@ -205,6 +205,8 @@ void build_hessian_tables(Engine& e);
 // rpm_device.hip: runs the NaN-propagation dependency probe on the device, then build_hessian_tables
 int ensure_hessian(Engine& e);
 int dev_eval_h(Engine& e, const double* d_x, double obj_factor, const double* d_lambda, double* d_values, void* stream);
+int dev_hess_tile_nodes(const Engine& e);   // TH of rpm_hess_kernel once the Hessian tables are on the device, else 0
+int dev_debug_hess_tt(Engine& e, const double* tmp, double* out);   // rpm_hess_tt_kernel alone, on the caller's per-node terms
 
 int dev_nlp2op(Engine& e, int phase, const double* x, const double* lambda, double* time, double* state, double* control,
                double* costate, double* pathmult, double* hamiltonian, double* mayer_cost, double* lagrange_cost);

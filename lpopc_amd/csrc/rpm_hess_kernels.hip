@@ -431,4 +431,30 @@ int dev_eval_h(Engine& e, const double* d_x, double obj_factor, const double* d_
   return RPM_OK;
 }
 
+int dev_hess_tile_nodes(const Engine& e) { return e.dev && e.dev->d_hpairs ? e.dev->hp.th : 0; }
+
+// Test hook of the t0/tf reduction.  Every functor shipped here is autonomous, so eval_h only ever hands rpm_hess_tt_kernel
+// rows of zeros; this runs the kernel alone on caller-given per-node terms.  tmp: n_instances x hess_tmp_len, phase p at
+// tt_tmp = 3 * (nodes of the phases before it): N terms of t0t0, then N of tftf, then N of tft0 (what rpm_hess_kernel writes).
+// out[(inst * P + p) * 3 + {0, 1, 2}] = the t0t0, tft0, tftf entries as stored in the Hessian values.
+int dev_debug_hess_tt(Engine& e, const double* tmp, double* out) {
+  int rc = ensure_hessian(e);
+  if (rc) return rc;
+  Device& d = *e.dev;
+  HIP_TRY(e, hipSetDevice(d.device_id));
+  const size_t B = size_t(e.n_instances);
+  HIP_TRY(e, hipStreamSynchronize(d.stream));
+  HIP_TRY(e, hipMemcpy(d.d_htmp, tmp, B * e.hess_tmp_len * sizeof(double), hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(rpm_hess_tt_kernel, dim3(unsigned(e.P), unsigned(e.n_instances)), dim3(256), 0, d.stream, d.kp, d.hp,
+                     d.d_htmp, d.d_hess);
+  HIP_TRY(e, hipGetLastError());
+  HIP_TRY(e, hipStreamSynchronize(d.stream));
+  for (size_t b = 0; b < B; ++b)
+    for (int p = 0; p < e.P; ++p)
+      for (int i = 0; i < 3; ++i)
+        HIP_TRY(e, hipMemcpy(out + (b * e.P + p) * 3 + i, d.d_hess + b * e.nnz_h + e.hess_phases[p].v0 + e.hess_phases[p].tt_dst[i],
+                             sizeof(double), hipMemcpyDeviceToHost));
+  return RPM_OK;
+}
+
 }  // namespace rpm

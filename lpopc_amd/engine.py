@@ -25,7 +25,7 @@ ABI_SYMBOLS = [
     "rpm_create", "rpm_destroy", "rpm_last_error", "rpm_device_init", "rpm_get_nlp_info",
     "rpm_get_bounds_info", "rpm_get_starting_point", "rpm_eval_f", "rpm_eval_grad_f", "rpm_eval_g",
     "rpm_eval_jac_g", "rpm_eval_pair", "rpm_eval_h", "rpm_finalize_solution", "rpm_get_solution", "rpm_eval_g_dev",
-    "rpm_eval_jac_g_dev", "rpm_eval_pair_dev", "rpm_eval_f_dev", "rpm_eval_grad_f_dev", "rpm_eval_h_dev",
+    "rpm_eval_jac_g_dev", "rpm_eval_pair_dev", "rpm_eval_f_dev", "rpm_eval_grad_f_dev", "rpm_eval_h_dev", "rpm_debug_hess_tt",
     "rpm_synchronize", "rpm_set_option", "rpm_get_option", "rpm_set_instance_constants", "rpm_get_phase_sizes", "rpm_get_phase_tables",
     "rpm_shard_segments", "rpm_shard_pack_dev", "rpm_shard_unpack_dev", "rpm_shard_slot_len", "rpm_shard_pack_all_dev", "rpm_shard_unpack_all_dev", "rpm_nlp2op_control", "rpm_final_result_save",
     "rpm_solution_error", "rpm_ph_refine_mesh", "rpm_ph_refine_from_error",
@@ -94,6 +94,7 @@ def lib(path=None):
     L.rpm_eval_f_dev.argtypes = [vp, vp, vp, vp]
     L.rpm_eval_grad_f_dev.argtypes = [vp, vp, vp, vp]
     L.rpm_eval_h_dev.argtypes = [vp, vp, C.c_double, vp, vp, vp]
+    L.rpm_debug_hess_tt.argtypes = [vp, dp, C.c_int, dp]
     L.rpm_synchronize.argtypes = [vp]
     L.rpm_set_option.argtypes = [vp, C.c_char_p, C.c_int]
     L.rpm_set_instance_constants.argtypes = [vp, C.c_int, dp, C.c_int]
@@ -427,6 +428,14 @@ class NLPEngine:
     def eval_h_dev(self, d_x, obj_factor, d_lambda, d_values, stream=None):
         self._check(self._L.rpm_eval_h_dev(self._h, self._ptr(d_x), float(obj_factor), self._ptr(d_lambda),
                                            self._ptr(d_values), self._stream(stream)))
+
+    def debug_hess_tt(self, tmp):
+        """rpm_debug_hess_tt: rpm_hess_tt_kernel alone on per-node terms (n_instances, 3 * sum N) -> (n_instances, n_phases, 3)
+        = the t0t0, tft0, tftf entries.  Per phase the rows are the terms of t0t0, tftf, tft0."""
+        tmp = np.ascontiguousarray(tmp, dtype=np.float64)
+        out = np.zeros((self.n_instances, self.n_phases, 3))
+        self._check(self._L.rpm_debug_hess_tt(self._h, _dp(tmp), int(tmp.size // self.n_instances), _dp(out)))
+        return out
 
     def synchronize(self):
         self._check(self._L.rpm_synchronize(self._h))

@@ -106,6 +106,9 @@ void orpm_jac_structure(orpm* o, int* iRow, int* jCol);
 void orpm_eval_jac_g(orpm* o, const double* x, double* values);
 void orpm_hess_structure(orpm* o, int* iRow, int* jCol);
 void orpm_eval_h(orpm* o, const double* x, double obj_factor, const double* lambda, double* values);
+/* the same walk with every term's magnitude added up instead of the signed terms: per stored entry, what rounding
+ * noise of orpm_eval_h (in any evaluation order, with any libm) is a small multiple of 2^-52 of */
+void orpm_eval_h_mag(orpm* o, const double* x, double obj_factor, const double* lambda, double* values);
 
 void orpm_get_phase_sizes(const orpm* o, int phase, int* n_nodes, int* d_nnz, int* doff_nnz);
 void orpm_get_phase_tables(const orpm* o, int phase, double* points, double* weights, int* d_rows,

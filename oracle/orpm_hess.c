@@ -280,10 +280,29 @@ static double accu_prod(const double* a, const double* b, int n) {
   return v1 + v2;
 }
 
-void orpm_eval_h(orpm* o, const double* x, double sigma, const double* lambda, double* values) {
+/* second difference of one output.  mag: the same four values with every sign made positive (orpm_eval_h_mag) */
+static inline double diff2(int mag, double fab, double fa, double fb, double f0) {
+  return mag ? fabs(fab) + fabs(fa) + fabs(fb) + fabs(f0) : fab - fa - fb + f0;
+}
+
+/* The one walk behind orpm_eval_h (mag = 0) and orpm_eval_h_mag (mag = 1).  mag = 1 evaluates, entry by entry, the same
+ * expression with every F, multiplier, sigma, weight and factor replaced by its absolute value and every subtraction
+ * by an addition: the sum of the magnitudes of the terms the entry is made of.  It carries the 1/den of the entry,
+ * so rounding noise of any evaluation order is a small multiple of 2^-52 * mag at every step size. */
+static void eval_h_walk(orpm* o, const double* x, double sigma, const double* lambda, double* values, int mag) {
   ohess* h = (ohess*)o->hess;
   if (!h) return;
   int s = 0;
+  double* lam_abs = NULL;
+  if (mag) {
+    int m = 0;
+    for (int i = 0; i < o->P; i++) m += o->ph[i].ncon;
+    for (int i = 0; i < o->L; i++) m += o->lk[i].nlink;
+    lam_abs = NEW(double, m > 0 ? m : 1);
+    for (int i = 0; i < m; i++) lam_abs[i] = fabs(lambda[i]);
+    lambda = lam_abs;
+    sigma = fabs(sigma);
+  }
   for (int ip = 0; ip < o->P; ip++) {
     const ophase* p = &o->ph[ip];
     const hphase* q = &h->ph[ip];
@@ -313,20 +332,20 @@ void orpm_eval_h(orpm* o, const double* x, double sigma, const double* lambda, d
       double sd_ = 0.0, sp_ = 0.0;                                                                           \
       for (int o_ = 0; o_ < nx; o_++) {                                                                      \
         size_t ix = k + (size_t)o_ * N;                                                                      \
-        double hh = (Fab[ix] - Fa[a][ix] - Fa[b][ix] + F0[ix]) / den;                                        \
+        double hh = diff2(mag, Fab[ix], Fa[a][ix], Fa[b][ix], F0[ix]) / den;                                       \
         double term = lam_d[(size_t)o_ * N + k] * hh;                                                        \
         sd_ = (o_ == 0) ? term : sd_ + term;                                                                 \
       }                                                                                                      \
       for (int o_ = 0; o_ < nc; o_++) {                                                                      \
         size_t ix = k + (size_t)(nx + o_) * N;                                                               \
-        double hh = (Fab[ix] - Fa[a][ix] - Fa[b][ix] + F0[ix]) / den;                                        \
+        double hh = diff2(mag, Fab[ix], Fa[a][ix], Fa[b][ix], F0[ix]) / den;                                       \
         double term = lam_p[(size_t)o_ * N + k] * hh;                                                        \
         sp_ = (o_ == 0) ? term : sp_ + term;                                                                 \
       }                                                                                                      \
       size_t il = k + (size_t)(nx + nc) * N;                                                                 \
-      double hL = (Fab[il] - Fa[a][il] - Fa[b][il] + F0[il]) / den;                                          \
+      double hL = diff2(mag, Fab[il], Fa[a][il], Fa[b][il], F0[il]) / den;                                        \
       double sL = (sigma * p->weights[k]) * hL;                                                              \
-      XI[k] = (tf - t0) / 2.0 * (sL - sd_) + sp_;                                                            \
+      XI[k] = mag ? fabs((tf - t0) / 2.0) * (fabs(sL) + sd_) + sp_ : (tf - t0) / 2.0 * (sL - sd_) + sp_;     \
     }                                                                                                        \
   } while (0)
     double* VI = values + s;
@@ -346,11 +365,11 @@ void orpm_eval_h(orpm* o, const double* x, double sigma, const double* lambda, d
 #define ENDPT(a, b, den, dst)                                                                         \
   do {                                                                                                \
     eval_endpoint(o, &sl, ip + 1, (a), (b), Eab, &Mab);                                               \
-    double hM = (Mab - Ma[a] - Ma[b] + M0) / (den);                                                   \
+    double hM = diff2(mag, Mab, Ma[a], Ma[b], M0) / (den);                                            \
     double ls = 0.0;                                                                                  \
     if (ne > 0) {                                                                                     \
       for (int e_ = 0; e_ < ne; e_++)                                                                 \
-        hEv[e_] = (Eab[e_] - Ea[(size_t)(a)*ne + e_] - Ea[(size_t)(b)*ne + e_] + E0[e_]) / ((den)*1.0); \
+        hEv[e_] = diff2(mag, Eab[e_], Ea[(size_t)(a)*ne + e_], Ea[(size_t)(b)*ne + e_], E0[e_]) / ((den)*1.0); \
       ls = accu_prod(hEv, lam_e, ne);                                                                 \
     }                                                                                                 \
     (dst) = sigma * hM + ls;                                                                          \
@@ -398,6 +417,20 @@ void orpm_eval_h(orpm* o, const double* x, double sigma, const double* lambda, d
     orpm_solcost sc;
     orpm_mk_solcost(&sl, ip + 1, &sc);
     orpm_deriv_lagrange(o, &sc, dLag);
+    if (mag) { /* (|F_v| + |F_0|) / h_v where the derivative is a difference, |d| where it is the user's */
+      int an_d = o->first_derive == RPM_DERIVE_ANALYTIC && o->fun->deriv_dae;
+      int an_l = o->first_derive == RPM_DERIVE_ANALYTIC && o->fun->deriv_lagrange;
+      for (int v = 0; v < ncolD; v++)
+        for (int k = 0; k < N; k++) {
+          double hv = pert_of(o, &sl, v, k);
+          size_t il = k + (size_t)(nx + nc) * N;
+          for (int o_ = 0; o_ < nx; o_++) {
+            size_t ix = k + (size_t)o_ * N, id = ix + (size_t)v * ((size_t)N * nx);
+            dstate[id] = an_d ? fabs(dstate[id]) : (fabs(Fa[v][ix]) + fabs(F0[ix])) / hv;
+          }
+          dLag[k + (size_t)v * N] = an_l ? fabs(dLag[k + (size_t)v * N]) : (fabs(Fa[v][il]) + fabs(F0[il])) / hv;
+        }
+    }
     double* D1 = NEW(double, N); /* sum_lambda_plus_ddae_v - sigma_plus_dLagrange_v */
 #define FIRST(v)                                                                          \
   for (int k = 0; k < N; k++) {                                                           \
@@ -406,7 +439,8 @@ void orpm_eval_h(orpm* o, const double* x, double sigma, const double* lambda, d
       double term = lam_d[(size_t)o_ * N + k] * dstate[(k + (size_t)o_ * N) + (size_t)(v) * ((size_t)N * nx)]; \
       sdd = (o_ == 0) ? term : sdd + term;                                                \
     }                                                                                     \
-    D1[k] = sdd - (sigma * p->weights[k]) * dLag[k + (size_t)(v)*N];                      \
+    D1[k] = mag ? sdd + fabs(sigma * p->weights[k]) * dLag[k + (size_t)(v)*N]             \
+                : sdd - (sigma * p->weights[k]) * dLag[k + (size_t)(v)*N];                \
   }
     double* rows[2];
     rows[0] = NEW(double, (size_t)N * nv); /* hLI_t0x.., hLI_t0u.. */
@@ -417,7 +451,7 @@ void orpm_eval_h(orpm* o, const double* x, double sigma, const double* lambda, d
       for (int k = 0; k < N; k++) {
         double talpha = (1 - p->points[k]) / 2.0, tbeta = (1 + p->points[k]) / 2.0;
         rows[0][k + (size_t)v * N] = 0.5 * D1[k] + talpha * XI[k];
-        rows[1][k + (size_t)v * N] = -0.5 * D1[k] + tbeta * XI[k];
+        rows[1][k + (size_t)v * N] = (mag ? 0.5 : -0.5) * D1[k] + tbeta * XI[k];
       }
     }
     /* tt scalars, :206-218 */
@@ -433,8 +467,8 @@ void orpm_eval_h(orpm* o, const double* x, double sigma, const double* lambda, d
       ta[k] = (1 - p->points[k]) / 2.0;
       tb[k] = (1 + p->points[k]) / 2.0;
       w1[k] = D1[k] + ta[k] * XI[k];
-      w2[k] = -D1[k] + tb[k] * XI[k];
-      w3[k] = tb[k] - ta[k];
+      w2[k] = (mag ? D1[k] : -D1[k]) + tb[k] * XI[k];
+      w3[k] = mag ? fabs(tb[k] - ta[k]) : tb[k] - ta[k];
       w4[k] = tb[k] * XI[k];
     }
     double h_t0t0 = orpm_arma_dot(ta, w1, N);
@@ -532,7 +566,7 @@ void orpm_eval_h(orpm* o, const double* x, double sigma, const double* lambda, d
   do {                                                                                                 \
     LINK_AT((a), (b), Lab);                                                                            \
     double den = (o->tol * (1 + fabs(base[a]))) * (o->tol * (1 + fabs(base[b])));                      \
-    for (int q_ = 0; q_ < nl; q_++) hL[q_] = (Lab[q_] - La[(size_t)(a)*nl + q_] - La[(size_t)(b)*nl + q_] + L0[q_]) / den; \
+    for (int q_ = 0; q_ < nl; q_++) hL[q_] = diff2(mag, Lab[q_], La[(size_t)(a)*nl + q_], La[(size_t)(b)*nl + q_], L0[q_]) / den; \
     (dst) = accu_prod(hL, lam_l, nl);                                                                  \
   } while (0)
     for (int i = 0; i < nxl; i++)
@@ -550,4 +584,15 @@ void orpm_eval_h(orpm* o, const double* x, double sigma, const double* lambda, d
     free(hL);
     free(w);
   }
+  free(lam_abs);
+}
+
+void orpm_eval_h(orpm* o, const double* x, double sigma, const double* lambda, double* values) {
+  eval_h_walk(o, x, sigma, lambda, values, 0);
+}
+
+/* per stored entry: the sum of the magnitudes of the terms orpm_eval_h adds up for it (>= |H| entrywise, even in
+ * lambda and sigma, 0 only where every term is 0).  The yardstick of the entrywise Hessian comparisons in tests/. */
+void orpm_eval_h_mag(orpm* o, const double* x, double sigma, const double* lambda, double* values) {
+  eval_h_walk(o, x, sigma, lambda, values, 1);
 }

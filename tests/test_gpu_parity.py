@@ -357,6 +357,15 @@ def test_exact_hessian(built, name, make, tol):
     hv, hr = eng.eval_h(x, sigma, lam), orc.eval_h(x, sigma, lam)
     scale = max(1.0, float(np.max(np.abs(hr))))
     assert np.max(np.abs(hv - hr)) <= tol * scale
+    # the global scale above is larger than most of the matrix; the rule that pins every entry is the entrywise one of
+    # tests/test_gpu_hessian.py, |d|_i <= C 2^-52 mag_i.  It is applied at that module's iterates: at the 0.1 % perturbation
+    # of the guess used above the functions cancel internally and two builds of the ORACLE already differ by up to 390
+    # of those units (tests/_hessian_cases.py::iterates).  At the default step of this test the rule, too, resolves under
+    # 2 % of the entries to 1e-6 of their value: what pins the matrix is tests/test_gpu_hessian.py at step 1e-3
+    import _hessian_cases as hc
+    for xe in hc.iterates(orc.starting_point()):
+        for sg, lm in hc.draws(eng.m):
+            hc.assert_entrywise(eng.eval_h(xe, sg, lm), orc.eval_h(xe, sg, lm), orc.eval_h_mag(xe, sg, lm), what=name)
     # the assembled matrix acts like the derivative of the Lagrangian gradient (oracle-free consistency check;
     # loose because of the reference's pertxf(i)-for-pertxf(j) denominators, LpHessian.cpp:1588,1612)
     if name in ("bryson_denham", "hypersensitive", "quadrotor"):
