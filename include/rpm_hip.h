@@ -343,6 +343,21 @@ int rpm_ipm_debug_solve(rpm_ipm* s, const double* k_storage, const double* rhs, 
  * tells whether the layout can hold entry (ua, uc) */
 int rpm_ipm_debug_solve_dense(rpm_ipm* s, const double* k_dense, const double* rhs, double* sol, int* n_pos, int* n_neg);
 int rpm_ipm_debug_slot(rpm_ipm* s, int ua, int uc, long long* offset);
+/* test hooks of the limited-memory BFGS kernels (host pointers; RPM_E_UNSUPPORTED on a solver with the exact Hessian).  They run
+ * the solver's own launchers on the caller's data:
+ *   _step   one pass of the update as the solve loop runs it after the residual: x, glag_new = grad_x L(x, lambda), glag_old =
+ *           grad_x L(x_previous, lambda) (n_instances x n each), mode / status per instance (NULL = 0: a regular, running
+ *           instance).  reset != 0 starts a sequence: bounds and instance records as at the start of a solve, empty memory.
+ *           x at fixed variables is the caller's to keep at the bound.
+ *   _state  per instance: record[8] = sigma, pairs held, consecutive skips, previous iterate valid, updates, skips, and the two
+ *           decision words; M (12 x 12); the pair columns S, Y (6 x n each, oldest first).  A NULL array is left out.
+ *   _solve  (K0 - E M^-1 E') d = rhs with the memory as it stands: K0 as nnz lower-triangle entries (rows >= cols, unknown
+ *           order, each once; one structure, values n_instances x nnz), rhs and sol n_instances x Nt in unknown order.  Every
+ *           instance is made live; an entry the layout has no slot for gives RPM_E_INVALID. */
+int rpm_ipm_debug_lbfgs_step(rpm_ipm* s, int reset, const double* x, const double* glag_new, const double* glag_old, const int* mode,
+                             const int* status);
+int rpm_ipm_debug_lbfgs_state(rpm_ipm* s, double* record, double* M, double* S, double* Y);
+int rpm_ipm_debug_lbfgs_solve(rpm_ipm* s, int nnz, const int* rows, const int* cols, const double* vals, const double* rhs, double* sol);
 
 /* ---- device-resident variants (inputs/outputs already in HBM; used by benches, by the
  *      MPC sweep and by any device-side solver).  Pointers are device pointers on the

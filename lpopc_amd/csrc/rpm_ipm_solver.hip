@@ -618,6 +618,105 @@ int rpm_ipm_debug_slot(rpm_ipm* h, int ua, int uc, long long* offset) {
   return RPM_OK;
 }
 
+/* test hooks of the limited-memory kernels (rpm_ipm_lbfgs.hip): the production launchers on the caller's data, no kernel of
+ * their own.  RPM_E_UNSUPPORTED on a solver created with the exact Hessian. */
+/* One pass of the solve loop between ipm_launch_residual and fetch_counts: x (B x n) into the first n entries of every row of
+ * D.v, glag_new into D.glag, glag_old into D.lb_gold, mode / status (B ints, NULL = 0) into the instance records, then
+ * lb_launch_update.  reset != 0: ipm_launch_init first (vl / vu from the solver's bounds, fresh instance records), then
+ * lb_launch_reset; the first call of a sequence has to reset.  x at fixed variables is the caller's to keep at the bound. */
+int rpm_ipm_debug_lbfgs_step(rpm_ipm* h, int reset, const double* x, const double* glag_new, const double* glag_old, const int* mode,
+                             const int* status) {
+  if (!h || !x || !glag_new || !glag_old) return RPM_E_INVALID;
+  if (!h->lbfgs) { h->err = "rpm_ipm_debug_lbfgs_step: the solver was created with the exact Hessian"; return RPM_E_UNSUPPORTED; }
+  const IpmPlan& p = h->plan;
+  IpmDev& D = h->D;
+  hipStream_t st = static_cast<hipStream_t>(dev_stream(h->eng->e));
+  const size_t B = size_t(D.B), row = size_t(p.n) * sizeof(double), pitch = size_t(p.nv) * sizeof(double);
+  IPM_TRY(h, hipMemcpyAsync(D.xt, x, B * row, hipMemcpyHostToDevice, st));
+  if (reset) {
+    ipm_launch_init(D, D.xt, st);
+    lb_launch_reset(D, st);
+  }
+  IPM_TRY(h, hipMemcpy2DAsync(D.v, pitch, x, row, row, B, hipMemcpyHostToDevice, st));
+  IPM_TRY(h, hipMemcpy2DAsync(D.glag, pitch, glag_new, row, row, B, hipMemcpyHostToDevice, st));
+  IPM_TRY(h, hipMemcpy2DAsync(D.lb_gold, pitch, glag_old, row, row, B, hipMemcpyHostToDevice, st));
+  std::vector<IpmInst> inst(B);
+  IPM_TRY(h, hipMemcpyAsync(inst.data(), D.inst, B * sizeof(IpmInst), hipMemcpyDeviceToHost, st));
+  IPM_TRY(h, hipStreamSynchronize(st));
+  for (size_t bi = 0; bi < B; ++bi) {
+    inst[bi].mode = mode ? mode[bi] : 0;
+    inst[bi].status = status ? status[bi] : 0;
+  }
+  IPM_TRY(h, hipMemcpyAsync(D.inst, inst.data(), B * sizeof(IpmInst), hipMemcpyHostToDevice, st));
+  lb_launch_update(D, st);
+  int rc = launch_check(h, "limited-memory update");
+  if (rc) return rc;
+  IPM_TRY(h, hipStreamSynchronize(st));
+  return RPM_OK;
+}
+
+/* what the update left: per instance the first 8 doubles of its record (sigma, pairs held, consecutive skips, previous iterate
+ * valid, updates, skips, the two decision words), M (B x 12 x 12) and the pair columns S, Y (B x 6 x n, oldest first); NULL = skip */
+int rpm_ipm_debug_lbfgs_state(rpm_ipm* h, double* record, double* M, double* S, double* Y) {
+  if (!h) return RPM_E_INVALID;
+  if (!h->lbfgs) { h->err = "rpm_ipm_debug_lbfgs_state: the solver was created with the exact Hessian"; return RPM_E_UNSUPPORTED; }
+  IpmDev& D = h->D;
+  hipStream_t st = static_cast<hipStream_t>(dev_stream(h->eng->e));
+  const size_t B = size_t(D.B), th2 = size_t(2 * IPM_LB_H) * size_t(2 * IPM_LB_H), cols = B * IPM_LB_H * size_t(D.n);
+  IPM_TRY(h, hipStreamSynchronize(st));
+  std::vector<double> small(B * IPM_LB_SMALL);
+  IPM_TRY(h, hipMemcpy(small.data(), D.lb_small, small.size() * sizeof(double), hipMemcpyDeviceToHost));
+  for (size_t bi = 0; bi < B; ++bi) {
+    if (record) std::memcpy(record + bi * 8, small.data() + bi * IPM_LB_SMALL, 8 * sizeof(double));
+    if (M) std::memcpy(M + bi * th2, small.data() + bi * IPM_LB_SMALL + 8, th2 * sizeof(double));
+  }
+  if (S) IPM_TRY(h, hipMemcpy(S, D.lb_S, cols * sizeof(double), hipMemcpyDeviceToHost));
+  if (Y) IPM_TRY(h, hipMemcpy(Y, D.lb_Y, cols * sizeof(double), hipMemcpyDeviceToHost));
+  return RPM_OK;
+}
+
+/* K d = rhs with K = K0 - E M^-1 E' and the memory as it stands, the way an iteration does it: K0 (the matrix of the diagonal
+ * Hessian; lower triangle in coordinate form, unknown order, every entry once, one structure for all instances, values B x nnz)
+ * is factored, Z = K0^-1 E and C = M - E'Z follow, rhs (B x Nt, unknown order) is substituted and corrected (check_status 1).
+ * Every instance is made live first.  An entry the layout has no slot for: RPM_E_INVALID. */
+int rpm_ipm_debug_lbfgs_solve(rpm_ipm* h, int nnz, const int* rows, const int* cols, const double* vals, const double* rhs, double* sol) {
+  if (!h || nnz < 0 || (nnz && (!rows || !cols || !vals)) || !rhs || !sol) return RPM_E_INVALID;
+  if (!h->lbfgs) { h->err = "rpm_ipm_debug_lbfgs_solve: the solver was created with the exact Hessian"; return RPM_E_UNSUPPORTED; }
+  const IpmPlan& p = h->plan;
+  IpmDev& D = h->D;
+  hipStream_t st = static_cast<hipStream_t>(dev_stream(h->eng->e));
+  const size_t B = size_t(D.B), Nt = size_t(p.Nt);
+  std::vector<double> store(B * size_t(p.storage()), 0.0), r(B * size_t(p.Nt_alloc), 0.0);
+  for (int k = 0; k < nnz; ++k) {
+    const int a = rows[k], c = cols[k];
+    const long long o = (a >= c && c >= 0 && a < p.Nt) ? ipm_plan_offset(p, a, c) : -1;
+    if (o < 0) { h->err = "rpm_ipm_debug_lbfgs_solve: entry (" + std::to_string(a) + ", " + std::to_string(c) + ") has no slot in the layout"; return RPM_E_INVALID; }
+    for (size_t bi = 0; bi < B; ++bi) store[bi * size_t(p.storage()) + size_t(o)] = vals[bi * size_t(nnz) + size_t(k)];
+  }
+  for (size_t bi = 0; bi < B; ++bi)
+    for (size_t a = 0; a < Nt; ++a) r[bi * p.Nt_alloc + p.pos[a]] = rhs[bi * Nt + a];
+  std::vector<IpmInst> inst(B);
+  for (auto& s2 : inst) { s2 = IpmInst{}; s2.refactor = 1; }
+  IPM_TRY(h, hipMemcpyAsync(D.inst, inst.data(), B * sizeof(IpmInst), hipMemcpyHostToDevice, st));
+  IPM_TRY(h, hipMemcpyAsync(D.K, store.data(), store.size() * sizeof(double), hipMemcpyHostToDevice, st));
+  IPM_TRY(h, hipMemcpyAsync(D.rhs, r.data(), r.size() * sizeof(double), hipMemcpyHostToDevice, st));
+  const int df_keep = D.df_on;
+  D.df_on = 0;                 // factor what is in the storage, not the solver's own matrix
+  kkt_launch_factor(D, h->factor_mt, h->factor_lds, st);
+  lb_launch_columns_and_solve(D, st);
+  lb_launch_small(D, st);
+  kkt_launch_solve(D, 1, st);
+  lb_launch_correct(D, 1, st);
+  D.df_on = df_keep;
+  int rc = launch_check(h, "limited-memory solve");
+  if (rc) return rc;
+  IPM_TRY(h, hipStreamSynchronize(st));
+  IPM_TRY(h, hipMemcpy(r.data(), D.rhs, r.size() * sizeof(double), hipMemcpyDeviceToHost));
+  for (size_t bi = 0; bi < B; ++bi)
+    for (size_t a = 0; a < Nt; ++a) sol[bi * Nt + a] = r[bi * p.Nt_alloc + p.pos[a]];
+  return RPM_OK;
+}
+
 /* KKT position of every unknown ([0,n) variables, then the slacks, then the m multipliers) — for tests and tools */
 int rpm_ipm_get_permutation(rpm_ipm* h, int* pos, int capacity) {
   if (!h || !pos || capacity < h->plan.Nt) return RPM_E_INVALID;

@@ -38,6 +38,7 @@ ABI_SYMBOLS = [
     "rpm_sweep_create", "rpm_sweep_destroy", "rpm_sweep_last_error", "rpm_sweep_size", "rpm_sweep_engine", "rpm_sweep_solver", "rpm_sweep_share",
     "rpm_sweep_set_option", "rpm_sweep_set_bounds", "rpm_sweep_solve", "rpm_sweep_get_stats",
     "rpm_ipm_get_stats", "rpm_ipm_get_subproblems", "rpm_ipm_get_trace", "rpm_ipm_get_restorations", "rpm_ipm_get_kernel_times", "rpm_ipm_solve", "rpm_ipm_solve_dev", "rpm_ipm_get_permutation", "rpm_ipm_debug_solve", "rpm_ipm_debug_solve_dense", "rpm_ipm_debug_slot",
+    "rpm_ipm_debug_lbfgs_step", "rpm_ipm_debug_lbfgs_state", "rpm_ipm_debug_lbfgs_solve",
 ]
 
 
@@ -136,6 +137,9 @@ def lib(path=None):
     L.rpm_ipm_debug_solve.argtypes = [vp, dp, dp, dp, ip, ip]
     L.rpm_ipm_debug_solve_dense.argtypes = [vp, dp, dp, dp, ip, ip]
     L.rpm_ipm_debug_slot.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_longlong)]
+    L.rpm_ipm_debug_lbfgs_step.argtypes = [vp, C.c_int, dp, dp, dp, ip, ip]
+    L.rpm_ipm_debug_lbfgs_state.argtypes = [vp, dp, dp, dp, dp]
+    L.rpm_ipm_debug_lbfgs_solve.argtypes = [vp, C.c_int, ip, ip, dp, dp, dp]
     L.rpm_shard_segments.argtypes = [vp, C.c_int, C.c_int, C.POINTER(_abi.rpm_segment), ip, ip]
     L.rpm_shard_pack_dev.argtypes = [vp, C.c_int, vp, vp, vp]
     L.rpm_shard_unpack_dev.argtypes = [vp, C.c_int, vp, C.c_int, vp, vp]
@@ -745,6 +749,36 @@ class BatchedIPM:
         off = C.c_longlong()
         self._chk(self._L.rpm_ipm_debug_slot(self._h, int(ua), int(uc), C.byref(off)))
         return off.value
+
+    def debug_lbfgs_step(self, x, glag_new, glag_old, reset=False, mode=None, status=None):
+        """One pass of the limited-memory update (rpm_ipm_debug_lbfgs_step): x, glag_new, glag_old (n_instances, n); mode, status
+        per instance (None = 0).  The first call of a sequence resets."""
+        B, n = self._e.n_instances, self._e.n
+        a = [np.ascontiguousarray(v, dtype=np.float64) for v in (x, glag_new, glag_old)]
+        assert all(v.shape == (B, n) for v in a)
+        flags = [None if f is None else np.ascontiguousarray(f, dtype=np.int32) for f in (mode, status)]
+        assert all(f is None or f.shape == (B,) for f in flags)
+        self._chk(self._L.rpm_ipm_debug_lbfgs_step(self._h, int(bool(reset)), _dp(a[0]), _dp(a[1]), _dp(a[2]),
+                                                   *[None if f is None else _ip(f) for f in flags]))
+
+    def debug_lbfgs_state(self):
+        """-> dict(record (B, 8): sigma, pairs held, consecutive skips, previous iterate valid, updates, skips, two decision words;
+        M (B, 12, 12); S, Y (B, 6, n), oldest pair first)."""
+        B, n = self._e.n_instances, self._e.n
+        out = {"record": np.zeros((B, 8)), "M": np.zeros((B, 12, 12)), "S": np.zeros((B, 6, n)), "Y": np.zeros((B, 6, n))}
+        self._chk(self._L.rpm_ipm_debug_lbfgs_state(self._h, _dp(out["record"]), _dp(out["M"]), _dp(out["S"]), _dp(out["Y"])))
+        return out
+
+    def debug_lbfgs_solve(self, rows, cols, vals, rhs):
+        """(K0 - E M^-1 E') d = rhs with the memory as it stands: K0 as lower-triangle entries (rows >= cols, unknown order),
+        vals (n_instances, nnz), rhs (n_instances, Nt) -> d (n_instances, Nt)."""
+        B, nt = self._e.n_instances, self.info()["kkt_order"]
+        rows, cols = np.ascontiguousarray(rows, dtype=np.int32), np.ascontiguousarray(cols, dtype=np.int32)
+        v, r = np.ascontiguousarray(vals, dtype=np.float64), np.ascontiguousarray(rhs, dtype=np.float64)
+        assert rows.shape == cols.shape == (v.shape[1],) and v.shape[0] == B and r.shape == (B, nt)
+        sol = np.zeros((B, nt))
+        self._chk(self._L.rpm_ipm_debug_lbfgs_solve(self._h, rows.size, _ip(rows), _ip(cols), _dp(v), _dp(r), _dp(sol)))
+        return sol
 
     def solve(self, x0):
         """x0: (n_instances, n) starting points -> dict(x, lambda, obj, status, iterations, kkt_error)."""

@@ -151,6 +151,65 @@ class _GradientScaled:
         return self.sf * self.o.eval_h(x, sigma, lam * self.sc / self.sf)     # as the device forms it: one scalar factor outside
 
 
+class LimitedMemory:
+    """Ipopt's LimMemQuasiNewtonUpdater with its defaults (BFGS, scalar1 scaling), in the arithmetic of `dtype`: the history of
+    pairs (oldest first), sigma, the counter of consecutive skips, the previous iterate (`prev`, None = not valid: the next
+    point only becomes the previous one) and the compact representation  B = sigma I - Q M^-1 Q',  Q = [sigma S  Y],
+    M = [[sigma S'S, L], [L', -D]]  (Byrd, Nocedal, Schnabel 1994).  solve() runs it in float64; tests run it in
+    numpy.longdouble against the device kernels."""
+
+    def __init__(self, n, dtype=np.float64, max_history=6, max_skipping=2, init_val_min=1e-8, init_val_max=1e8):
+        self.n, self.dtype = n, dtype
+        self.max_history, self.max_skipping, self.init_val_min, self.init_val_max = max_history, max_skipping, init_val_min, init_val_max
+        self.updates = self.skips = 0
+        self.empty()
+
+    def empty(self):
+        """no pairs, sigma = 1, no previous iterate (the counters of a solve go on)"""
+        self.S, self.Y, self.sigma, self.skipped, self.prev = [], [], self.dtype(1.0), 0, None
+
+    def update(self, s_, y_):
+        """the pair (s, y) of an accepted step (y already 0 at fixed variables) -> "none" (s = 0: nothing to learn), "skip",
+        "skip-empty" (the second skip in a row: the memory is emptied) or "store" """
+        s_, y_ = np.asarray(s_, dtype=self.dtype), np.asarray(y_, dtype=self.dtype)
+        sn, yn = np.linalg.norm(s_), np.linalg.norm(y_)
+        if sn == 0.0:
+            return "none"                               # lambda changed only (recalc_y): nothing to learn
+        sty = self.dtype(s_ @ y_)
+        if not (sty > np.sqrt(np.finfo(float).eps) * sn * yn):
+            self.skips += 1
+            self.skipped += 1
+            if self.skipped >= self.max_skipping:
+                self.S, self.Y, self.sigma, self.skipped = [], [], self.dtype(1.0), 0
+                return "skip-empty"
+            return "skip"
+        self.skipped = 0
+        self.S.append(s_)
+        self.Y.append(y_)
+        if len(self.S) > self.max_history:
+            self.S.pop(0)
+            self.Y.pop(0)
+        self.sigma = min(self.dtype(self.init_val_max), max(self.dtype(self.init_val_min), sty / self.dtype(s_ @ s_)))
+        self.updates += 1
+        return "store"
+
+    def compact(self):
+        """-> Q (n x 2c), M (2c x 2c) for the c pairs held"""
+        Sm, Ym = np.array(self.S, dtype=self.dtype).reshape(len(self.S), self.n).T, np.array(self.Y, dtype=self.dtype).reshape(len(self.Y), self.n).T
+        SY = Sm.T @ Ym
+        Lm, Dm = np.tril(SY, -1), np.diag(np.diag(SY))
+        Mm = np.block([[self.sigma * (Sm.T @ Sm), Lm], [Lm.T, -Dm]])
+        return np.hstack([self.sigma * Sm, Ym]), Mm
+
+    def matrix(self, solve=np.linalg.solve):
+        """B (n x n) from the compact representation; `solve` for dtypes numpy's LAPACK does not take"""
+        Bm = self.sigma * np.eye(self.n, dtype=self.dtype)
+        if self.S:
+            Q, Mm = self.compact()
+            Bm = Bm - Q @ solve(Mm, Q.T)
+        return Bm
+
+
 def solve(orc, x0, x_l=None, x_u=None, **options):
     """-> dict(x, lambda, obj, status, iterations, kkt_error, trace); status codes as rpm_ipm_solve (0 converged, 1 acceptable level, ...)."""
     o = dict(DEFAULTS)
@@ -167,7 +226,8 @@ def solve(orc, x0, x_l=None, x_u=None, **options):
     ji, jj = orc.jac_structure()
     lbfgs = o["hessian_approximation"] == "limited-memory"
     hi, hj = (np.zeros(0, dtype=int), np.zeros(0, dtype=int)) if lbfgs else orc.hess_structure()
-    lm = dict(S=[], Y=[], sigma=1.0, skipped=0, prev=None, updates=0, skips=0)
+    lm = LimitedMemory(n, max_history=o["limited_memory_max_history"], max_skipping=o["limited_memory_max_skipping"],
+                       init_val_min=o["limited_memory_init_val_min"], init_val_max=o["limited_memory_init_val_max"])
     ineq = np.nonzero(gl != gu)[0]
     ns, nv = ineq.size, n + ineq.size
     row_slack = -np.ones(m, dtype=int)
@@ -230,43 +290,12 @@ def solve(orc, x0, x_l=None, x_u=None, **options):
 
     def lm_update(x_new, glag_x_new, lam_new):
         """Ipopt's LimMemQuasiNewtonUpdater::UpdateHessian (BFGS): one pair per accepted step."""
-        if lm["prev"] is None:
+        if lm.prev is None:
             return
-        x_old, grad_old, jv_old = lm["prev"]
+        x_old, grad_old, jv_old = lm.prev
         g_old = grad_old.copy()
         np.add.at(g_old, jj, jv_old * lam_new[ji])     # grad_x L(x_old, lambda_new): the SAME multipliers on both sides
-        s_, y_ = x_new - x_old, glag_x_new - g_old
-        y_ = np.where(free[:n], y_, 0.0)
-        sn, yn = np.linalg.norm(s_), np.linalg.norm(y_)
-        if sn == 0.0:
-            return                                      # lambda changed only (recalc_y): nothing to learn
-        sty = float(s_ @ y_)
-        if not (sty > np.sqrt(np.finfo(float).eps) * sn * yn):
-            lm["skips"] += 1
-            lm["skipped"] += 1
-            if lm["skipped"] >= o["limited_memory_max_skipping"]:
-                lm["S"], lm["Y"], lm["sigma"], lm["skipped"] = [], [], 1.0, 0
-            return
-        lm["skipped"] = 0
-        lm["S"].append(s_)
-        lm["Y"].append(y_)
-        if len(lm["S"]) > o["limited_memory_max_history"]:
-            lm["S"].pop(0)
-            lm["Y"].pop(0)
-        lm["sigma"] = min(o["limited_memory_init_val_max"], max(o["limited_memory_init_val_min"], sty / float(s_ @ s_)))
-        lm["updates"] += 1
-
-    def lm_matrix():
-        """B (n x n) from the compact representation."""
-        Bm = lm["sigma"] * np.eye(n)
-        if lm["S"]:
-            Sm, Ym = np.array(lm["S"]).T, np.array(lm["Y"]).T
-            SY = Sm.T @ Ym
-            Lm, Dm = np.tril(SY, -1), np.diag(np.diag(SY))
-            Mm = np.block([[lm["sigma"] * (Sm.T @ Sm), Lm], [Lm.T, -Dm]])
-            Q = np.hstack([lm["sigma"] * Sm, Ym])
-            Bm = Bm - Q @ np.linalg.solve(Mm, Q.T)
-        return Bm
+        lm.update(x_new - x_old, np.where(free[:n], glag_x_new - g_old, 0.0))
 
     def ls_multipliers(xr, jR):
         """least-squares multipliers (section 3.6): [[I, A^T], [A, -delta_c]] [w; lambda] = -[grad f - zL + zU; 0]; 0 when they exceed mult_reset"""
@@ -406,7 +435,7 @@ def solve(orc, x0, x_l=None, x_u=None, **options):
         c = cons(v, g)
         if lbfgs:
             lm_update(x.copy(), glag[:n].copy(), lam)
-            lm["prev"] = (x.copy(), grad.copy(), jv.copy())
+            lm.prev = (x.copy(), grad.copy(), jv.copy())
         dinf = np.max(np.abs((glag - zL + zU)[free])) if free.any() else 0.0
         cinf, theta = (np.max(np.abs(c)), np.abs(c).sum()) if m else (0.0, 0.0)
         prods = np.concatenate([zL[lo] * (v[lo] - vl[lo]), zU[up] * (vu[up] - v[up])])
@@ -476,7 +505,7 @@ def solve(orc, x0, x_l=None, x_u=None, **options):
         W = np.zeros((nv, nv))
         if lbfgs:
             hv = np.zeros(0)
-            W[:n, :n] = lm_matrix()
+            W[:n, :n] = lm.matrix()
         else:
             hv = orc.eval_h(x, 1.0, lam)
             np.add.at(W, (hi, hj), hv)
@@ -586,7 +615,7 @@ def solve(orc, x0, x_l=None, x_u=None, **options):
                 break
         if not accepted and status == 3 and o["resto"] and theta > o["tol"]:
             status = _restore()
-            lm.update(S=[], Y=[], sigma=1.0, skipped=0, prev=None)      # the point moved by another problem's steps
+            lm.empty()      # the point moved by another problem's steps
             if status is None:
                 continue
         elif not accepted and status == 3 and o["resto"] and n_recalc < o["max_recalc_y"]:
@@ -609,4 +638,4 @@ def solve(orc, x0, x_l=None, x_u=None, **options):
                           smin=float(min(dl[lo].min(initial=1e300), du[up].min(initial=1e300)))))
         it += 1
     return dict(x=v[:n].copy(), slack=v[n:].copy(), **{"lambda": lam * sc_u / sf_u}, obj=f / sf_u, status=status, iterations=it, kkt_error=err0, trace=trace, restorations=n_resto,
-                multiplier_recalculations=n_recalc, lm_updates=lm["updates"], lm_skips=lm["skips"])
+                multiplier_recalculations=n_recalc, lm_updates=lm.updates, lm_skips=lm.skips)
