@@ -230,6 +230,31 @@ int rpm_solution_error_batch_dev(rpm_engine* e, const double* d_x, const int* d_
 int rpm_solution_error_batch(rpm_engine* e, const double* x, const int* instance_mask, double* interval_error,
                              double* rel_err_max, double* rel_err, int* nonfinite);
 
+/* A sweep's solutions carried onto another mesh: the fourth step of solve, estimate, refine, re-solve.  `from` is the engine the
+ * solutions were computed on, `to` an engine of the same problem (same problem id, phase count, per-phase nx / nu / nq and
+ * n_instances) on any other mesh: refined, coarsened or the same; to == from is legal.  x_from: n_instances x from.n, x_to:
+ * n_instances x to.n, both instance-major; nonfinite: n_instances ints or NULL, 1 when any carried value of the instance is NaN
+ * or Inf (an instance with NaN / Inf or with tf == t0 yields NaN / Inf for itself only).  Per instance, phase and column the
+ * arithmetic is that of the one-instance route — rpm_nlp2op_control's time and control-at-tau=1, a new rpm_create carrying them
+ * as the guess, rpm_get_starting_point — operation by operation: time[k] = (tf - t0) (tau_k + 1) / 2 + t0, knots
+ * 2 (time[k] - time[0]) / (time[N] - time[0]) - 1, the natural cubic spline of LpGuessChecker through the N + 1 knots evaluated
+ * at the target's points (states also at 1), t0 = time[0], tf = time[N], static parameters copied.  Only the spline's cubes
+ * differ: A * A * A on the device, pow(A, 3) on the host, so the two routes agree to rounding, not to the bit; t0, tf and the
+ * parameters agree to the bit.  Multipliers are not carried (rpm_ipm_solve takes no starting lambda).  The caller builds the
+ * next engine and re-applies per-instance constants and bounds.
+ * Argument errors are decided on the host before anything is queued: NULL arrays, engines that do not match, engines bound
+ * to different devices, overlapping x_from / x_to: RPM_E_INVALID; interval-sharded engines, a column that does not fit one
+ * workgroup's LDS: RPM_E_UNSUPPORTED (columns that do not fit together are dealt over several workgroups).  The message is
+ * rpm_last_error(from).
+ * The _dev form takes device arrays and queues one launch (two with d_nonfinite) on `stream`.  The first call on a pair of
+ * engines uploads a small launch plan (and initialises an engine that has no device yet on the other's device); every later
+ * call allocates nothing, copies nothing and never synchronises, so it can follow rpm_ipm_solve_dev on the caller's stream and be
+ * captured into a graph.  The host-pointer form stages its arrays and blocks.  The calling thread's current device is
+ * restored.  Option "carry_tile" (0 = automatic, 1, 2, 4, 8) on `from`: instances per workgroup; every value gives the same bits. */
+int rpm_carry_solution_batch_dev(rpm_engine* from, rpm_engine* to, const double* d_x_from, double* d_x_to, int* d_nonfinite,
+                                 void* stream);
+int rpm_carry_solution_batch(rpm_engine* from, rpm_engine* to, const double* x_from, double* x_to, int* nonfinite);
+
 /* hp-Liu refinement: LiuHpMeshRefineAlg::RefineMesh, Core/LpLiuHpMeshRefineAlg.cpp:12-260 (with Reducing_N :438-481,
  * Increasing_N :379-436, Dividing_mesh :321-377, CanWeIncreaseN :606-681; Merging_mesh's verdict is unused by the
  * reference, equal-N satisfied neighbours always merge).  The object keeps the reference's histories (meshes with their
@@ -562,6 +587,10 @@ int rpm_sweep_solve(rpm_sweep* s, double* x, double* lambda, double* obj, int* s
  * error as long as one instance of the sweep is included. */
 int rpm_sweep_solution_error(rpm_sweep* s, const double* x, const int* instance_mask, double* interval_error,
                              double* rel_err_max, double* rel_err, int* nonfinite);
+/* rpm_carry_solution_batch on every share side by side (x_from: B x from.n, x_to: B x to.n, nonfinite: B or NULL).  The two
+ * sweeps must deal their instances alike (same device list, same n_instances), else RPM_E_INVALID; the message is
+ * rpm_sweep_last_error(from). */
+int rpm_sweep_carry_solution(rpm_sweep* from, rpm_sweep* to, const double* x_from, double* x_to, int* nonfinite);
 int rpm_sweep_get_stats(rpm_sweep* s, int* iterations, int* factorizations, int* trial_points);
 
 #ifdef __cplusplus

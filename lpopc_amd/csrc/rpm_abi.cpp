@@ -8,6 +8,8 @@
 #include <new>
 #include <string>
 
+#include <atomic>
+
 #include "rpm_engine.hpp"
 #include "rpm_pin.h"
 
@@ -57,6 +59,8 @@ int rpm_create(const rpm_problem_desc* desc, rpm_engine** out) {
     delete h;
     return rc;
   }
+  static std::atomic<long long> next_serial{1};
+  h->e.serial = next_serial.fetch_add(1);
   *out = h;
   return RPM_OK;
 }
@@ -375,6 +379,30 @@ int rpm_solution_error_batch(rpm_engine* h, const double* x, const int* instance
   RPM_GUARD_END(e)
 }
 
+// ---- a sweep's solutions carried onto another mesh of the same problem (rpm_carry_kernels.hip) -----------------------
+int rpm_carry_solution_batch_dev(rpm_engine* from, rpm_engine* to, const double* d_x_from, double* d_x_to, int* d_nonfinite,
+                                 void* stream) {
+  if (!from) return RPM_E_INVALID;
+  Engine& e = from->e;
+  RPM_GUARD_BEGIN
+  if (!to) return fail(e, RPM_E_INVALID, "carry_solution_batch_dev: the target engine is NULL");
+  if (!d_x_from) return fail(e, RPM_E_INVALID, "carry_solution_batch_dev: d_x_from is NULL");
+  if (!d_x_to) return fail(e, RPM_E_INVALID, "carry_solution_batch_dev: d_x_to is NULL");
+  return rpm::dev_carry_batch(e, to->e, d_x_from, d_x_to, d_nonfinite, stream);
+  RPM_GUARD_END(e)
+}
+
+int rpm_carry_solution_batch(rpm_engine* from, rpm_engine* to, const double* x_from, double* x_to, int* nonfinite) {
+  if (!from) return RPM_E_INVALID;
+  Engine& e = from->e;
+  RPM_GUARD_BEGIN
+  if (!to) return fail(e, RPM_E_INVALID, "carry_solution_batch: the target engine is NULL");
+  if (!x_from) return fail(e, RPM_E_INVALID, "carry_solution_batch: x_from is NULL");
+  if (!x_to) return fail(e, RPM_E_INVALID, "carry_solution_batch: x_to is NULL");
+  return rpm::host_carry_batch(e, to->e, x_from, x_to, nonfinite);
+  RPM_GUARD_END(e)
+}
+
 // ---- hp-Liu mesh refinement (second method) ------------------------------------
 struct rpm_hpliu {
   rpm::HpLiu h;
@@ -619,6 +647,14 @@ int rpm_set_option(rpm_engine* h, const char* key, int value) {
   } else if (k == "mesh_err_tile") {
     if (value != 0 && value != 1 && value != 2 && value != 4 && value != 8 && value != 16) return fail(e, RPM_E_INVALID, "mesh_err_tile must be 0 (auto), 1, 2, 4, 8 or 16");
     e.opt_mesh_err_tile = value;
+  } else if (k == "carry_tile") {
+    if (value != 0 && value != 1 && value != 2 && value != 4 && value != 8) return fail(e, RPM_E_INVALID, "carry_tile must be 0 (auto), 1, 2, 4 or 8");
+    e.opt_carry_tile = value;
+    return RPM_OK;
+  } else if (k == "carry_lds_bytes") {   // for tests of the column split: the LDS one workgroup of the carry may use
+    if (value < 0) return fail(e, RPM_E_INVALID, "carry_lds_bytes must be 0 (what the device offers) or a byte count");
+    e.opt_carry_lds = value;
+    return RPM_OK;
   } else if (k == "pipeline") {
     if (value < -1 || value > 1) return fail(e, RPM_E_INVALID, "pipeline must be -1 (auto), 0 or 1");
     e.opt_pipeline = value;
@@ -654,6 +690,9 @@ int rpm_get_option(rpm_engine* h, const char* key, int* value) {
   else if (k == "role_loop") *value = e.role_looped ? 1 : 0;
   else if (k == "pipeline") *value = e.opt_pipeline;
   else if (k == "mesh_err_tile") *value = e.opt_mesh_err_tile;
+  else if (k == "carry_tile") *value = e.opt_carry_tile;
+  else if (k == "carry_lds_bytes") *value = e.opt_carry_lds;
+  else if (k == "carry_groups") *value = rpm::carry_group_count(e);   // workgroups per tile of instances under the current options (0: a column does not fit)
   else if (k == "stage_roles") *value = e.opt_stage_roles;
   else if (k == "const_once") *value = e.opt_const_once;
   else if (k == "instance_align") *value = e.opt_instance_align;

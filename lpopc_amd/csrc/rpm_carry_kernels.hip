@@ -1,0 +1,421 @@
+// rpm_carry_kernels.hip — the solutions of a whole sweep carried onto another mesh of the same problem: what lpopc does
+// between two meshes (Nlp2OpConverter::Nlp2OpControl installs time / state / control / parameter as the next guess,
+// Core/Nlp2OPConverter.cpp:160-193; LpGuessChecker splines it onto the new nodes, Core/LpGuessChecker.cpp:208-294), for all
+// instances of an engine at once and without leaving the device.  Per instance, phase and column, in this order:
+//   1. time[k] = (tf - t0) * (tau_k + 1) / 2 + t0 at the N LGR points and at tau = 1            (rpm_post_kernel)
+//   2. controls only: the value at tau = 1, post_spline_end through the N points                (rpm_post_spline_kernel)
+//   3. knots tau_g[k] = 2 * (time[k] - time[0]) / (time[N] - time[0]) - 1                       (rpm_setup.cpp, starting point)
+//   4. the natural cubic spline of spline_eval (rpm_setup.cpp) through the N + 1 knots, evaluated at the target phase's
+//      points, states also at 1.0
+//   5. t0 = time[0], tf = time[N]; static parameters copied.
+// Everything but the cubes of step 4 repeats the one-instance path (rpm_nlp2op_control, a new rpm_create carrying the guess,
+// rpm_get_starting_point) operation by operation; the cubes are A * A * A here and glibc's pow(A, 3) there.
+#include <mutex>
+
+#include "rpm_device_internal.hpp"
+
+namespace rpm {
+
+// One workgroup's share: columns [col0, col0 + ncols) of a phase (states first, then controls) for a tile of instances.
+struct CarryGroup {
+  int phase, col0, ncols;
+  int first;   // the phase's first group also writes t0, tf and the static parameters
+};
+
+// Dynamic LDS of rpm_carry_kernel, offsets in doubles.  Rows are Mp = (N + 1) | 1 doubles apart: the lanes that walk different
+// rows in step then sit on different banks (an odd number of doubles is 2 * odd dwords; 32 lanes x 2 dwords cover the 64 banks).
+struct CarryLds {
+  int Mp;
+  int pts;     // [Mp]               the source phase's LGR points
+  int tau;     // [TB][Mp]           knots tau_g of every instance
+  int mu;      // [TB][Mp]           mu of the forward recurrence: depends on the knots only
+  int y;       // [TB * ncols][Mp]   the columns, row = instance * ncols + column
+  int c;       // [TB * ncols][Mp]   z of the forward recurrence, overwritten by the second derivatives c
+  int total;
+  __host__ __device__ constexpr CarryLds(int M, int TB, int ncols)
+      : Mp(M | 1), pts(0), tau(Mp), mu(tau + TB * Mp), y(mu + TB * Mp), c(y + TB * ncols * Mp), total(c + TB * ncols * Mp) {}
+};
+static_assert(CarryLds(65, 8, 16).Mp == 65 && CarryLds(64, 1, 1).Mp == 65 && CarryLds(65, 8, 16).total == 65 * (1 + 16 + 2 * 128),
+              "CarryLds: an array overlaps its neighbour or the total changed");
+
+// spline_eval's tail (rpm_setup.cpp): binary search for the knot interval, then A, B, Cc, Dd as written there.  The search
+// halves kr - kl whatever the comparisons say, and its trip count is bounded besides: NaN knots cannot spin it.
+__device__ __forceinline__ double carry_eval(double x, const double* xd, const double* yd, const double* c, int n) {
+  int kl = 1, kr = n;
+  for (int it = 0; it < 32 && kr - kl > 1; ++it) {
+    const int k = (kr + kl) / 2;
+    if (xd[k - 1] > x) kr = k; else kl = k;
+  }
+  const double h = xd[kr - 1] - xd[kl - 1];
+  const double A = (xd[kr - 1] - x) / h, B = (x - xd[kl - 1]) / h;
+  const double Cc = (A * A * A - A) * (h * h) / 6.0, Dd = (B * B * B - B) * (h * h) / 6.0;
+  return A * yd[kl - 1] + B * yd[kr - 1] + Cc * c[kl - 1] + Dd * c[kr - 1];
+}
+
+// Workgroup (group of columns of a phase, tile of TB instances), 256 threads.  x is instance-major with every column
+// contiguous in k, so the columns are staged with k-fastest loads; one lane per (instance, column) runs the recurrences out
+// of LDS; all lanes evaluate, the outputs of one (instance, column) on consecutive lanes, so the stores are contiguous runs.
+__global__ void __launch_bounds__(256)
+rpm_carry_kernel(const PhaseDev* __restrict__ fph, const double* __restrict__ fpts, int n_from, const PhaseDev* __restrict__ tph,
+                 const double* __restrict__ tpts, int n_to, const CarryGroup* __restrict__ groups, int B, int TB,
+                 const double* __restrict__ x_from, double* __restrict__ x_to) {
+  extern __shared__ __align__(16) double carry_sm[];
+  const CarryGroup v = groups[blockIdx.x];
+  const PhaseDev pf = fph[v.phase], pt = tph[v.phase];
+  const int N = pf.N, M = N + 1, Nt = pt.N, nx = pf.nx, ncols = v.ncols;
+  const CarryLds L(M, TB, ncols);
+  const int Mp = L.Mp;
+  double* pts = carry_sm + L.pts;
+  double* tau = carry_sm + L.tau;
+  double* mu = carry_sm + L.mu;
+  double* ys = carry_sm + L.y;
+  double* cs = carry_sm + L.c;
+  const int b0 = blockIdx.y * TB;
+  const int nb = B - b0 < TB ? B - b0 : TB;
+  const int tid = threadIdx.x, nt = blockDim.x;
+  const double* fp = fpts + pf.node0;
+
+  // ---- stage: points, every instance's knots, the columns ------------------------------------------------------
+  for (int k = tid; k < N; k += nt) pts[k] = fp[k];
+  for (int idx = tid; idx < nb * M; idx += nt) {
+    const int k = idx % M, bi = idx / M;
+    const double* xb = x_from + size_t(b0 + bi) * n_from;
+    const double t0 = xb[pf.x_t0], tf = xb[pf.x_t0 + 1];
+    const double time_k = (tf - t0) * ((k < N ? fp[k] : 1.0) + 1) / 2 + t0;
+    const double time_0 = (tf - t0) * (fp[0] + 1) / 2 + t0, time_N = (tf - t0) * (1.0 + 1) / 2 + t0;
+    tau[bi * Mp + k] = 2 * (time_k - time_0) / (time_N - time_0) - 1;
+  }
+  for (int idx = tid; idx < nb * ncols * M; idx += nt) {
+    const int k = idx % M, cl = (idx / M) % ncols, bi = idx / (M * ncols);
+    const double* xb = x_from + size_t(b0 + bi) * n_from;
+    const int col = v.col0 + cl;
+    double val = 0.0;   // a control's entry at tau = 1 is computed below
+    if (col < nx) val = xb[pf.x_state0 + col * M + k];
+    else if (k < N) val = xb[pf.x_control0 + (col - nx) * N + k];
+    ys[(bi * ncols + cl) * Mp + k] = val;
+  }
+  __syncthreads();
+
+  // ---- wave 0: mu, once per instance.  The other waves: the controls' values at tau = 1 -------------------------------
+  if (tid < 64) {
+    for (int bi = tid; bi < nb; bi += 64) {
+      const double* xd = tau + bi * Mp;
+      double* m = mu + bi * Mp;
+      m[0] = 0.0;
+      for (int i = 1; i < M - 1; ++i) {
+        const double him1 = xd[i] - xd[i - 1], hi = xd[i + 1] - xd[i];
+        const double li = 2 * (xd[i + 1] - xd[i - 1]) - him1 * m[i - 1];
+        m[i] = hi / li;
+      }
+      m[M - 1] = 0.0;
+    }
+  } else {
+    for (int r = tid - 64; r < nb * ncols; r += nt - 64) {
+      if (v.col0 + r % ncols < nx) continue;
+      double* y = ys + r * Mp;
+      y[N] = post_spline_end(N, pts, [&](int k) -> double { return y[k]; });
+    }
+  }
+  __syncthreads();
+
+  // ---- one lane per (instance, column): forward recurrence, back substitution, interior c doubled ------------------
+  for (int r = tid; r < nb * ncols; r += nt) {
+    const double* xd = tau + (r / ncols) * Mp;
+    const double* m = mu + (r / ncols) * Mp;
+    const double* y = ys + r * Mp;
+    double* c = cs + r * Mp;
+    double z = 0.0;
+    c[0] = 0.0;
+    for (int i = 1; i < M - 1; ++i) {
+      const double him1 = xd[i] - xd[i - 1], hi = xd[i + 1] - xd[i];
+      const double alpha = 3.0 / hi * (y[i + 1] - y[i]) - 3.0 / him1 * (y[i] - y[i - 1]);
+      const double li = 2 * (xd[i + 1] - xd[i - 1]) - him1 * m[i - 1];
+      z = (alpha - him1 * z) / li;
+      c[i] = z;
+    }
+    c[M - 1] = 0.0;
+    double next = 0.0;   // c[j + 1] before its doubling
+    for (int j = M - 2; j >= 0; --j) {
+      next = c[j] - m[j] * next;
+      c[j] = j >= 1 ? 2 * next : next;
+    }
+  }
+  __syncthreads();
+
+  // ---- evaluate and store: states at the target's points and at 1.0, controls at the points ---------------------
+  const double* tp = tpts + pt.node0;
+  const int ns = nx - v.col0 < 0 ? 0 : (nx - v.col0 < ncols ? nx - v.col0 : ncols);   // state columns of this group
+  const int nc = ncols - ns, Q = Nt + 1;
+  for (int idx = tid; idx < nb * ns * Q; idx += nt) {
+    const int q = idx % Q, cl = (idx / Q) % ns, bi = idx / (Q * ns);
+    const int r = bi * ncols + cl;
+    x_to[size_t(b0 + bi) * n_to + pt.x_state0 + (v.col0 + cl) * Q + q] =
+        carry_eval(q < Nt ? tp[q] : 1.0, tau + bi * Mp, ys + r * Mp, cs + r * Mp, M);
+  }
+  for (int idx = tid; idx < nb * nc * Nt; idx += nt) {
+    const int q = idx % Nt, cl = ns + (idx / Nt) % nc, bi = idx / (Nt * nc);
+    const int r = bi * ncols + cl;
+    x_to[size_t(b0 + bi) * n_to + pt.x_control0 + (v.col0 + cl - nx) * Nt + q] =
+        carry_eval(tp[q], tau + bi * Mp, ys + r * Mp, cs + r * Mp, M);
+  }
+  if (v.first)
+    for (int idx = tid; idx < nb * (2 + pf.nq); idx += nt) {
+      const int j = idx % (2 + pf.nq), bi = idx / (2 + pf.nq);
+      const double* xb = x_from + size_t(b0 + bi) * n_from;
+      const double t0 = xb[pf.x_t0], tf = xb[pf.x_t0 + 1];
+      double val;
+      if (j == 0) val = (tf - t0) * (fp[0] + 1) / 2 + t0;          // time[0]
+      else if (j == 1) val = (tf - t0) * (1.0 + 1) / 2 + t0;       // time[N]
+      else val = xb[pf.x_t0 + j];
+      x_to[size_t(b0 + bi) * n_to + pt.x_t0 + j] = val;
+    }
+}
+
+// nonfinite[b] = 1 when any carried value of instance b is NaN or Inf: one workgroup per instance over its finished block
+// (queued behind rpm_carry_kernel; a block-wide OR, no atomics)
+__global__ void __launch_bounds__(256) rpm_carry_flag_kernel(int n_to, const double* __restrict__ x_to, int* __restrict__ nonfinite) {
+  const double* xb = x_to + size_t(blockIdx.x) * n_to;
+  bool bad = false;
+  for (int i = threadIdx.x; i < n_to; i += blockDim.x) bad |= !(fabs(xb[i]) <= 1.7976931348623157e308);
+  const int any = __syncthreads_or(bad ? 1 : 0);
+  if (threadIdx.x == 0) nonfinite[blockIdx.x] = any ? 1 : 0;
+}
+
+namespace {
+
+constexpr size_t kCarryLdsLimit = 160 * 1024;   // LDS of one CU of the MI355X
+
+struct DeviceRestore {   // the calling thread's current device, put back on every exit path
+  int prev = -1;
+  DeviceRestore() { if (hipGetDevice(&prev) != hipSuccess) prev = -1; }
+  ~DeviceRestore() { if (prev >= 0) (void)hipSetDevice(prev); }
+};
+
+struct CarryPlan {
+  long long to_serial = 0;
+  int tile_opt = 0, lds_opt = 0;   // the options the plan was made under
+  int TB = 1, n_groups = 0;
+  size_t lds = 0;
+  CarryGroup* d_groups = nullptr;
+};
+struct CarryState {
+  std::vector<CarryPlan> plans;
+  // host-pointer form: the device output block and a page-locked mirror of the verdicts
+  double* out = nullptr;
+  int *out_flag = nullptr, *h_flag = nullptr;
+  size_t out_cap = 0, flag_cap = 0;
+};
+
+size_t carry_budget(const Engine& from) {
+  return from.opt_carry_lds > 0 ? std::min(size_t(from.opt_carry_lds), kCarryLdsLimit) : kCarryLdsLimit;
+}
+
+// Host planner: instances per workgroup and the split of every phase's columns over workgroups.  Columns are independent,
+// so a phase whose columns do not fit one workgroup's LDS is dealt over several; the tile shrinks before one column is refused.
+bool carry_plan(const Engine& from, int* TB_out, std::vector<CarryGroup>* groups, size_t* lds_out) {
+  const size_t budget = carry_budget(from) / sizeof(double);
+  // automatic: 2 instances per workgroup (reasoned; tools/bench_sweep_carry.py measures every value)
+  int TB = from.opt_carry_tile > 0 ? from.opt_carry_tile : 2;
+  while (TB > 1 && TB / 2 >= from.n_instances) TB >>= 1;
+  for (;; TB >>= 1) {
+    bool fits = true;
+    for (const PhaseHost& p : from.ph) fits = fits && size_t(CarryLds(p.N + 1, TB, 1).total) <= budget;
+    if (fits) break;
+    if (TB == 1) return false;
+  }
+  size_t lds = 0;
+  if (groups) groups->clear();
+  for (size_t ip = 0; ip < from.ph.size(); ++ip) {
+    const PhaseHost& p = from.ph[ip];
+    const int cols = p.nx + p.nu;
+    int most = 1;   // the most columns that fit next to the per-instance rows
+    while (most < cols && size_t(CarryLds(p.N + 1, TB, most + 1).total) <= budget) ++most;
+    const int n_groups = cols > 0 ? (cols + most - 1) / most : 1;
+    const int per = cols > 0 ? (cols + n_groups - 1) / n_groups : 0;
+    for (int g = 0, col0 = 0; g < n_groups; ++g, col0 += per) {
+      const CarryGroup cg{int(ip), col0, std::min(per, cols - col0), g == 0 ? 1 : 0};
+      lds = std::max(lds, size_t(CarryLds(p.N + 1, TB, cg.ncols).total) * sizeof(double));
+      if (groups) groups->push_back(cg);
+    }
+  }
+  *TB_out = TB;
+  *lds_out = lds;
+  return true;
+}
+
+// hipFuncAttributeMaxDynamicSharedMemorySize is per device and only ever raised here
+std::mutex g_carry_attr_mutex;
+size_t g_carry_attr[64] = {};
+
+int carry_devices(Engine& from, Engine& to) {
+  int id = from.dev ? from.dev->device_id : (to.dev ? to.dev->device_id : 0);
+  if (!from.dev) {
+    const int rc = device_init(from, id);
+    if (rc) return rc;
+  }
+  if (!to.dev) {
+    const int rc = device_init(to, id);
+    if (rc) {
+      from.err = to.err;
+      return rc;
+    }
+  }
+  return RPM_OK;
+}
+
+CarryState& carry_state(Device& d) {
+  if (!d.carry) d.carry = new CarryState();
+  return *static_cast<CarryState*>(d.carry);
+}
+
+int carry_launch(Engine& from, Engine& to, const double* d_x_from, double* d_x_to, int* d_nonfinite, hipStream_t st) {
+  Device& d = *from.dev;
+  HIP_TRY(from, hipSetDevice(d.device_id));
+  CarryState& cs = carry_state(d);
+  const CarryPlan* plan = nullptr;
+  for (const CarryPlan& p : cs.plans)
+    if (p.to_serial == to.serial && p.tile_opt == from.opt_carry_tile && p.lds_opt == from.opt_carry_lds) plan = &p;
+  if (!plan) {   // first call on this pair of engines: the only allocation and the only blocking copy
+    CarryPlan p;
+    std::vector<CarryGroup> groups;
+    if (!carry_plan(from, &p.TB, &groups, &p.lds)) {
+      from.err = "carry_solution_batch: a column does not fit one workgroup's LDS";
+      return RPM_E_UNSUPPORTED;
+    }
+    p.to_serial = to.serial;
+    p.tile_opt = from.opt_carry_tile;
+    p.lds_opt = from.opt_carry_lds;
+    p.n_groups = int(groups.size());
+    HIP_TRY(from, upload(&p.d_groups, groups));
+    if (p.lds > 64 * 1024 && d.device_id >= 0 && d.device_id < 64) {
+      std::lock_guard<std::mutex> lock(g_carry_attr_mutex);
+      if (g_carry_attr[d.device_id] < p.lds) {
+        HIP_TRY(from, hipFuncSetAttribute(reinterpret_cast<const void*>(rpm_carry_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                          int(kCarryLdsLimit)));
+        g_carry_attr[d.device_id] = kCarryLdsLimit;
+      }
+    }
+    cs.plans.push_back(p);
+    plan = &cs.plans.back();
+  }
+  const int B = from.n_instances;
+  hipLaunchKernelGGL(rpm_carry_kernel, dim3(unsigned(plan->n_groups), unsigned((B + plan->TB - 1) / plan->TB)), dim3(256), plan->lds, st,
+                     d.d_phases, d.d_points, from.n, to.dev->d_phases, to.dev->d_points, to.n, plan->d_groups, B, plan->TB, d_x_from,
+                     d_x_to);
+  if (d_nonfinite) hipLaunchKernelGGL(rpm_carry_flag_kernel, dim3(unsigned(B)), dim3(256), 0, st, to.n, d_x_to, d_nonfinite);
+  const hipError_t s = hipGetLastError();
+  if (s != hipSuccess) {
+    from.err = std::string("carry_solution_batch launch: ") + hipGetErrorString(s);
+    return RPM_E_DEVICE;
+  }
+  return RPM_OK;
+}
+
+int carry_fail(Engine& e, int code, const std::string& msg) {
+  e.err = msg;
+  return code;
+}
+
+}  // namespace
+
+void carry_destroy(Device* d) {
+  CarryState* cs = static_cast<CarryState*>(d->carry);
+  if (!cs) return;
+  for (CarryPlan& p : cs->plans)
+    if (p.d_groups) (void)hipFree(p.d_groups);
+  if (cs->out) (void)hipFree(cs->out);
+  if (cs->out_flag) (void)hipFree(cs->out_flag);
+  if (cs->h_flag) (void)hipHostFree(cs->h_flag);
+  delete cs;
+  d->carry = nullptr;
+}
+
+int carry_group_count(const Engine& from) {
+  int TB = 0;
+  size_t lds = 0;
+  std::vector<CarryGroup> groups;
+  return carry_plan(from, &TB, &groups, &lds) ? int(groups.size()) : 0;
+}
+
+// every argument error, decided on the host before a device is touched (x_from / x_to: both host or both device pointers)
+int carry_check(Engine& from, const Engine& to, const void* x_from, const void* x_to) {
+  const std::string who = "carry_solution_batch: ";
+  for (int i = 0; i < std::min(from.P, to.P); ++i) {   // the sizes first: they say more than "another problem"
+    const PhaseHost &a = from.ph[size_t(i)], &b = to.ph[size_t(i)];
+    const std::string tag = " differs in phase " + std::to_string(i + 1);
+    if (a.nx != b.nx) return carry_fail(from, RPM_E_INVALID, who + "nx" + tag);
+    if (a.nu != b.nu) return carry_fail(from, RPM_E_INVALID, who + "nu" + tag);
+    if (a.nq != b.nq) return carry_fail(from, RPM_E_INVALID, who + "nq" + tag);
+  }
+  if (from.P != to.P) return carry_fail(from, RPM_E_INVALID, who + "the engines have different phase counts");
+  if (from.problem_id != to.problem_id) return carry_fail(from, RPM_E_INVALID, who + "the engines hold different problems");
+  if (from.n_instances != to.n_instances)
+    return carry_fail(from, RPM_E_INVALID, who + "n_instances differs (" + std::to_string(from.n_instances) + " and " +
+                                               std::to_string(to.n_instances) + ")");
+  if (from.dev && to.dev && from.dev->device_id != to.dev->device_id)
+    return carry_fail(from, RPM_E_INVALID, who + "the engines are bound to different devices");
+  const char* a = static_cast<const char*>(x_from);
+  const char* b = static_cast<const char*>(x_to);
+  const size_t na = size_t(from.n_instances) * from.n * sizeof(double), nb = size_t(to.n_instances) * to.n * sizeof(double);
+  if (a < b + nb && b < a + na) return carry_fail(from, RPM_E_INVALID, who + "x_from and x_to overlap");
+  auto sharded = [](const Engine& e) { return e.shard_mode == RPM_SHARD_INTERVALS && e.shard_world > 1; };
+  if (sharded(from) || sharded(to)) return carry_fail(from, RPM_E_UNSUPPORTED, who + "not with interval sharding");
+  int TB = 0;
+  size_t lds = 0;
+  if (!carry_plan(from, &TB, nullptr, &lds)) {
+    int most = 0;
+    for (const PhaseHost& p : from.ph) most = std::max(most, p.N + 1);
+    return carry_fail(from, RPM_E_UNSUPPORTED, who + "a column of " + std::to_string(most) + " knots does not fit one workgroup's LDS");
+  }
+  return RPM_OK;
+}
+
+// device-resident: one launch (two with the verdicts) on `stream`; after the first call on a pair of engines nothing else
+int dev_carry_batch(Engine& from, Engine& to, const double* d_x_from, double* d_x_to, int* d_nonfinite, void* stream) {
+  int rc = carry_check(from, to, d_x_from, d_x_to);
+  if (rc) return rc;
+  DeviceRestore restore;
+  rc = carry_devices(from, to);
+  if (rc) return rc;
+  return carry_launch(from, to, d_x_from, d_x_to, d_nonfinite, static_cast<hipStream_t>(stream));
+}
+
+// the same through host arrays: x_from up through the staging slot, the carried block and the verdicts back; blocking
+int host_carry_batch(Engine& from, Engine& to, const double* x_from, double* x_to, int* nonfinite) {
+  int rc = carry_check(from, to, x_from, x_to);
+  if (rc) return rc;
+  DeviceRestore restore;
+  rc = carry_devices(from, to);
+  if (rc) return rc;
+  Device& d = *from.dev;
+  HIP_TRY(from, hipSetDevice(d.device_id));
+  CarryState& cs = carry_state(d);
+  const size_t B = size_t(from.n_instances), count = B * to.n;
+  if (cs.out_cap < count) {
+    HIP_TRY(from, hipStreamSynchronize(d.stream));
+    if (cs.out) HIP_TRY(from, hipFree(cs.out));
+    cs.out = nullptr;
+    cs.out_cap = 0;
+    HIP_TRY(from, hipMalloc(reinterpret_cast<void**>(&cs.out), count * sizeof(double)));
+    cs.out_cap = count;
+  }
+  if (cs.flag_cap < B) {
+    HIP_TRY(from, hipMalloc(reinterpret_cast<void**>(&cs.out_flag), B * sizeof(int)));
+    HIP_TRY(from, hipHostMalloc(reinterpret_cast<void**>(&cs.h_flag), B * sizeof(int), hipHostMallocDefault));
+    cs.flag_cap = B;
+  }
+  host_new_x(from);   // d_x is about to hold other values than the callbacks' last x
+  rc = dev_upload(from, d.d_x, x_from, B * from.n, STAGE_X);
+  if (rc) return rc;
+  rc = carry_launch(from, to, d.d_x, cs.out, nonfinite ? cs.out_flag : nullptr, d.stream);
+  if (rc) return rc;
+  if (nonfinite) HIP_TRY(from, hipMemcpyAsync(cs.h_flag, cs.out_flag, B * sizeof(int), hipMemcpyDeviceToHost, d.stream));
+  rc = dev_download(from, x_to, cs.out, count, STAGE_G);
+  if (rc) return rc;
+  HIP_TRY(from, hipStreamSynchronize(d.stream));
+  dev_stage_synced(from);
+  if (nonfinite) std::memcpy(nonfinite, cs.h_flag, B * sizeof(int));
+  return RPM_OK;
+}
+
+}  // namespace rpm

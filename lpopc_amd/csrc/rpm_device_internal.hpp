@@ -123,6 +123,7 @@ struct Device {
   void* host_path = nullptr;    // state of the host-pointer delivery (rpm_host_path.hip)
   void* exchange = nullptr;     // pack / unpack tables of the interval-sharded exchange (rpm_peer.hip)
   void* mesh_batch = nullptr;   // tables and workspace of the batched mesh-error estimate (rpm_post_kernels.hip), built on first use
+  void* carry = nullptr;        // launch plans of the batched carry, one per target engine (rpm_carry_kernels.hip), built on first use
   struct SegTable { void* ptr = nullptr; int count = 0; int stride = -1; };
   SegTable segtab[2][2];        // [g|values][pack|unpack] run tables of the interval sharding
 };
@@ -144,6 +145,26 @@ __device__ __forceinline__ void chk_report(int* chk, bool bad_g, bool bad_j) {
   if (chk == nullptr) return;
   if (bad_g) atomicOr_system(chk, 1);
   if (bad_j) atomicOr_system(chk + 1, 1);
+}
+
+// Value at tau = +1 of the natural cubic spline through (tau_k, Y(k)), k < N (LpGuessChecker::spline_interpolation,
+// Core/LpGuessChecker.cpp:208-270, specialised to the last interval: only the forward recurrence's final z is needed because
+// c[n-1] = 0).  One definition for rpm_post_spline_kernel and the batched carry (rpm_carry_kernels.hip): same operations, same bits.
+template <class YF>
+__device__ __forceinline__ double post_spline_end(int N, const double* tau, YF Y) {
+  double mu = 0.0, z = 0.0;
+  for (int i = 1; i < N - 1; ++i) {
+    const double him1 = tau[i] - tau[i - 1], hi = tau[i + 1] - tau[i];
+    const double alpha = 3.0 / hi * (Y(i + 1) - Y(i)) - 3.0 / him1 * (Y(i) - Y(i - 1));
+    const double li = 2 * (tau[i + 1] - tau[i - 1]) - him1 * mu;
+    mu = hi / li;
+    z = (alpha - him1 * z) / li;
+  }
+  const double d2l = (N - 2 >= 1) ? 2 * z : 0.0;   // c[n-2] = z[n-2] - mu[n-2]*c[n-1], doubled for interior knots
+  const double h = tau[N - 1] - tau[N - 2];
+  const double A = (tau[N - 1] - 1.0) / h, B = (1.0 - tau[N - 2]) / h;
+  const double Cc = (pow(A, 3.0) - A) * (h * h) / 6.0, Dd = (pow(B, 3.0) - B) * (h * h) / 6.0;
+  return A * Y(N - 2) + B * Y(N - 1) + Cc * d2l + Dd * 0.0;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -190,6 +211,7 @@ void dev_stage_synced(Engine& e);    // the engine's stream was synchronised: ev
 std::string dev_pin_last_error();
 void exchange_destroy(Device* d);    // rpm_peer.hip
 void mesh_batch_destroy(Device* d);  // rpm_post_kernels.hip
+void carry_destroy(Device* d);       // rpm_carry_kernels.hip
 
 // rpm_tile_kernels.hip: occupancy, LDS size and eligibility of the pipelined kernel for this engine (device_init)
 void tile_pipeline_setup(Engine& e, Device* d, const ProblemDims& pd, int device_id);

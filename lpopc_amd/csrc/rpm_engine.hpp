@@ -182,6 +182,9 @@ struct Engine {
   int opt_ipm_local_border = 1;  // rpm_ipm_create: an interval block carries only the rows of the global border that its interior has entries with (0: all of them)
   int opt_ipm_nested = -1;       // rpm_ipm_create: nested dissection of the KKT matrix over the mesh intervals (rpm_ipm.hpp): -1 when the structure allows, 0 never, 1 must
   int opt_mesh_err_tile = 0;     // batched mesh-error estimate: instances per workgroup (0: as many of 8, 4, 2, 1 as the LDS tile holds)
+  int opt_carry_tile = 0;        // batched carry: instances per workgroup (0: automatic)
+  int opt_carry_lds = 0;         // batched carry: LDS bytes one workgroup may use (0: what the device offers; smaller values are for tests of the column split)
+  long long serial = 0;          // unique per rpm_create in this process: what a cached launch plan names its target engine by
   int ipm_attached = 0;          // rpm_ipm solvers built on this engine: they size their buffers from stride_g/values
   // solution kept by finalize_solution (LpopcIpopt.cpp:237-243)
   std::vector<double> sol_x, sol_lambda;
@@ -240,6 +243,13 @@ int dev_solution_error_batch(Engine& e, const double* d_x, const int* d_mask, do
                              double* d_rel_err, int* d_nonfinite, void* stream);
 int host_solution_error_batch(Engine& e, const double* x, const int* mask, double* interval_error, double* rel_err_max,
                               double* rel_err, int* nonfinite);
+
+// rpm_carry_kernels.hip: the solutions of all instances of `from` splined onto the mesh of `to` (the next mesh's starting
+// points).  carry_check decides every argument error on the host; the two drivers call it before they touch a device.
+int carry_check(Engine& from, const Engine& to, const void* x_from, const void* x_to);
+int carry_group_count(const Engine& from);   // workgroups per tile of instances under the engine's options; 0: a column does not fit
+int dev_carry_batch(Engine& from, Engine& to, const double* d_x_from, double* d_x_to, int* d_nonfinite, void* stream);
+int host_carry_batch(Engine& from, Engine& to, const double* x_from, double* x_to, int* nonfinite);
 
 // rpm_shard.cpp: rank's contiguous runs of g (which=0) or of the Jacobian values (which=1)
 std::vector<rpm_segment> shard_segments(const Engine& e, int which, int rank, int* packed_len);

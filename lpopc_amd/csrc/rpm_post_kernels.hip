@@ -117,19 +117,7 @@ __global__ void rpm_post_spline_kernel(int N, const double* __restrict__ tau, co
   const double* y = cols + size_t(col) * N;
   // optional scaling y_k -> scale_num * (1/w_k) * y_k / scale_den  (path multipliers, Nlp2OPConverter.cpp:92)
   auto Y = [&](int k) -> double { return w ? scale_num * ((1 / w[k]) * y[k]) / scale_den : y[k]; };
-  double mu = 0.0, z = 0.0;
-  for (int i = 1; i < N - 1; ++i) {
-    const double him1 = tau[i] - tau[i - 1], hi = tau[i + 1] - tau[i];
-    const double alpha = 3.0 / hi * (Y(i + 1) - Y(i)) - 3.0 / him1 * (Y(i) - Y(i - 1));
-    const double li = 2 * (tau[i + 1] - tau[i - 1]) - him1 * mu;
-    mu = hi / li;
-    z = (alpha - him1 * z) / li;
-  }
-  const double d2l = (N - 2 >= 1) ? 2 * z : 0.0;   // c[n-2] = z[n-2] - mu[n-2]*c[n-1], doubled for interior knots
-  const double h = tau[N - 1] - tau[N - 2];
-  const double A = (tau[N - 1] - 1.0) / h, B = (1.0 - tau[N - 2]) / h;
-  const double Cc = (pow(A, 3.0) - A) * (h * h) / 6.0, Dd = (pow(B, 3.0) - B) * (h * h) / 6.0;
-  out[col] = A * Y(N - 2) + B * Y(N - 1) + Cc * d2l + Dd * 0.0;
+  out[col] = post_spline_end(N, tau, Y);
 }
 
 template <class Prob>

@@ -186,6 +186,40 @@ int rpm_sweep_solution_error(rpm_sweep* s, const double* x, const int* instance_
   return RPM_OK;
 }
 
+/* rpm_carry_solution_batch on every share, side by side: x_from B x from.n, x_to B x to.n, nonfinite B or NULL.  The two sweeps
+ * must deal their instances alike (same devices, same shares). */
+int rpm_sweep_carry_solution(rpm_sweep* from, rpm_sweep* to, const double* x_from, double* x_to, int* nonfinite) {
+  if (!from) return RPM_E_INVALID;
+  if (!to || !x_from || !x_to) {
+    from->err = !to ? "rpm_sweep_carry_solution: the target sweep is NULL" : "rpm_sweep_carry_solution: x_from or x_to is NULL";
+    return RPM_E_INVALID;
+  }
+  if (from->B != to->B || from->dev != to->dev || from->count != to->count) {
+    from->err = "rpm_sweep_carry_solution: the sweeps have different shares (devices or instance counts)";
+    return RPM_E_INVALID;
+  }
+  const size_t N = from->eng.size();
+  int prev = -1;
+  if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+  std::vector<int> rcs(N, RPM_OK);
+  auto run = [&](size_t r) {
+    (void)hipSetDevice(from->dev[r]);
+    const size_t i0 = size_t(from->first[r]);
+    rcs[r] = rpm_carry_solution_batch(from->eng[r], to->eng[r], x_from + i0 * from->n, x_to + i0 * to->n, nonfinite ? nonfinite + i0 : nullptr);
+  };
+  std::vector<std::thread> th;
+  for (size_t r = 1; r < N; ++r) th.emplace_back(run, r);
+  run(0);
+  for (std::thread& t : th) t.join();
+  if (prev >= 0) (void)hipSetDevice(prev);
+  for (size_t r = 0; r < N; ++r)
+    if (rcs[r]) {
+      from->err = "share " + std::to_string(r) + " (device " + std::to_string(from->dev[r]) + "): " + rpm_last_error(from->eng[r]);
+      return rcs[r];
+    }
+  return RPM_OK;
+}
+
 /* totals over the shares of the last solve: batched iterations (the largest share's count), factorisations and trial points (sums) */
 int rpm_sweep_get_stats(rpm_sweep* s, int* iterations, int* factorizations, int* trial_points) {
   if (!s) return RPM_E_INVALID;

@@ -30,6 +30,7 @@ ABI_SYMBOLS = [
     "rpm_shard_segments", "rpm_shard_pack_dev", "rpm_shard_unpack_dev", "rpm_shard_slot_len", "rpm_shard_pack_all_dev", "rpm_shard_unpack_all_dev", "rpm_nlp2op_control", "rpm_final_result_save",
     "rpm_solution_error", "rpm_ph_refine_mesh", "rpm_ph_refine_from_error",
     "rpm_solution_error_batch_sizes", "rpm_solution_error_batch_dev", "rpm_solution_error_batch", "rpm_sweep_solution_error",
+    "rpm_carry_solution_batch_dev", "rpm_carry_solution_batch", "rpm_sweep_carry_solution",
     "rpm_hpliu_create", "rpm_hpliu_destroy", "rpm_hpliu_last_error", "rpm_hpliu_refine",
     "rpm_ipm_create", "rpm_ipm_destroy", "rpm_ipm_last_error", "rpm_ipm_set_option", "rpm_ipm_set_bounds", "rpm_ipm_set_all_bounds", "rpm_ipm_get_info",
     "rpm_group_create", "rpm_group_destroy", "rpm_group_last_error", "rpm_group_size", "rpm_group_engine", "rpm_group_device_init",
@@ -111,6 +112,9 @@ def lib(path=None):
     L.rpm_solution_error_batch_dev.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
     L.rpm_solution_error_batch.argtypes = [vp, dp, ip, dp, dp, dp, ip]
     L.rpm_sweep_solution_error.argtypes = [vp, dp, ip, dp, dp, dp, ip]
+    L.rpm_carry_solution_batch_dev.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.rpm_carry_solution_batch.argtypes = [vp, vp, dp, dp, ip]
+    L.rpm_sweep_carry_solution.argtypes = [vp, vp, dp, dp, ip]
     L.rpm_hpliu_create.argtypes = [C.c_int, C.c_double, C.c_int, C.c_double, C.POINTER(vp)]
     L.rpm_hpliu_destroy.argtypes = [vp]
     L.rpm_hpliu_destroy.restype = None
@@ -529,6 +533,23 @@ class NLPEngine:
         """The next mesh of the sweep: per phase ph_refine_from_error on rel_err_max (the worst included instance decides)."""
         est = self.solution_error_batch(x, mask)
         return [self.ph_refine_from_error(p, est["rel_err_max"][p], tol, nmin, nmax) for p in range(self.n_phases)]
+
+    # ---- the sweep's solutions carried onto another mesh (rpm_carry_solution_batch*) -----------------------------------
+    def carry_solution_batch(self, to, x):
+        """The solutions x (n_instances x n) of this engine splined onto the mesh of engine `to` (same problem, any mesh)
+        -> (x_to: n_instances x to.n, the next solve's starting points; nonfinite: n_instances ints)."""
+        if self._L is not to._L:
+            raise RpmError(RPM_E_INVALID, "carry_solution_batch: the engines must come from one native library")
+        x = self._x(x)
+        out = self._own("carry", self.n_instances * to.n)
+        flags = np.zeros(self.n_instances, dtype=np.int32)
+        self._check(self._L.rpm_carry_solution_batch(self._h, to._h, _dp(x), _dp(out), _ip(flags)))
+        return out.reshape(self.n_instances, to.n).copy(), flags
+
+    def carry_solution_batch_dev(self, to, d_x, d_x_to, d_nonfinite=None, stream=None):
+        """Device-resident form on torch CUDA tensors (float64; d_nonfinite int32).  Asynchronous on `stream`."""
+        self._check(self._L.rpm_carry_solution_batch_dev(self._h, to._h, self._ptr(d_x), self._ptr(d_x_to), self._ptr(d_nonfinite),
+                                                         self._stream(stream)))
 
     # ---- tables and sharding ---------------------------------------------------------------
     def phase_tables(self, phase):

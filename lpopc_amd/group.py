@@ -199,6 +199,17 @@ class SweepGroup:
         return _batch_estimate(self._L.rpm_sweep_solution_error, self._check, self._h, x, self.n_instances, sizes, shapes,
                                mask, full)
 
+    def carry_solution(self, to, x):
+        """rpm_sweep_carry_solution: the sweep's solutions x (B x n) splined onto the mesh of sweep `to` (same problem, same
+        shares) -> (x_to: B x to.n, nonfinite: B ints); equal to one engine holding all instances bit for bit."""
+        x = np.ascontiguousarray(x, dtype=np.float64).ravel()
+        if x.size != self.n * self.n_instances:
+            raise RpmError(RPM_E_INVALID, "x has %d entries, expected %d" % (x.size, self.n * self.n_instances))
+        out = np.zeros((self.n_instances, to.n))
+        flags = np.zeros(self.n_instances, dtype=np.int32)
+        self._check(self._L.rpm_sweep_carry_solution(self._h, to._h, _dp(x), _dp(out), _ip(flags)))
+        return out, flags
+
     def ph_refine(self, x, tol, nmin, nmax, mask=None):
         """The sweep's next mesh: per phase (no_more_refine, mesh, nodes, interval_error) from rel_err_max."""
         est = self.solution_error(x, mask)

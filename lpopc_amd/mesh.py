@@ -81,3 +81,19 @@ def install_guess(engine, optpro, x=None, lam=None):
         p0 = off + nx * M + nu * (M - 1) + 2                      # [X | U | t0 tf | p], Core/LpBoundsChecker.cpp:51-138
         ph.vparameterguess = [float(v) for v in xs[p0:p0 + nq]]   # vparameterguess, Nlp2OPConverter.cpp:185-193
         off = p0 + nq
+
+
+def install_sweep_mesh(optpro, refine_result):
+    """The meshes NLPEngine.ph_refine_sweep / SweepGroup.ph_refine returned (per phase (no_more_refine, mesh_points,
+    nodes_per_interval, interval_error)) written into the problem: MeshRefiner.RefineMesh's bookkeeping for a sweep, whose
+    instances share one transcription and so one next mesh.  Returns NoMoreRefine (every phase met the tolerance); the caller
+    builds the next engine or sweep from `optpro` and carries the solutions over (carry_solution_batch / carry_solution)."""
+    if len(refine_result) != optpro.GetPhaseNum():
+        raise LpopcException("install_sweep_mesh: %d phases refined, the problem has %d" % (len(refine_result), optpro.GetPhaseNum()))
+    no_more = True
+    for i, (done, mesh, nodes, _) in enumerate(refine_result):   # the reference rewrites the mesh even when nothing changed
+        ph = optpro.GetPhase(i)
+        ph.meshpoints = list(np.asarray(mesh, dtype=np.float64).tolist())
+        ph.nodesperinterval = [int(v) for v in nodes]
+        no_more = no_more and bool(done)
+    return no_more
