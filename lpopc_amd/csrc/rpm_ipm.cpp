@@ -174,7 +174,7 @@ struct NdClass {
   std::vector<int> ivl;     // Nt: interval of an interior unknown, -1 otherwise
   std::vector<int> loc;     // Nt: local index inside its interval (interior) or level-2 position (separator / border)
 };
-size_t factor_lds_of(int b, int nb) {   // = kkt_factor_lds_bytes (rpm_ipm_kernels.hip)
+size_t factor_lds_of(int b, int nb) {   // = kkt_factor_lds_bytes (rpm_kkt_factor.hip)
   const size_t W = IPM_PLAN_W;
   return (size_t(b + 24) * W + W * (W + 1) + W * W + W + 2 * size_t(nb) * W + size_t(nb) * (nb + 1) / 2) * sizeof(double);
 }

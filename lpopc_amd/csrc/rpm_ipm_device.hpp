@@ -1,5 +1,6 @@
-// rpm_ipm_device.hpp — what the two HIP translation units of row f-2 share: the parameter blocks of the interior-point
-// kernels (rpm_ipm_kernels.hip) and their launchers, used by the solver loop and the C ABI (rpm_ipm_solver.hip).
+// rpm_ipm_device.hpp — what the HIP translation units of row f-2 share: the parameter blocks of the interior-point
+// kernels (rpm_ipm_step_kernels.hip, rpm_kkt_factor.hip, rpm_kkt_solve.hip, rpm_ipm_lbfgs.hip) and their launchers, used by the
+// solver loop and the C ABI (rpm_ipm_solver.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -167,7 +168,7 @@ constexpr int IPM_VEC_BLOCKS = 64;   // most workgroups per instance of a vector
 constexpr int IPM_VEC_PART = 24;     // doubles of partial results per workgroup
 constexpr int IPM_MT = 8;   // most 16-row tiles per wave of the factorisation: block columns of up to 4 x 8 x 16 = 512 rows
 
-// launchers (rpm_ipm_kernels.hip); all asynchronous on `st`
+// launchers (rpm_ipm_step_kernels.hip; assemble: rpm_kkt_factor.hip, inertia: rpm_kkt_solve.hip); all asynchronous on `st`
 void ipm_launch_init(const IpmDev& D, const double* d_x0, hipStream_t st);
 void ipm_launch_init_slack(const IpmDev& D, hipStream_t st);
 void ipm_launch_pack_x(const IpmDev& D, hipStream_t st);
@@ -193,7 +194,7 @@ void lb_launch_columns_and_solve(const IpmDev& D, hipStream_t st);   // Z <- K0^
 void lb_launch_small(const IpmDev& D, hipStream_t st);                // C = M - E'Z, LU
 void lb_launch_correct(const IpmDev& D, int check_status, hipStream_t st);   // Woodbury correction of the solution in D.rhs
 void ipm_launch_jt_lambda_into(const IpmDev& D, double* out, hipStream_t st);   // grad f + A'lambda of the running instances into out (B x nv)
-// factorisation / substitution of every running instance; tiles_per_wave 4 or IPM_MT
+// factorisation (rpm_kkt_factor.hip) / substitution (rpm_kkt_solve.hip) of every running instance; tiles_per_wave 4 or IPM_MT
 size_t kkt_factor_lds_bytes(const IpmPlan& p);
 hipError_t kkt_factor_prepare(int tiles_per_wave, size_t lds_bytes);
 size_t kkt_factor_dense_lds_bytes(int block_rows);
@@ -206,5 +207,8 @@ void kkt_launch_factor(const IpmDev& D, int tiles_per_wave, size_t lds_bytes, hi
 // forward_done: D.rhs is the right-hand side the factorisation just ran over (kkt_level1_fused: its level-1 forward sweep is done)
 void kkt_launch_solve(const IpmDev& D, int check_status, hipStream_t st, int forward_done = 0);
 int kkt_level1_fused(const IpmDev& D);
+// kkt_vec_kernel over n_rhs right-hand sides of D.rhs: mode 0 v[dst[i]] = 0, mode 1 v[dst[i]] = v[src[i]], i < n (check_status as
+// above; 3: the running instances that refactor)
+void kkt_launch_vec(const IpmDev& D, unsigned n_rhs, const int* dst, const int* src, int n, int mode, int check_status, hipStream_t st);
 
 }  // namespace rpm

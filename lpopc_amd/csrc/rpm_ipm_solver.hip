@@ -1,4 +1,4 @@
-// rpm_ipm_solver.hip — row f-2, host side: the interior-point loop over the batched kernels of rpm_ipm_kernels.hip (per
+// rpm_ipm_solver.hip — row f-2, host side: the interior-point loop over the batched kernels of rpm_ipm_step_kernels.hip, rpm_kkt_factor.hip and rpm_kkt_solve.hip (per
 // iteration three counters come back from the device, nothing else) and the rpm_ipm_* entry points of the C ABI.
 #include <algorithm>
 #include <cmath>
@@ -180,7 +180,7 @@ int rpm_ipm_create(rpm_engine* eng, rpm_ipm** out) {
   {
     std::vector<int> long_cols;
     for (int i = 0; i < p.n; ++i)
-      if (p.jt_ptr[i + 1] - p.jt_ptr[i] > 256) long_cols.push_back(i);   // = IPM_LONG_COLUMN (rpm_ipm_kernels.hip)
+      if (p.jt_ptr[i + 1] - p.jt_ptr[i] > 256) long_cols.push_back(i);   // = IPM_LONG_COLUMN (rpm_ipm_step_kernels.hip)
     D.n_long = int(long_cols.size());
     A_(ipm_alloc_c(h, &D.long_cols, long_cols));
   }
