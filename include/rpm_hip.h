@@ -255,6 +255,30 @@ int rpm_carry_solution_batch_dev(rpm_engine* from, rpm_engine* to, const double*
                                  void* stream);
 int rpm_carry_solution_batch(rpm_engine* from, rpm_engine* to, const double* x_from, double* x_to, int* nonfinite);
 
+/* Solution extraction for a whole sweep: Nlp2OpConverter::Nlp2OpControl, Core/Nlp2OPConverter.cpp:13-196, for all phases and all
+ * n_instances instances of the engine at once, every instance with its own constants (rpm_set_instance_constants) and static
+ * parameters.  x: n_instances x n, lambda: n_instances x m, both packed and instance-major as rpm_ipm_solve[_dev] returns them.
+ * out: n_instances x EB, instance-major; one instance's block holds the phases one after the other, each phase in this order
+ * time (M), state (M nx), control (M nu), costate (M nx), pathmult (M nc), hamiltonian (M), mayer_cost (1), lagrange_cost (1),
+ * M = N + 1, every array column-major with M rows: exactly the arrays rpm_nlp2op_control returns, and per instance the same
+ * bits (the arithmetic is that call's, operation by operation and sum by sum in the same order).  The path multipliers read
+ * lambda without the phase offset, as the reference does (:88), from the base of the instance's own block.
+ * rpm_nlp2op_batch_layout (host only, no device needed): the offsets of a phase's eight fields inside an instance's block, in
+ * the order above, and EB; either output may be NULL.  A phase out of range: RPM_E_INVALID.
+ * nonfinite: n_instances ints or NULL, 1 when the instance's block holds a NaN or Inf; an instance with NaN / Inf in x or lambda,
+ * or with tf == t0 where a field divides by tf - t0, spoils its own block only.
+ * Argument errors are decided on the host before anything is queued: NULL x, lambda or out: RPM_E_INVALID; an interval-sharded
+ * engine, a spline column that does not fit one workgroup's LDS: RPM_E_UNSUPPORTED, with a message; no device: RPM_E_DEVICE.
+ * The _dev form takes device arrays and queues one launch (two with d_nonfinite; one more when the spline columns of a phase do
+ * not fit one workgroup's LDS and are dealt over several) on `stream` (a hipStream_t, NULL = the legacy default stream).  The
+ * first call on an engine may upload a small launch plan and allocate a workspace; every later call allocates nothing, copies
+ * nothing and never synchronises, so it can follow rpm_ipm_solve_dev on the caller's stream and be captured into a graph.  The
+ * host-pointer form stages its arrays like the other batched host-pointer calls and blocks.  The calling thread's current device
+ * is restored.  Option "extract_tile" (0 = automatic, 1, 2, 4, 8): instances per workgroup; every value gives the same bits. */
+int rpm_nlp2op_batch_layout(rpm_engine* e, int phase, long long field_offset[8], long long* block_doubles);
+int rpm_nlp2op_batch_dev(rpm_engine* e, const double* d_x, const double* d_lambda, double* d_out, int* d_nonfinite, void* stream);
+int rpm_nlp2op_batch(rpm_engine* e, const double* x, const double* lambda, double* out, int* nonfinite);
+
 /* hp-Liu refinement: LiuHpMeshRefineAlg::RefineMesh, Core/LpLiuHpMeshRefineAlg.cpp:12-260 (with Reducing_N :438-481,
  * Increasing_N :379-436, Dividing_mesh :321-377, CanWeIncreaseN :606-681; Merging_mesh's verdict is unused by the
  * reference, equal-N satisfied neighbours always merge).  The object keeps the reference's histories (meshes with their
@@ -591,6 +615,9 @@ int rpm_sweep_solution_error(rpm_sweep* s, const double* x, const int* instance_
  * sweeps must deal their instances alike (same device list, same n_instances), else RPM_E_INVALID; the message is
  * rpm_sweep_last_error(from). */
 int rpm_sweep_carry_solution(rpm_sweep* from, rpm_sweep* to, const double* x_from, double* x_to, int* nonfinite);
+/* rpm_nlp2op_batch on every share side by side (x: B x n, lambda: B x m, out: B x EB, nonfinite: B or NULL): what one engine
+ * holding all B instances returns, bit for bit. */
+int rpm_sweep_nlp2op(rpm_sweep* s, const double* x, const double* lambda, double* out, int* nonfinite);
 int rpm_sweep_get_stats(rpm_sweep* s, int* iterations, int* factorizations, int* trial_points);
 
 #ifdef __cplusplus

@@ -403,6 +403,37 @@ int rpm_carry_solution_batch(rpm_engine* from, rpm_engine* to, const double* x_f
   RPM_GUARD_END(e)
 }
 
+// ---- solution extraction for every phase and every instance of the engine (a sweep), rpm_extract_kernels.hip ---------
+int rpm_nlp2op_batch_layout(rpm_engine* h, int phase, long long field_offset[8], long long* block_doubles) {
+  if (!h) return RPM_E_INVALID;
+  Engine& e = h->e;
+  if (phase < 0 || phase >= e.P) return fail(e, RPM_E_INVALID, "nlp2op_batch_layout: the phase index is out of range");
+  rpm::nlp2op_batch_layout(e, phase, field_offset, block_doubles);
+  return RPM_OK;
+}
+
+int rpm_nlp2op_batch_dev(rpm_engine* h, const double* d_x, const double* d_lambda, double* d_out, int* d_nonfinite, void* stream) {
+  if (!h) return RPM_E_INVALID;
+  Engine& e = h->e;
+  RPM_GUARD_BEGIN
+  if (!d_x) return fail(e, RPM_E_INVALID, "nlp2op_batch_dev: d_x is NULL");
+  if (!d_lambda) return fail(e, RPM_E_INVALID, "nlp2op_batch_dev: d_lambda is NULL");
+  if (!d_out) return fail(e, RPM_E_INVALID, "nlp2op_batch_dev: d_out is NULL");
+  return rpm::dev_nlp2op_batch(e, d_x, d_lambda, d_out, d_nonfinite, stream);
+  RPM_GUARD_END(e)
+}
+
+int rpm_nlp2op_batch(rpm_engine* h, const double* x, const double* lambda, double* out, int* nonfinite) {
+  if (!h) return RPM_E_INVALID;
+  Engine& e = h->e;
+  RPM_GUARD_BEGIN
+  if (!x) return fail(e, RPM_E_INVALID, "nlp2op_batch: x is NULL");
+  if (!lambda) return fail(e, RPM_E_INVALID, "nlp2op_batch: lambda is NULL");
+  if (!out) return fail(e, RPM_E_INVALID, "nlp2op_batch: out is NULL");
+  return rpm::host_nlp2op_batch(e, x, lambda, out, nonfinite);
+  RPM_GUARD_END(e)
+}
+
 // ---- hp-Liu mesh refinement (second method) ------------------------------------
 struct rpm_hpliu {
   rpm::HpLiu h;
@@ -655,6 +686,14 @@ int rpm_set_option(rpm_engine* h, const char* key, int value) {
     if (value < 0) return fail(e, RPM_E_INVALID, "carry_lds_bytes must be 0 (what the device offers) or a byte count");
     e.opt_carry_lds = value;
     return RPM_OK;
+  } else if (k == "extract_tile") {
+    if (value != 0 && value != 1 && value != 2 && value != 4 && value != 8) return fail(e, RPM_E_INVALID, "extract_tile must be 0 (auto), 1, 2, 4 or 8");
+    e.opt_extract_tile = value;
+    return RPM_OK;
+  } else if (k == "extract_lds_bytes") {   // for tests of the column split: the LDS the staged arrays of one workgroup of the extraction may use
+    if (value < 0) return fail(e, RPM_E_INVALID, "extract_lds_bytes must be 0 (what the device offers) or a byte count");
+    e.opt_extract_lds = value;
+    return RPM_OK;
   } else if (k == "pipeline") {
     if (value < -1 || value > 1) return fail(e, RPM_E_INVALID, "pipeline must be -1 (auto), 0 or 1");
     e.opt_pipeline = value;
@@ -693,6 +732,9 @@ int rpm_get_option(rpm_engine* h, const char* key, int* value) {
   else if (k == "carry_tile") *value = e.opt_carry_tile;
   else if (k == "carry_lds_bytes") *value = e.opt_carry_lds;
   else if (k == "carry_groups") *value = rpm::carry_group_count(e);   // workgroups per tile of instances under the current options (0: a column does not fit)
+  else if (k == "extract_tile") *value = e.opt_extract_tile;
+  else if (k == "extract_lds_bytes") *value = e.opt_extract_lds;
+  else if (k == "extract_groups") *value = rpm::extract_group_count(e);   // workgroups per tile of instances of the spline launch (0: one fused launch, -1: a column does not fit)
   else if (k == "stage_roles") *value = e.opt_stage_roles;
   else if (k == "const_once") *value = e.opt_const_once;
   else if (k == "instance_align") *value = e.opt_instance_align;

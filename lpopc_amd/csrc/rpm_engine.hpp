@@ -184,6 +184,8 @@ struct Engine {
   int opt_mesh_err_tile = 0;     // batched mesh-error estimate: instances per workgroup (0: as many of 8, 4, 2, 1 as the LDS tile holds)
   int opt_carry_tile = 0;        // batched carry: instances per workgroup (0: automatic)
   int opt_carry_lds = 0;         // batched carry: LDS bytes one workgroup may use (0: what the device offers; smaller values are for tests of the column split)
+  int opt_extract_tile = 0;      // batched extraction: instances per workgroup (0: automatic)
+  int opt_extract_lds = 0;       // batched extraction: LDS bytes one workgroup's staged arrays may use (0: what the device offers; smaller values are for tests of the column split)
   long long serial = 0;          // unique per rpm_create in this process: what a cached launch plan names its target engine by
   int ipm_attached = 0;          // rpm_ipm solvers built on this engine: they size their buffers from stride_g/values
   // solution kept by finalize_solution (LpopcIpopt.cpp:237-243)
@@ -250,6 +252,14 @@ int carry_check(Engine& from, const Engine& to, const void* x_from, const void* 
 int carry_group_count(const Engine& from);   // workgroups per tile of instances under the engine's options; 0: a column does not fit
 int dev_carry_batch(Engine& from, Engine& to, const double* d_x_from, double* d_x_to, int* d_nonfinite, void* stream);
 int host_carry_batch(Engine& from, Engine& to, const double* x_from, double* x_to, int* nonfinite);
+
+// rpm_extract_kernels.hip: Nlp2OpControl for all phases and all instances of the engine.  nlp2op_batch_layout is host only;
+// extract_check decides every error of the engine's state on the host, the two drivers call it before they touch a device.
+void nlp2op_batch_layout(const Engine& e, int phase, long long field_offset[8], long long* block_doubles);
+int extract_check(Engine& e);
+int extract_group_count(const Engine& e);   // workgroups per tile of instances of the spline launch; 0: one fused launch, -1: a column does not fit
+int dev_nlp2op_batch(Engine& e, const double* d_x, const double* d_lambda, double* d_out, int* d_nonfinite, void* stream);
+int host_nlp2op_batch(Engine& e, const double* x, const double* lambda, double* out, int* nonfinite);
 
 // rpm_shard.cpp: rank's contiguous runs of g (which=0) or of the Jacobian values (which=1)
 std::vector<rpm_segment> shard_segments(const Engine& e, int which, int rank, int* packed_len);

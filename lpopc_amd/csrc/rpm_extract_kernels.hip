@@ -1,0 +1,509 @@
+// rpm_extract_kernels.hip — solution extraction for a whole sweep: Nlp2OpConverter::Nlp2OpControl (Core/Nlp2OPConverter.cpp:13-196)
+// for every phase and every instance of an engine in one launch (two with the NaN/Inf verdicts), nothing but the caller's arrays
+// crossing the call.  The specification is the one-instance route of rpm_post_kernels.hip (rpm_post_spline_kernel + rpm_post_kernel +
+// rpm_post_cost_kernel): per instance b the arithmetic below is that route's on x + b * n and lambda + b * m, operation by
+// operation and sum by sum in the same order (-ffp-contract=off: same order, same bits), with the user functions reading
+// instance b's constants and static parameters.
+//
+// One instance's block of EB doubles holds the phases one after the other, each phase time (M), state (M nx), control (M nu),
+// costate (M nx), pathmult (M nc), hamiltonian (M), mayer_cost (1), lagrange_cost (1), M = N + 1, every array column-major with
+// M rows: the arrays rpm_nlp2op_control returns.
+#include <mutex>
+
+#include "rpm_device_internal.hpp"
+
+namespace rpm {
+
+// One workgroup's share of rpm_extract_spline_kernel: spline columns [col0, col0 + ncols) of a phase, the nu controls first,
+// then the nc path-multiplier columns.
+struct ExtractGroup {
+  int phase, col0, ncols;
+};
+
+// Dynamic LDS of the two kernels, offsets in doubles.  Rows are Np = N | 1 doubles apart, so the lanes that walk different rows
+// in step sit on different banks (rpm_carry_kernels.hip, CarryLds).  rpm_extract_kernel: red_rows = TB, and when it also runs
+// the splines (fused) lag_rows = TB and ncols = nu + nc, else both 0; rpm_extract_spline_kernel: red_rows = lag_rows = 0.
+struct ExtractLds {
+  int Np;
+  int red;     // [red_rows][256]      partial sums of lagrange_cost
+  int lag;     // [lag_rows][Np]       the Lagrangian at the nodes of every instance
+  int pts;     // [Np]                 the phase's LGR points    (ncols > 0)
+  int w;       // [Np]                 its weights               (ncols > 0)
+  int cols;    // [TB * ncols][Np]     the spline columns, row = instance * ncols + column
+  int ends;    // [TB * ncols]         their values at tau = 1
+  int total;
+  __host__ __device__ constexpr ExtractLds(int N, int TB, int ncols, int red_rows, int lag_rows)
+      : Np(N | 1), red(0), lag(red_rows * 256), pts(lag + lag_rows * Np), w(pts + (ncols > 0 ? Np : 0)), cols(w + (ncols > 0 ? Np : 0)),
+        ends(cols + TB * ncols * Np), total(ends + TB * ncols) {}
+  __host__ __device__ constexpr int staged() const { return total - lag; }   // all but the partial sums: what the planner's LDS budget counts
+};
+static_assert(ExtractLds(64, 8, 4, 8, 8).Np == 65 && ExtractLds(64, 8, 4, 8, 8).total == 8 * 256 + 65 * (8 + 2 + 32) + 32 &&
+                  ExtractLds(64, 8, 0, 8, 0).total == 8 * 256 && ExtractLds(65, 2, 3, 0, 0).total == 65 * (2 + 6) + 6,
+              "ExtractLds: an array overlaps its neighbour or the total changed");
+
+__host__ __device__ inline long long extract_phase_doubles(int N, int nx, int nu, int nc) {
+  return (long long)(N + 1) * (2 + 2 * nx + nu + nc) + 2;
+}
+
+// The values at tau = 1 of spline columns [col0, col0 + ncols) of phase `ph` for instances b0 .. b0 + nb: the columns are staged
+// with k-fastest loads, then one lane per (instance, column) runs post_spline_end out of LDS.  ends[bi * ncols + cl].  A
+// path-multiplier column j reads lambda WITHOUT the phase offset, lam[N * nx + j * N + k] from the base of the instance's own
+// block (Nlp2OPConverter.cpp:88), and is scaled inside the accessor, 2 ((1 / w_k) lambda) / (tf - t0) (:92), as
+// rpm_post_spline_kernel does it.  The caller synchronises before it reads `ends`.
+__device__ __forceinline__ void extract_spline_ends(const KParams& K, const PhaseDev& ph, int col0, int ncols, int b0, int nb,
+                                                    const double* __restrict__ x, const double* __restrict__ lam, double* pts,
+                                                    double* w, double* cols, int Np, double* ends) {
+  const int N = ph.N, nu = ph.nu, tid = threadIdx.x, nt = blockDim.x;
+  for (int k = tid; k < N; k += nt) {
+    pts[k] = K.points[ph.node0 + k];
+    w[k] = K.weights[ph.node0 + k];
+  }
+  for (int idx = tid; idx < nb * ncols * N; idx += nt) {
+    const int k = idx % N, cl = (idx / N) % ncols, bi = idx / (N * ncols);
+    const int col = col0 + cl;
+    const double* src = col < nu ? x + size_t(b0 + bi) * K.n + ph.x_control0 + col * N
+                                 : lam + size_t(b0 + bi) * K.m + N * ph.nx + (col - nu) * N;
+    cols[(bi * ncols + cl) * Np + k] = src[k];
+  }
+  __syncthreads();
+  for (int r = tid; r < nb * ncols; r += nt) {
+    const int bi = r / ncols, col = col0 + r % ncols;
+    const double* y = cols + r * Np;
+    if (col < nu) {
+      ends[r] = post_spline_end(N, pts, [&](int k) -> double { return y[k]; });
+    } else {
+      const double* xb = x + size_t(b0 + bi) * K.n;
+      const double tspan = xb[ph.x_t0 + 1] - xb[ph.x_t0];
+      ends[r] = post_spline_end(N, pts, [&](int k) -> double { return 2.0 * ((1 / w[k]) * y[k]) / tspan; });
+    }
+  }
+}
+
+// Only when a phase's columns do not fit one workgroup's LDS next to the node part: workgroup (group of columns, tile of TB
+// instances), the values at tau = 1 into the workspace, ends_ws[b * ET + phase * ecols + column].
+__global__ void __launch_bounds__(256)
+rpm_extract_spline_kernel(const KParams K, const ExtractGroup* __restrict__ groups, int B, int TB, const double* __restrict__ x,
+                          const double* __restrict__ lam, double* __restrict__ ends_ws, int ET, int ecols) {
+  extern __shared__ __align__(16) double extract_ssm[];
+  const ExtractGroup v = groups[blockIdx.x];
+  const PhaseDev ph = K.phases[v.phase];
+  const ExtractLds L(ph.N, TB, v.ncols, 0, 0);
+  const int b0 = blockIdx.y * TB;
+  const int nb = B - b0 < TB ? B - b0 : TB;
+  extract_spline_ends(K, ph, v.col0, v.ncols, b0, nb, x, lam, extract_ssm + L.pts, extract_ssm + L.w, extract_ssm + L.cols, L.Np,
+                      extract_ssm + L.ends);
+  __syncthreads();
+  for (int r = threadIdx.x; r < nb * v.ncols; r += blockDim.x)
+    ends_ws[size_t(b0 + r / v.ncols) * ET + v.phase * ecols + v.col0 + r % v.ncols] = extract_ssm[L.ends + r];
+}
+
+// Workgroup (phase, tile of TB instances), 256 threads.  Items run k-fastest inside an instance: the lanes that share an instance
+// read every x / lambda column and store every output column as a contiguous run.  `fused`: the workgroup runs the phase's splines
+// itself and keeps their end values and the Lagrangian in LDS; otherwise the end values come from rpm_extract_spline_kernel and
+// the Lagrangian goes through the workspace lag_ws[b * NT + node] (written and read by this workgroup only).
+template <class Prob>
+__global__ void __launch_bounds__(256)
+rpm_extract_kernel(const KParams K, int B, int TB, int fused, long long EB, const double* __restrict__ x,
+                   const double* __restrict__ lam, const double* ends_ws, int ET, int ecols, double* lag_ws, int NT,
+                   double* __restrict__ out) {
+  constexpr int NX = Prob::NX, NU = Prob::NU, NC = Prob::NC;
+  constexpr int NXs = NX > 0 ? NX : 1, NUs = NU > 0 ? NU : 1, NCs = NC > 0 ? NC : 1;
+  extern __shared__ __align__(16) double extract_sm[];
+  const int p = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
+  const PhaseDev ph = K.phases[p];
+  const int N = ph.N, M = N + 1, ncols = ph.nu + ph.nc;   // what the host planner sized the launch by
+  const int b0 = blockIdx.y * TB;
+  const int nb = B - b0 < TB ? B - b0 : TB;
+  long long base = 0;   // the phase's offset inside an instance's block
+  for (int q = 0; q < p; ++q) base += extract_phase_doubles(K.phases[q].N, K.phases[q].nx, K.phases[q].nu, K.phases[q].nc);
+  const ExtractLds L(N, TB, fused ? ncols : 0, TB, fused ? TB : 0);
+  double* red = extract_sm + L.red;
+  if (fused && ncols > 0)
+    extract_spline_ends(K, ph, 0, ncols, b0, nb, x, lam, extract_sm + L.pts, extract_sm + L.w, extract_sm + L.cols, L.Np,
+                        extract_sm + L.ends);
+  // ---- end-point costates -trans(D(:,N)) * lambda: only the rows of the last mesh interval reach the last column, summed in
+  // ascending row order.  One lane per (instance, state), taken from the top of the workgroup so that they run beside the
+  // spline lanes instead of behind them; inside the node loop the one lane of k = N would walk nx chains of dependent loads.
+  // Parked in `red`, which the cost reduction needs only after the node loop.
+  static_assert(NX <= 256, "the end-point costates of an instance are parked in its 256 partial sums");
+  for (int idx = nt - 1 - tid; idx < nb * NX; idx += nt) {
+    const int s = idx % NXs, bi = idx / NXs;
+    const double* lp = lam + size_t(b0 + bi) * K.m + ph.g0;
+    const NodeDev last = K.nodes[ph.node0 + N - 1];
+    double acc = 0.0;
+    for (int r = last.dcol0; r < N; ++r) {
+      const NodeDev nr = K.nodes[ph.node0 + r];
+      acc += K.dvals[nr.drow_off + nr.dlen - 1] * lp[s * N + r];
+    }
+    red[bi * 256 + s] = -acc;
+  }
+  __syncthreads();
+  const long long o_state = M, o_control = o_state + (long long)M * NX, o_costate = o_control + (long long)M * NU,
+                  o_pathmult = o_costate + (long long)M * NX, o_ham = o_pathmult + (long long)M * NC, o_mayer = o_ham + M;
+
+  // ---- per node: rpm_post_kernel's body, statement by statement (the end-point costate comes from above) ---------
+  for (int idx = tid; idx < nb * M; idx += nt) {
+    const int k = idx % M, bi = idx / M;
+    const size_t b = size_t(b0 + bi);
+    const double* xb = x + b * K.n;
+    const double* lb = lam + b * K.m;   // the base of the instance's own multipliers
+    const double* cb = K.consts + b * K.consts_stride;
+    const double* u_end = fused ? extract_sm + L.ends + bi * ncols : ends_ws + b * ET + p * ecols;
+    const double* pm_end = u_end + NU;
+    double* lag = fused ? extract_sm + L.lag + bi * L.Np : lag_ws + b * NT + ph.node0;
+    double* ob = out + b * EB + base;
+    const double t0 = xb[ph.x_t0], tf = xb[ph.x_t0 + 1];
+    const double tau = k < N ? K.points[ph.node0 + k] : 1.0;
+    const double t = (tf - t0) * (tau + 1) / 2 + t0;                        // :49
+    ob[k] = t;
+    double xs[NXs], us[NUs], cst[NXs];
+#pragma unroll
+    for (int s = 0; s < NX; ++s) {
+      xs[s] = xb[ph.x_state0 + s * M + k];
+      ob[o_state + s * M + k] = xs[s];
+    }
+#pragma unroll
+    for (int j = 0; j < NU; ++j) {
+      us[j] = k < N ? xb[ph.x_control0 + j * N + k] : u_end[j];             // :53-64
+      ob[o_control + j * M + k] = us[j];
+    }
+    const double* lp = lb + ph.g0;                                          // this phase's multipliers, :73
+#pragma unroll
+    for (int s = 0; s < NX; ++s) {
+      cst[s] = k < N ? -((1 / K.weights[ph.node0 + k]) * lp[s * N + k]) : red[bi * 256 + s];   // -(W^-1 lambda), :75-79
+      ob[o_costate + s * M + k] = cst[s];
+    }
+#pragma unroll
+    for (int j = 0; j < NC; ++j)   // lambda WITHOUT the phase offset, exactly as Nlp2OPConverter.cpp:88 reads it
+      ob[o_pathmult + j * M + k] = k < N ? 2 * ((1 / K.weights[ph.node0 + k]) * lb[N * NX + j * N + k]) / (tf - t0) : pm_end[j];
+    double f[NXs], cp[NCs];
+    pf_dae<Prob>(ph.phase_num, t, xs, us, xb + ph.x_t0 + 2, cb, f, cp);
+    const double Lk = pf_lagrange<Prob>(ph.phase_num, t, xs, us, xb + ph.x_t0 + 2, cb);
+    double sum = 0.0;
+#pragma unroll
+    for (int s = 0; s < NX; ++s) {
+      const double term = cst[s] * f[s];
+      sum = (s == 0) ? term : sum + term;
+    }
+    ob[o_ham + k] = Lk + sum;                                               // :146
+    if (k < N) lag[k] = Lk;
+    if (k == 0) {
+      double x0[NXs], xf[NXs];
+#pragma unroll
+      for (int s = 0; s < NX; ++s) {
+        x0[s] = xb[ph.x_state0 + s * M];
+        xf[s] = xb[ph.x_state0 + s * M + N];
+      }
+      ob[o_mayer] = pf_mayer<Prob>(ph.phase_num, t0, x0, tf, xf, xb + ph.x_t0 + 2, cb);
+    }
+  }
+  __syncthreads();
+
+  // ---- lagrange_cost = (tf - t0) (w . L[0..N-1]) / 2 (:134) in rpm_post_cost_kernel's order, per instance: 256 partial sums over
+  // k = t (mod 256) in ascending k, the halving tree 128 .. 1, then the scaling
+  for (int idx = tid; idx < nb * 256; idx += nt) {
+    const int t = idx & 255, bi = idx >> 8;
+    const double* lag = fused ? extract_sm + L.lag + bi * L.Np : lag_ws + size_t(b0 + bi) * NT + ph.node0;
+    double s = 0.0;
+    for (int k = t; k < N; k += 256) s += K.weights[ph.node0 + k] * lag[k];
+    red[idx] = s;
+  }
+  __syncthreads();
+  for (int st = 128; st > 0; st >>= 1) {
+    for (int idx = tid; idx < nb * st; idx += nt) {
+      const int t = idx % st, bi = idx / st;
+      red[bi * 256 + t] += red[bi * 256 + t + st];
+    }
+    __syncthreads();
+  }
+  for (int bi = tid; bi < nb; bi += nt) {
+    const size_t b = size_t(b0 + bi);
+    const double* xb = x + b * K.n;
+    out[b * EB + base + o_mayer + 1] = (xb[ph.x_t0 + 1] - xb[ph.x_t0]) * red[bi * 256] / 2.0;
+  }
+}
+
+// nonfinite[b] = 1 when instance b's finished block holds a NaN or Inf: one workgroup per instance, a block-wide OR, no atomics
+__global__ void __launch_bounds__(256) rpm_extract_flag_kernel(long long EB, const double* __restrict__ out, int* __restrict__ nonfinite) {
+  const double* ob = out + size_t(blockIdx.x) * EB;
+  bool bad = false;
+  for (long long i = threadIdx.x; i < EB; i += blockDim.x) bad |= !(fabs(ob[i]) <= 1.7976931348623157e308);
+  const int any = __syncthreads_or(bad ? 1 : 0);
+  if (threadIdx.x == 0) nonfinite[blockIdx.x] = any ? 1 : 0;
+}
+
+namespace {
+
+constexpr size_t kExtractLdsLimit = 160 * 1024;   // LDS of one CU of the MI355X
+constexpr int kExtractAutoTile = 1;               // the fastest of 1, 2, 4, 8 in profiles/sweep_extract.json (tools/bench_sweep_extract.py)
+
+struct DeviceRestore {   // the calling thread's current device, put back on every exit path
+  int prev = -1;
+  DeviceRestore() { if (hipGetDevice(&prev) != hipSuccess) prev = -1; }
+  ~DeviceRestore() { if (prev >= 0) (void)hipSetDevice(prev); }
+};
+
+struct ExtractPlan {
+  int tile_opt = 0, lds_opt = 0;   // the options the plan was made under
+  int TB = 1, fused = 1, n_groups = 0;
+  size_t lds_node = 0, lds_spline = 0;
+  ExtractGroup* d_groups = nullptr;
+};
+struct ExtractState {
+  std::vector<ExtractPlan> plans;
+  double *ends_ws = nullptr, *lag_ws = nullptr;   // the split plans' workspace
+  // host-pointer form: the device output block and a page-locked mirror of the verdicts
+  double* out = nullptr;
+  int *out_flag = nullptr, *h_flag = nullptr;
+};
+
+// doubles the staged arrays of one workgroup may take: what the device offers less the partial sums of the largest tile, or
+// the option when that is smaller
+size_t extract_budget(const Engine& e) {
+  const size_t most = kExtractLdsLimit - 8 * 256 * sizeof(double);
+  return (e.opt_extract_lds > 0 ? std::min(size_t(e.opt_extract_lds), most) : most) / sizeof(double);
+}
+
+// Host planner.  Fused (one launch): every phase's spline columns fit one workgroup's LDS next to the Lagrangian rows; the
+// tile is halved before that is given up.  Otherwise the columns are dealt over the workgroups of a spline launch of their own,
+// again halving the tile first, and only a single column that does not fit is refused.
+bool extract_plan(const Engine& e, ExtractPlan* plan, std::vector<ExtractGroup>* groups) {
+  const size_t budget = extract_budget(e);
+  int TB0 = e.opt_extract_tile > 0 ? e.opt_extract_tile : kExtractAutoTile;
+  while (TB0 > 1 && TB0 / 2 >= e.n_instances) TB0 >>= 1;
+  ExtractPlan pl;
+  pl.tile_opt = e.opt_extract_tile;
+  pl.lds_opt = e.opt_extract_lds;
+  if (groups) groups->clear();
+  for (int TB = TB0; TB >= 1; TB >>= 1) {
+    bool fits = true;
+    size_t lds = 0;
+    for (const PhaseHost& p : e.ph) {
+      const ExtractLds L(p.N, TB, p.nu + p.nc, TB, TB);
+      fits = fits && size_t(L.staged()) <= budget;
+      lds = std::max(lds, size_t(L.total) * sizeof(double));
+    }
+    if (fits) {
+      pl.TB = TB;
+      pl.fused = 1;
+      pl.lds_node = lds;
+      *plan = pl;
+      return true;
+    }
+  }
+  int TB = TB0;
+  for (;; TB >>= 1) {
+    bool fits = true;
+    for (const PhaseHost& p : e.ph) fits = fits && (p.nu + p.nc == 0 || size_t(ExtractLds(p.N, TB, 1, 0, 0).total) <= budget);
+    if (fits) break;
+    if (TB == 1) return false;
+  }
+  pl.TB = TB;
+  pl.fused = 0;
+  pl.lds_node = size_t(ExtractLds(1, TB, 0, TB, 0).total) * sizeof(double);
+  for (size_t ip = 0; ip < e.ph.size(); ++ip) {
+    const PhaseHost& p = e.ph[ip];
+    const int cols = p.nu + p.nc;
+    if (cols == 0) continue;
+    int most = 1;   // the most columns of TB instances that fit
+    while (most < cols && size_t(ExtractLds(p.N, TB, most + 1, 0, 0).total) <= budget) ++most;
+    const int n_groups = (cols + most - 1) / most, per = (cols + n_groups - 1) / n_groups;
+    for (int col0 = 0; col0 < cols; col0 += per) {
+      const ExtractGroup g{int(ip), col0, std::min(per, cols - col0)};
+      pl.lds_spline = std::max(pl.lds_spline, size_t(ExtractLds(p.N, TB, g.ncols, 0, 0).total) * sizeof(double));
+      ++pl.n_groups;
+      if (groups) groups->push_back(g);
+    }
+  }
+  *plan = pl;
+  return true;
+}
+
+int extract_ecols(const Engine& e) {
+  int c = 0;
+  for (const PhaseHost& p : e.ph) c = std::max(c, p.nu + p.nc);
+  return c;
+}
+int extract_nodes(const Engine& e) {
+  int n = 0;
+  for (const PhaseHost& p : e.ph) n += p.N;
+  return n;
+}
+
+// hipFuncAttributeMaxDynamicSharedMemorySize is per device and only ever raised here
+std::mutex g_extract_attr_mutex;
+
+ExtractState& extract_state(Device& d) {
+  if (!d.extract) d.extract = new ExtractState();
+  return *static_cast<ExtractState*>(d.extract);
+}
+
+int extract_fail(Engine& e, int code, const std::string& msg) {
+  e.err = msg;
+  return code;
+}
+
+int extract_device(Engine& e) {
+  if (!e.dev) {
+    const int rc = device_init(e, 0);
+    if (rc) return rc;
+  }
+  HIP_TRY(e, hipSetDevice(e.dev->device_id));
+  return RPM_OK;
+}
+
+int extract_launch(Engine& e, const double* d_x, const double* d_lambda, double* d_out, int* d_nonfinite, hipStream_t st) {
+  Device& d = *e.dev;
+  ExtractState& es = extract_state(d);
+  const ExtractPlan* plan = nullptr;
+  for (const ExtractPlan& p : es.plans)
+    if (p.tile_opt == e.opt_extract_tile && p.lds_opt == e.opt_extract_lds) plan = &p;
+  const size_t B = size_t(e.n_instances);
+  const int ET = e.P * extract_ecols(e), NT = extract_nodes(e);
+  if (!plan) {   // first call under these options: the only allocations and the only blocking copy
+    ExtractPlan p;
+    std::vector<ExtractGroup> groups;
+    if (!extract_plan(e, &p, &groups)) return extract_fail(e, RPM_E_UNSUPPORTED, "nlp2op_batch: a column does not fit one workgroup's LDS");
+    if (!p.fused) {
+      HIP_TRY(e, upload(&p.d_groups, groups));
+      if (!es.ends_ws) {
+        HIP_TRY(e, hipMalloc(reinterpret_cast<void**>(&es.ends_ws), std::max<size_t>(B * ET, 1) * sizeof(double)));
+        HIP_TRY(e, hipMalloc(reinterpret_cast<void**>(&es.lag_ws), std::max<size_t>(B * NT, 1) * sizeof(double)));
+      }
+    }
+    if (std::max(p.lds_node, p.lds_spline) > 64 * 1024) {
+      std::lock_guard<std::mutex> lock(g_extract_attr_mutex);
+      hipError_t s = hipSuccess;
+      if (p.lds_node > 64 * 1024)
+        with_problem(e.problem_id, [&](auto prob) {
+          using P = decltype(prob);
+          s = hipFuncSetAttribute(reinterpret_cast<const void*>(rpm_extract_kernel<P>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  int(kExtractLdsLimit));
+        });
+      if (s == hipSuccess && p.lds_spline > 64 * 1024)
+        s = hipFuncSetAttribute(reinterpret_cast<const void*>(rpm_extract_spline_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                int(kExtractLdsLimit));
+      HIP_TRY(e, s);
+    }
+    es.plans.push_back(p);
+    plan = &es.plans.back();
+  }
+  long long EB = 0;
+  nlp2op_batch_layout(e, 0, nullptr, &EB);
+  const int Bi = e.n_instances, TB = plan->TB;
+  const unsigned tiles = unsigned((Bi + TB - 1) / TB);
+  if (!plan->fused && plan->n_groups > 0)
+    hipLaunchKernelGGL(rpm_extract_spline_kernel, dim3(unsigned(plan->n_groups), tiles), dim3(256), plan->lds_spline, st, d.kp,
+                       plan->d_groups, Bi, TB, d_x, d_lambda, es.ends_ws, ET, extract_ecols(e));
+  const bool known = with_problem(e.problem_id, [&](auto prob) {
+    using P = decltype(prob);
+    hipLaunchKernelGGL((rpm_extract_kernel<P>), dim3(unsigned(e.P), tiles), dim3(256), plan->lds_node, st, d.kp, Bi, TB, plan->fused,
+                       EB, d_x, d_lambda, es.ends_ws, ET, extract_ecols(e), es.lag_ws, NT, d_out);
+  });
+  if (!known) return extract_fail(e, RPM_E_UNSUPPORTED, "nlp2op_batch: this library has no kernels for the engine's problem");
+  if (d_nonfinite) hipLaunchKernelGGL(rpm_extract_flag_kernel, dim3(unsigned(Bi)), dim3(256), 0, st, EB, d_out, d_nonfinite);
+  const hipError_t s = hipGetLastError();
+  if (s != hipSuccess) return extract_fail(e, RPM_E_DEVICE, std::string("nlp2op_batch launch: ") + hipGetErrorString(s));
+  return RPM_OK;
+}
+
+}  // namespace
+
+void extract_destroy(Device* d) {
+  ExtractState* es = static_cast<ExtractState*>(d->extract);
+  if (!es) return;
+  for (ExtractPlan& p : es->plans)
+    if (p.d_groups) (void)hipFree(p.d_groups);
+  for (void* p : {static_cast<void*>(es->ends_ws), static_cast<void*>(es->lag_ws), static_cast<void*>(es->out), static_cast<void*>(es->out_flag)})
+    if (p) (void)hipFree(p);
+  if (es->h_flag) (void)hipHostFree(es->h_flag);
+  delete es;
+  d->extract = nullptr;
+}
+
+// host only: the offsets of a phase's eight fields inside an instance's block, and the block's length
+void nlp2op_batch_layout(const Engine& e, int phase, long long field_offset[8], long long* block_doubles) {
+  long long off = 0;
+  for (int ip = 0; ip < e.P; ++ip) {
+    const PhaseHost& p = e.ph[size_t(ip)];
+    const long long M = p.N + 1;
+    if (ip == phase && field_offset) {
+      const long long len[8] = {M, M * p.nx, M * p.nu, M * p.nx, M * p.nc, M, 1, 1};
+      long long o = off;
+      for (int f = 0; f < 8; ++f) {
+        field_offset[f] = o;
+        o += len[f];
+      }
+    }
+    off += extract_phase_doubles(p.N, p.nx, p.nu, p.nc);
+  }
+  if (block_doubles) *block_doubles = off;
+}
+
+// workgroups per tile of instances of the spline launch under the engine's options: 0 when the extraction is one fused launch,
+// -1 when a column does not fit
+int extract_group_count(const Engine& e) {
+  ExtractPlan p;
+  if (!extract_plan(e, &p, nullptr)) return -1;
+  return p.fused ? 0 : p.n_groups;
+}
+
+// every error of the engine's state, decided on the host before a device is touched
+int extract_check(Engine& e) {
+  const std::string who = "nlp2op_batch: ";
+  if (e.shard_mode == RPM_SHARD_INTERVALS && e.shard_world > 1) return extract_fail(e, RPM_E_UNSUPPORTED, who + "not with interval sharding");
+  for (const PhaseHost& p : e.ph)   // the path multipliers' unshifted index stays inside the instance's own lambda block
+    if ((long long)p.N * (p.nx + p.nc) > e.m) return extract_fail(e, RPM_E_UNSUPPORTED, who + "a phase's path multipliers would be read past the instance's multipliers");
+  ExtractPlan p;
+  if (!extract_plan(e, &p, nullptr)) {
+    int most = 0;
+    for (const PhaseHost& q : e.ph) most = std::max(most, q.N);
+    return extract_fail(e, RPM_E_UNSUPPORTED, who + "a column of " + std::to_string(most) + " nodes does not fit one workgroup's LDS");
+  }
+  return RPM_OK;
+}
+
+// device-resident: one launch (the spline launch before it when the columns are dealt, the verdicts' after it) on `stream`; after
+// the first call on an engine nothing else
+int dev_nlp2op_batch(Engine& e, const double* d_x, const double* d_lambda, double* d_out, int* d_nonfinite, void* stream) {
+  int rc = extract_check(e);
+  if (rc) return rc;
+  DeviceRestore restore;
+  rc = extract_device(e);
+  if (rc) return rc;
+  return extract_launch(e, d_x, d_lambda, d_out, d_nonfinite, static_cast<hipStream_t>(stream));
+}
+
+// the same through host arrays: x and lambda up through the staging slots, the blocks and the verdicts back; blocking
+int host_nlp2op_batch(Engine& e, const double* x, const double* lambda, double* out, int* nonfinite) {
+  int rc = extract_check(e);
+  if (rc) return rc;
+  DeviceRestore restore;
+  rc = extract_device(e);
+  if (rc) return rc;
+  Device& d = *e.dev;
+  ExtractState& es = extract_state(d);
+  const size_t B = size_t(e.n_instances);
+  long long EB = 0;
+  nlp2op_batch_layout(e, 0, nullptr, &EB);
+  if (!es.out) {
+    HIP_TRY(e, hipMalloc(reinterpret_cast<void**>(&es.out), B * size_t(EB) * sizeof(double)));
+    HIP_TRY(e, hipMalloc(reinterpret_cast<void**>(&es.out_flag), B * sizeof(int)));
+    HIP_TRY(e, hipHostMalloc(reinterpret_cast<void**>(&es.h_flag), B * sizeof(int), hipHostMallocDefault));
+  }
+  host_new_x(e);   // d_x is about to hold other values than the callbacks' last x
+  rc = dev_upload(e, d.d_x, x, B * e.n, STAGE_X);
+  if (rc == RPM_OK) rc = dev_upload(e, d.d_lambda, lambda, B * e.m, STAGE_LAMBDA);
+  if (rc) return rc;
+  rc = extract_launch(e, d.d_x, d.d_lambda, es.out, nonfinite ? es.out_flag : nullptr, d.stream);
+  if (rc) return rc;
+  if (nonfinite) HIP_TRY(e, hipMemcpyAsync(es.h_flag, es.out_flag, B * sizeof(int), hipMemcpyDeviceToHost, d.stream));
+  rc = dev_download(e, out, es.out, B * size_t(EB), STAGE_G);
+  if (rc) return rc;
+  HIP_TRY(e, hipStreamSynchronize(d.stream));
+  dev_stage_synced(e);
+  if (nonfinite) std::memcpy(nonfinite, es.h_flag, B * sizeof(int));
+  return RPM_OK;
+}
+
+}  // namespace rpm

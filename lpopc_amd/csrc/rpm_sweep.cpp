@@ -220,6 +220,37 @@ int rpm_sweep_carry_solution(rpm_sweep* from, rpm_sweep* to, const double* x_fro
   return RPM_OK;
 }
 
+/* rpm_nlp2op_batch on every share, side by side: x B x n, lambda B x m, out B x EB, nonfinite B or NULL */
+int rpm_sweep_nlp2op(rpm_sweep* s, const double* x, const double* lambda, double* out, int* nonfinite) {
+  if (!s) return RPM_E_INVALID;
+  if (!x || !lambda || !out) {
+    s->err = "rpm_sweep_nlp2op: x, lambda or out is NULL";
+    return RPM_E_INVALID;
+  }
+  const size_t N = s->eng.size();
+  long long EB = 0;
+  rpm_nlp2op_batch_layout(s->eng[0], 0, nullptr, &EB);
+  int prev = -1;
+  if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+  std::vector<int> rcs(N, RPM_OK);
+  auto run = [&](size_t r) {
+    (void)hipSetDevice(s->dev[r]);
+    const size_t i0 = size_t(s->first[r]);
+    rcs[r] = rpm_nlp2op_batch(s->eng[r], x + i0 * s->n, lambda + i0 * s->m, out + i0 * size_t(EB), nonfinite ? nonfinite + i0 : nullptr);
+  };
+  std::vector<std::thread> th;
+  for (size_t r = 1; r < N; ++r) th.emplace_back(run, r);
+  run(0);
+  for (std::thread& t : th) t.join();
+  if (prev >= 0) (void)hipSetDevice(prev);
+  for (size_t r = 0; r < N; ++r)
+    if (rcs[r]) {
+      s->err = "share " + std::to_string(r) + " (device " + std::to_string(s->dev[r]) + "): " + rpm_last_error(s->eng[r]);
+      return rcs[r];
+    }
+  return RPM_OK;
+}
+
 /* totals over the shares of the last solve: batched iterations (the largest share's count), factorisations and trial points (sums) */
 int rpm_sweep_get_stats(rpm_sweep* s, int* iterations, int* factorizations, int* trial_points) {
   if (!s) return RPM_E_INVALID;

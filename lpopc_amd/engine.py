@@ -31,6 +31,7 @@ ABI_SYMBOLS = [
     "rpm_solution_error", "rpm_ph_refine_mesh", "rpm_ph_refine_from_error",
     "rpm_solution_error_batch_sizes", "rpm_solution_error_batch_dev", "rpm_solution_error_batch", "rpm_sweep_solution_error",
     "rpm_carry_solution_batch_dev", "rpm_carry_solution_batch", "rpm_sweep_carry_solution",
+    "rpm_nlp2op_batch_layout", "rpm_nlp2op_batch_dev", "rpm_nlp2op_batch", "rpm_sweep_nlp2op",
     "rpm_hpliu_create", "rpm_hpliu_destroy", "rpm_hpliu_last_error", "rpm_hpliu_refine",
     "rpm_ipm_create", "rpm_ipm_destroy", "rpm_ipm_last_error", "rpm_ipm_set_option", "rpm_ipm_set_bounds", "rpm_ipm_set_all_bounds", "rpm_ipm_get_info",
     "rpm_group_create", "rpm_group_destroy", "rpm_group_last_error", "rpm_group_size", "rpm_group_engine", "rpm_group_device_init",
@@ -115,6 +116,10 @@ def lib(path=None):
     L.rpm_carry_solution_batch_dev.argtypes = [vp, vp, vp, vp, vp, vp]
     L.rpm_carry_solution_batch.argtypes = [vp, vp, dp, dp, ip]
     L.rpm_sweep_carry_solution.argtypes = [vp, vp, dp, dp, ip]
+    L.rpm_nlp2op_batch_layout.argtypes = [vp, C.c_int, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
+    L.rpm_nlp2op_batch_dev.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.rpm_nlp2op_batch.argtypes = [vp, dp, dp, dp, ip]
+    L.rpm_sweep_nlp2op.argtypes = [vp, dp, dp, dp, ip]
     L.rpm_hpliu_create.argtypes = [C.c_int, C.c_double, C.c_int, C.c_double, C.POINTER(vp)]
     L.rpm_hpliu_destroy.argtypes = [vp]
     L.rpm_hpliu_destroy.restype = None
@@ -242,6 +247,38 @@ def _batch_estimate(fn, check, handle, x, B, sizes, shapes, mask, full):
     if full:
         out["rel_err"] = _split_rel(rel, shapes)
     return out
+
+
+EXTRACT_FIELDS = ("time", "state", "control", "costate", "pathmult", "hamiltonian", "mayer_cost", "lagrange_cost")
+
+
+def _extract_layout(L, handle, n_phases, check):
+    """rpm_nlp2op_batch_layout for every phase -> (offsets: n_phases x 8 in the order of EXTRACT_FIELDS, EB)."""
+    offs, eb = np.zeros((n_phases, 8), dtype=np.int64), C.c_longlong()
+    for p in range(n_phases):
+        o = (C.c_longlong * 8)()
+        check(L.rpm_nlp2op_batch_layout(handle, p, o, C.byref(eb)))
+        offs[p] = list(o)
+    return offs, eb.value
+
+
+def _batch_extract(fn, check, handle, x, lam, B, m, layout):
+    """Shared by NLPEngine.nlp2op_batch and SweepGroup.nlp2op: call, then cut every instance's block per phase and field."""
+    offs, EB = layout
+    lam = np.ascontiguousarray(lam, dtype=np.float64).ravel()
+    if lam.size != B * m:
+        raise RpmError(RPM_E_INVALID, "lambda has %d entries, expected %d" % (lam.size, B * m))
+    out, flags = np.zeros((B, EB)), np.zeros(B, dtype=np.int32)
+    check(fn(handle, _dp(x), _dp(lam), _dp(out), _ip(flags)))
+    ends = np.append(offs.ravel()[1:], EB)             # a field ends where the next one starts
+    phases = []
+    for p in range(offs.shape[0]):
+        d = {}
+        for f, name in enumerate(EXTRACT_FIELDS):
+            a = out[:, offs[p, f]:ends[p * 8 + f]]
+            d[name] = a[:, 0].copy() if f >= 6 else a.copy()
+        phases.append(d)
+    return phases, flags
 
 
 class NLPEngine:
@@ -550,6 +587,25 @@ class NLPEngine:
         """Device-resident form on torch CUDA tensors (float64; d_nonfinite int32).  Asynchronous on `stream`."""
         self._check(self._L.rpm_carry_solution_batch_dev(self._h, to._h, self._ptr(d_x), self._ptr(d_x_to), self._ptr(d_nonfinite),
                                                          self._stream(stream)))
+
+    # ---- the extraction of a whole sweep: all phases, all instances (rpm_nlp2op_batch*) ---------------------------------
+    def nlp2op_batch_layout(self):
+        """(offsets, EB): per phase the offsets of time, state, control, costate, pathmult, hamiltonian, mayer_cost and
+        lagrange_cost inside one instance's block (n_phases x 8), and the block's length in doubles.  Host only."""
+        return _extract_layout(self._L, self._h, self.n_phases, self._check)
+
+    def nlp2op_batch(self, x, lam):
+        """Nlp2OpControl of every instance: x (n_instances x n), lam (n_instances x m) -> (per phase a dict with the keys of
+        nlp2op_control, every array with a leading instance axis and the two costs as n_instances-vectors; nonfinite:
+        n_instances ints)."""
+        return _batch_extract(self._L.rpm_nlp2op_batch, self._check, self._h, self._x(x), lam, self.n_instances, self.m,
+                              self.nlp2op_batch_layout())
+
+    def nlp2op_batch_dev(self, d_x, d_lambda, d_out, d_nonfinite=None, stream=None):
+        """Device-resident form on torch CUDA tensors (float64; d_out n_instances x EB in the library's layout, d_nonfinite
+        int32).  Asynchronous on `stream`."""
+        self._check(self._L.rpm_nlp2op_batch_dev(self._h, self._ptr(d_x), self._ptr(d_lambda), self._ptr(d_out),
+                                                 self._ptr(d_nonfinite), self._stream(stream)))
 
     # ---- tables and sharding ---------------------------------------------------------------
     def phase_tables(self, phase):

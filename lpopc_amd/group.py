@@ -7,7 +7,7 @@ import ctypes as C
 import numpy as np
 
 from . import _abi
-from .engine import RPM_E_INVALID, RPM_OK, RpmError, _batch_estimate, _dp, _ip, _phase_shapes, lib
+from .engine import RPM_E_INVALID, RPM_OK, RpmError, _batch_estimate, _batch_extract, _dp, _extract_layout, _ip, _phase_shapes, lib
 
 
 class _EngineView:
@@ -209,6 +209,15 @@ class SweepGroup:
         flags = np.zeros(self.n_instances, dtype=np.int32)
         self._check(self._L.rpm_sweep_carry_solution(self._h, to._h, _dp(x), _dp(out), _ip(flags)))
         return out, flags
+
+    def nlp2op(self, x, lam):
+        """rpm_sweep_nlp2op: as NLPEngine.nlp2op_batch, over all shares; equal to one engine holding all instances bit for bit."""
+        x = np.ascontiguousarray(x, dtype=np.float64).ravel()
+        if x.size != self.n * self.n_instances:
+            raise RpmError(RPM_E_INVALID, "x has %d entries, expected %d" % (x.size, self.n * self.n_instances))
+        e0 = self._L.rpm_sweep_engine(self._h, 0)
+        return _batch_extract(self._L.rpm_sweep_nlp2op, self._check, self._h, x, lam, self.n_instances, self.m,
+                              _extract_layout(self._L, e0, self.n_phases, self._check))
 
     def ph_refine(self, x, tol, nmin, nmax, mask=None):
         """The sweep's next mesh: per phase (no_more_refine, mesh, nodes, interval_error) from rel_err_max."""
