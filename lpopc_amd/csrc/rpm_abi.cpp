@@ -358,7 +358,7 @@ int rpm_solution_error_batch_dev(rpm_engine* h, const double* d_x, const int* d_
   Engine& e = h->e;
   RPM_GUARD_BEGIN
   if (!d_x) return fail(e, RPM_E_INVALID, "solution_error_batch_dev: d_x is NULL");
-  if (e.shard_mode == RPM_SHARD_INTERVALS && e.shard_world > 1) return fail(e, RPM_E_UNSUPPORTED, "solution_error_batch: not with interval sharding");
+  if (rpm::sharded(e)) return fail(e, RPM_E_UNSUPPORTED, "solution_error_batch: not with interval sharding");
   return rpm::dev_solution_error_batch(e, d_x, d_instance_mask, d_interval_error, d_rel_err_max, d_rel_err, d_nonfinite, stream);
   RPM_GUARD_END(e)
 }
@@ -369,7 +369,7 @@ int rpm_solution_error_batch(rpm_engine* h, const double* x, const int* instance
   Engine& e = h->e;
   RPM_GUARD_BEGIN
   if (!x) return fail(e, RPM_E_INVALID, "solution_error_batch: x is NULL");
-  if (e.shard_mode == RPM_SHARD_INTERVALS && e.shard_world > 1) return fail(e, RPM_E_UNSUPPORTED, "solution_error_batch: not with interval sharding");
+  if (rpm::sharded(e)) return fail(e, RPM_E_UNSUPPORTED, "solution_error_batch: not with interval sharding");
   if (instance_mask && rel_err_max) {
     bool any = false;
     for (int b = 0; b < e.n_instances; ++b) any = any || instance_mask[b] != 0;

@@ -2,7 +2,7 @@
 // between two meshes (Nlp2OpConverter::Nlp2OpControl installs time / state / control / parameter as the next guess,
 // Core/Nlp2OPConverter.cpp:160-193; LpGuessChecker splines it onto the new nodes, Core/LpGuessChecker.cpp:208-294), for all
 // instances of an engine at once and without leaving the device.  Per instance, phase and column, in this order:
-//   1. time[k] = (tf - t0) * (tau_k + 1) / 2 + t0 at the N LGR points and at tau = 1            (rpm_post_kernel)
+//   1. time[k] = post_time(t0, tf, tau_k) at the N LGR points and at tau = 1                     (rpm_post_device.hpp)
 //   2. controls only: the value at tau = 1, post_spline_end through the N points                (rpm_post_spline_kernel)
 //   3. knots tau_g[k] = 2 * (time[k] - time[0]) / (time[N] - time[0]) - 1                       (rpm_setup.cpp, starting point)
 //   4. the natural cubic spline of spline_eval (rpm_setup.cpp) through the N + 1 knots, evaluated at the target phase's
@@ -10,9 +10,7 @@
 //   5. t0 = time[0], tf = time[N]; static parameters copied.
 // Everything but the cubes of step 4 repeats the one-instance path (rpm_nlp2op_control, a new rpm_create carrying the guess,
 // rpm_get_starting_point) operation by operation; the cubes are A * A * A here and glibc's pow(A, 3) there.
-#include <mutex>
-
-#include "rpm_device_internal.hpp"
+#include "rpm_post_device.hpp"
 
 namespace rpm {
 
@@ -81,8 +79,8 @@ rpm_carry_kernel(const PhaseDev* __restrict__ fph, const double* __restrict__ fp
     const int k = idx % M, bi = idx / M;
     const double* xb = x_from + size_t(b0 + bi) * n_from;
     const double t0 = xb[pf.x_t0], tf = xb[pf.x_t0 + 1];
-    const double time_k = (tf - t0) * ((k < N ? fp[k] : 1.0) + 1) / 2 + t0;
-    const double time_0 = (tf - t0) * (fp[0] + 1) / 2 + t0, time_N = (tf - t0) * (1.0 + 1) / 2 + t0;
+    const double time_k = post_time(t0, tf, k < N ? fp[k] : 1.0);
+    const double time_0 = post_time(t0, tf, fp[0]), time_N = post_time(t0, tf, 1.0);
     tau[bi * Mp + k] = 2 * (time_k - time_0) / (time_N - time_0) - 1;
   }
   for (int idx = tid; idx < nb * ncols * M; idx += nt) {
@@ -164,32 +162,14 @@ rpm_carry_kernel(const PhaseDev* __restrict__ fph, const double* __restrict__ fp
       const double* xb = x_from + size_t(b0 + bi) * n_from;
       const double t0 = xb[pf.x_t0], tf = xb[pf.x_t0 + 1];
       double val;
-      if (j == 0) val = (tf - t0) * (fp[0] + 1) / 2 + t0;          // time[0]
-      else if (j == 1) val = (tf - t0) * (1.0 + 1) / 2 + t0;       // time[N]
+      if (j == 0) val = post_time(t0, tf, fp[0]);          // time[0]
+      else if (j == 1) val = post_time(t0, tf, 1.0);       // time[N]
       else val = xb[pf.x_t0 + j];
       x_to[size_t(b0 + bi) * n_to + pt.x_t0 + j] = val;
     }
 }
 
-// nonfinite[b] = 1 when any carried value of instance b is NaN or Inf: one workgroup per instance over its finished block
-// (queued behind rpm_carry_kernel; a block-wide OR, no atomics)
-__global__ void __launch_bounds__(256) rpm_carry_flag_kernel(int n_to, const double* __restrict__ x_to, int* __restrict__ nonfinite) {
-  const double* xb = x_to + size_t(blockIdx.x) * n_to;
-  bool bad = false;
-  for (int i = threadIdx.x; i < n_to; i += blockDim.x) bad |= !(fabs(xb[i]) <= 1.7976931348623157e308);
-  const int any = __syncthreads_or(bad ? 1 : 0);
-  if (threadIdx.x == 0) nonfinite[blockIdx.x] = any ? 1 : 0;
-}
-
 namespace {
-
-constexpr size_t kCarryLdsLimit = 160 * 1024;   // LDS of one CU of the MI355X
-
-struct DeviceRestore {   // the calling thread's current device, put back on every exit path
-  int prev = -1;
-  DeviceRestore() { if (hipGetDevice(&prev) != hipSuccess) prev = -1; }
-  ~DeviceRestore() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
 
 struct CarryPlan {
   long long to_serial = 0;
@@ -200,14 +180,11 @@ struct CarryPlan {
 };
 struct CarryState {
   std::vector<CarryPlan> plans;
-  // host-pointer form: the device output block and a page-locked mirror of the verdicts
-  double* out = nullptr;
-  int *out_flag = nullptr, *h_flag = nullptr;
-  size_t out_cap = 0, flag_cap = 0;
+  HostForm host;   // host-pointer form: the carried block
 };
 
 size_t carry_budget(const Engine& from) {
-  return from.opt_carry_lds > 0 ? std::min(size_t(from.opt_carry_lds), kCarryLdsLimit) : kCarryLdsLimit;
+  return from.opt_carry_lds > 0 ? std::min(size_t(from.opt_carry_lds), kCuLdsBytes) : kCuLdsBytes;
 }
 
 // Host planner: instances per workgroup and the split of every phase's columns over workgroups.  Columns are independent,
@@ -215,8 +192,7 @@ size_t carry_budget(const Engine& from) {
 bool carry_plan(const Engine& from, int* TB_out, std::vector<CarryGroup>* groups, size_t* lds_out) {
   const size_t budget = carry_budget(from) / sizeof(double);
   // automatic: 2 instances per workgroup (reasoned; tools/bench_sweep_carry.py measures every value)
-  int TB = from.opt_carry_tile > 0 ? from.opt_carry_tile : 2;
-  while (TB > 1 && TB / 2 >= from.n_instances) TB >>= 1;
+  int TB = clamp_tile(from.opt_carry_tile > 0 ? from.opt_carry_tile : 2, from.n_instances);
   for (;; TB >>= 1) {
     bool fits = true;
     for (const PhaseHost& p : from.ph) fits = fits && size_t(CarryLds(p.N + 1, TB, 1).total) <= budget;
@@ -230,8 +206,7 @@ bool carry_plan(const Engine& from, int* TB_out, std::vector<CarryGroup>* groups
     const int cols = p.nx + p.nu;
     int most = 1;   // the most columns that fit next to the per-instance rows
     while (most < cols && size_t(CarryLds(p.N + 1, TB, most + 1).total) <= budget) ++most;
-    const int n_groups = cols > 0 ? (cols + most - 1) / most : 1;
-    const int per = cols > 0 ? (cols + n_groups - 1) / n_groups : 0;
+    const auto [n_groups, per] = deal_columns(cols, most);
     for (int g = 0, col0 = 0; g < n_groups; ++g, col0 += per) {
       const CarryGroup cg{int(ip), col0, std::min(per, cols - col0), g == 0 ? 1 : 0};
       lds = std::max(lds, size_t(CarryLds(p.N + 1, TB, cg.ncols).total) * sizeof(double));
@@ -242,10 +217,6 @@ bool carry_plan(const Engine& from, int* TB_out, std::vector<CarryGroup>* groups
   *lds_out = lds;
   return true;
 }
-
-// hipFuncAttributeMaxDynamicSharedMemorySize is per device and only ever raised here
-std::mutex g_carry_attr_mutex;
-size_t g_carry_attr[64] = {};
 
 int carry_devices(Engine& from, Engine& to) {
   int id = from.dev ? from.dev->device_id : (to.dev ? to.dev->device_id : 0);
@@ -287,14 +258,7 @@ int carry_launch(Engine& from, Engine& to, const double* d_x_from, double* d_x_t
     p.lds_opt = from.opt_carry_lds;
     p.n_groups = int(groups.size());
     HIP_TRY(from, upload(&p.d_groups, groups));
-    if (p.lds > 64 * 1024 && d.device_id >= 0 && d.device_id < 64) {
-      std::lock_guard<std::mutex> lock(g_carry_attr_mutex);
-      if (g_carry_attr[d.device_id] < p.lds) {
-        HIP_TRY(from, hipFuncSetAttribute(reinterpret_cast<const void*>(rpm_carry_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                          int(kCarryLdsLimit)));
-        g_carry_attr[d.device_id] = kCarryLdsLimit;
-      }
-    }
+    HIP_TRY(from, raise_dynamic_lds(reinterpret_cast<const void*>(rpm_carry_kernel), p.lds));
     cs.plans.push_back(p);
     plan = &cs.plans.back();
   }
@@ -302,7 +266,7 @@ int carry_launch(Engine& from, Engine& to, const double* d_x_from, double* d_x_t
   hipLaunchKernelGGL(rpm_carry_kernel, dim3(unsigned(plan->n_groups), unsigned((B + plan->TB - 1) / plan->TB)), dim3(256), plan->lds, st,
                      d.d_phases, d.d_points, from.n, to.dev->d_phases, to.dev->d_points, to.n, plan->d_groups, B, plan->TB, d_x_from,
                      d_x_to);
-  if (d_nonfinite) hipLaunchKernelGGL(rpm_carry_flag_kernel, dim3(unsigned(B)), dim3(256), 0, st, to.n, d_x_to, d_nonfinite);
+  if (d_nonfinite) flag_launch(to.n, d_x_to, d_nonfinite, B, st);
   const hipError_t s = hipGetLastError();
   if (s != hipSuccess) {
     from.err = std::string("carry_solution_batch launch: ") + hipGetErrorString(s);
@@ -323,9 +287,7 @@ void carry_destroy(Device* d) {
   if (!cs) return;
   for (CarryPlan& p : cs->plans)
     if (p.d_groups) (void)hipFree(p.d_groups);
-  if (cs->out) (void)hipFree(cs->out);
-  if (cs->out_flag) (void)hipFree(cs->out_flag);
-  if (cs->h_flag) (void)hipHostFree(cs->h_flag);
+  cs->host.release();
   delete cs;
   d->carry = nullptr;
 }
@@ -358,7 +320,6 @@ int carry_check(Engine& from, const Engine& to, const void* x_from, const void* 
   const char* b = static_cast<const char*>(x_to);
   const size_t na = size_t(from.n_instances) * from.n * sizeof(double), nb = size_t(to.n_instances) * to.n * sizeof(double);
   if (a < b + nb && b < a + na) return carry_fail(from, RPM_E_INVALID, who + "x_from and x_to overlap");
-  auto sharded = [](const Engine& e) { return e.shard_mode == RPM_SHARD_INTERVALS && e.shard_world > 1; };
   if (sharded(from) || sharded(to)) return carry_fail(from, RPM_E_UNSUPPORTED, who + "not with interval sharding");
   int TB = 0;
   size_t lds = 0;
@@ -391,31 +352,16 @@ int host_carry_batch(Engine& from, Engine& to, const double* x_from, double* x_t
   HIP_TRY(from, hipSetDevice(d.device_id));
   CarryState& cs = carry_state(d);
   const size_t B = size_t(from.n_instances), count = B * to.n;
-  if (cs.out_cap < count) {
-    HIP_TRY(from, hipStreamSynchronize(d.stream));
-    if (cs.out) HIP_TRY(from, hipFree(cs.out));
-    cs.out = nullptr;
-    cs.out_cap = 0;
-    HIP_TRY(from, hipMalloc(reinterpret_cast<void**>(&cs.out), count * sizeof(double)));
-    cs.out_cap = count;
-  }
-  if (cs.flag_cap < B) {
-    HIP_TRY(from, hipMalloc(reinterpret_cast<void**>(&cs.out_flag), B * sizeof(int)));
-    HIP_TRY(from, hipHostMalloc(reinterpret_cast<void**>(&cs.h_flag), B * sizeof(int), hipHostMallocDefault));
-    cs.flag_cap = B;
-  }
+  rc = cs.host.ensure(from, count, B);
+  if (rc) return rc;
   host_new_x(from);   // d_x is about to hold other values than the callbacks' last x
   rc = dev_upload(from, d.d_x, x_from, B * from.n, STAGE_X);
   if (rc) return rc;
-  rc = carry_launch(from, to, d.d_x, cs.out, nonfinite ? cs.out_flag : nullptr, d.stream);
+  rc = carry_launch(from, to, d.d_x, cs.host.out, nonfinite ? cs.host.flags : nullptr, d.stream);
+  if (rc == RPM_OK) rc = cs.host.fetch(from, nonfinite, B);
+  if (rc == RPM_OK) rc = dev_download(from, x_to, cs.host.out, count, STAGE_G);
   if (rc) return rc;
-  if (nonfinite) HIP_TRY(from, hipMemcpyAsync(cs.h_flag, cs.out_flag, B * sizeof(int), hipMemcpyDeviceToHost, d.stream));
-  rc = dev_download(from, x_to, cs.out, count, STAGE_G);
-  if (rc) return rc;
-  HIP_TRY(from, hipStreamSynchronize(d.stream));
-  dev_stage_synced(from);
-  if (nonfinite) std::memcpy(nonfinite, cs.h_flag, B * sizeof(int));
-  return RPM_OK;
+  return cs.host.finish(from, nonfinite, B);
 }
 
 }  // namespace rpm

@@ -3,6 +3,8 @@
 // transfers and NaN/Inf scans of the host-pointer path, the interval-sharding copies.  The tile kernels (K1-K4) live in
 // rpm_tile_kernels.hip, the exact Hessian (K6) in rpm_hess_kernels.hip, the post-solve kernels in rpm_post_kernels.hip.
 // No CPU fallback lives here or anywhere else in the product.
+#include <mutex>
+
 #include "rpm_device_internal.hpp"
 #include "rpm_pin.h"
 
@@ -537,12 +539,17 @@ int dev_stage_download(Engine& e, int slot, double* host, const double* dev, siz
 }
 
 // ---- small helpers used by the C ABI (rpm_abi.cpp) ---------------------------------------------
-int dev_upload_x(Engine& e, const double* x) {
+int dev_bind(Engine& e) {
   if (!e.dev) {
     int rc = device_init(e, 0);
     if (rc) return rc;
   }
   HIP_TRY(e, hipSetDevice(e.dev->device_id));
+  return RPM_OK;
+}
+int dev_upload_x(Engine& e, const double* x) {
+  int rc = dev_bind(e);
+  if (rc) return rc;
   return dev_stage_upload(e, STAGE_X, e.dev->d_x, x, size_t(e.n_instances) * e.n);
 }
 // `host` is a caller's array: through the page-lock registry or the staging slot, never the runtime's pageable path
@@ -563,6 +570,52 @@ int dev_update_instance_constants(Engine& e) {
   d.kp.consts_stride = int(e.consts.size());
   host_new_x(e);   // constraint pair, objective and gradient cached under the old constants are gone
   return RPM_OK;
+}
+
+hipError_t raise_dynamic_lds(const void* kernel, size_t bytes) {
+  static std::mutex attr_mutex;
+  if (bytes <= 64 * 1024) return hipSuccess;
+  std::lock_guard<std::mutex> lock(attr_mutex);
+  return hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, int(kCuLdsBytes));
+}
+
+int HostForm::ensure(Engine& e, size_t doubles, size_t B) {
+  if (out_cap >= doubles && flag_cap >= B) return RPM_OK;
+  HIP_TRY(e, hipStreamSynchronize(e.dev->stream));   // nothing queued still uses what is replaced
+  if (out_cap < doubles) {
+    if (out) HIP_TRY(e, hipFree(out));
+    out = nullptr;
+    out_cap = 0;
+    HIP_TRY(e, hipMalloc(reinterpret_cast<void**>(&out), doubles * sizeof(double)));
+    out_cap = doubles;
+  }
+  if (flag_cap < B) {
+    if (flags) HIP_TRY(e, hipFree(flags));
+    flags = nullptr;
+    if (h_flags) HIP_TRY(e, hipHostFree(h_flags));
+    h_flags = nullptr;
+    flag_cap = 0;
+    HIP_TRY(e, hipMalloc(reinterpret_cast<void**>(&flags), B * sizeof(int)));
+    HIP_TRY(e, hipHostMalloc(reinterpret_cast<void**>(&h_flags), B * sizeof(int), hipHostMallocDefault));
+    flag_cap = B;
+  }
+  return RPM_OK;
+}
+int HostForm::fetch(Engine& e, const int* nonfinite, size_t B) {
+  if (nonfinite) HIP_TRY(e, hipMemcpyAsync(h_flags, flags, B * sizeof(int), hipMemcpyDeviceToHost, e.dev->stream));
+  return RPM_OK;
+}
+int HostForm::finish(Engine& e, int* nonfinite, size_t B) {
+  HIP_TRY(e, hipStreamSynchronize(e.dev->stream));
+  dev_stage_synced(e);
+  if (nonfinite) std::memcpy(nonfinite, h_flags, B * sizeof(int));
+  return RPM_OK;
+}
+void HostForm::release() {
+  if (out) (void)hipFree(out);
+  if (flags) (void)hipFree(flags);
+  if (h_flags) (void)hipHostFree(h_flags);
+  *this = HostForm{};
 }
 
 int dev_sync(Engine& e) {

@@ -16,6 +16,7 @@
 #ifdef RPM_USER_PROBLEM_HEADER
 #include RPM_USER_PROBLEM_HEADER   // defines struct rpm::UserProblem (same interface as the structs of problems.hpp)
 #endif
+#include "rpm_device_restore.hpp"
 #include "rpm_engine.hpp"
 
 namespace rpm {
@@ -141,7 +142,8 @@ struct Device {
 // Host-pointer path (K.chk != nullptr): every thread remembers whether a value it stored was NaN/Inf; the verdicts are
 // ORed into host-visible words (word 0: g, word 1: Jacobian values, word 3: objective gradient) — no separate scan
 // kernel, no extra launch.  An atomic is issued only when something is wrong.
-__device__ __forceinline__ void chk_note(bool& bad, double v) { bad |= !(fabs(v) <= 1.7976931348623157e308); }
+__device__ __forceinline__ bool nonfinite(double v) { return !(fabs(v) <= 1.7976931348623157e308); }   // NaN or Inf: the one predicate
+__device__ __forceinline__ void chk_note(bool& bad, double v) { bad |= nonfinite(v); }
 __device__ __forceinline__ void chk_report(int* chk, bool bad_g, bool bad_j) {
   if (chk == nullptr) return;
   if (bad_g) atomicOr_system(chk, 1);
@@ -200,6 +202,28 @@ inline hipError_t upload(T** dst, const std::vector<T>& src) {
   return s;
 }
 
+
+// ------------------------------------------------------------------------------------------
+// what the entry points of the sweep steps (mesh-error estimate, carry, extraction) share on the host; rpm_device.hip
+int dev_bind(Engine& e);   // device_init on device 0 unless the engine has a device, then that device made current
+constexpr size_t kCuLdsBytes = 160 * 1024;   // LDS of one CU of the MI355X
+// dynamic LDS above the 64 KiB every kernel may have: raises the kernel's hipFuncAttributeMaxDynamicSharedMemorySize to the
+// CU's LDS on the current device (the attribute is per device and only ever raised); below that nothing
+hipError_t raise_dynamic_lds(const void* kernel, size_t bytes);
+// nonfinite[b] = 1 when v[b * len .. + len) holds a NaN or Inf, else 0, for b < B: rpm_flag_kernel (rpm_post_kernels.hip) on `stream`
+void flag_launch(long long len, const double* v, int* nonfinite, int B, hipStream_t stream);
+
+// The host-pointer form of a sweep step: the device block its results land in, the device verdicts and their page-locked
+// mirror.  Grown on demand, never shrunk; what growing replaces is freed once the engine's stream is idle.
+struct HostForm {
+  double* out = nullptr;
+  int *flags = nullptr, *h_flags = nullptr;
+  size_t out_cap = 0, flag_cap = 0;
+  int ensure(Engine& e, size_t doubles, size_t B);
+  int fetch(Engine& e, const int* nonfinite, size_t B);   // queues the verdicts' copy to the mirror (nonfinite NULL: nothing)
+  int finish(Engine& e, int* nonfinite, size_t B);        // synchronises the engine's stream, then hands the verdicts out
+  void release();
+};
 
 void host_path_destroy(Device* d);   // rpm_host_path.hip
 // rpm_device.hip: staging slots (see Device::Stage)

@@ -199,6 +199,21 @@ struct Engine {
   Device* dev = nullptr;
 };
 
+inline bool sharded(const Engine& e) { return e.shard_mode == RPM_SHARD_INTERVALS && e.shard_world > 1; }   // interval sharding: the sweep steps refuse it
+
+// launch planning of the sweep steps (host arithmetic, no device needed).  deal_columns: `cols` independent columns of which at
+// most `most` fit one workgroup, dealt evenly over the fewest workgroups: (workgroups, columns per workgroup); a phase without
+// columns still gets one workgroup.  clamp_tile: a tile of TB instances halved while half of it still holds all B.
+inline std::pair<int, int> deal_columns(int cols, int most) {
+  if (cols <= 0) return {1, 0};
+  const int n_groups = (cols + most - 1) / most;
+  return {n_groups, (cols + n_groups - 1) / n_groups};
+}
+inline int clamp_tile(int TB, int B) {
+  while (TB > 1 && TB / 2 >= B) TB >>= 1;
+  return TB;
+}
+
 // rpm_setup.cpp
 int setup_engine(Engine& e, const rpm_problem_desc* d);  // returns RPM_* code, message in e.err
 void build_tiles(Engine& e, int tile_nodes);

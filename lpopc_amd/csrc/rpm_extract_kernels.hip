@@ -1,16 +1,13 @@
 // rpm_extract_kernels.hip — solution extraction for a whole sweep: Nlp2OpConverter::Nlp2OpControl (Core/Nlp2OPConverter.cpp:13-196)
 // for every phase and every instance of an engine in one launch (two with the NaN/Inf verdicts), nothing but the caller's arrays
 // crossing the call.  The specification is the one-instance route of rpm_post_kernels.hip (rpm_post_spline_kernel + rpm_post_kernel +
-// rpm_post_cost_kernel): per instance b the arithmetic below is that route's on x + b * n and lambda + b * m, operation by
-// operation and sum by sum in the same order (-ffp-contract=off: same order, same bits), with the user functions reading
-// instance b's constants and static parameters.
+// rpm_post_cost_kernel): per instance b the kernels below apply that route's rules (rpm_post_device.hpp, the one copy both
+// routes call) to x + b * n and lambda + b * m, with the user functions reading instance b's constants and static parameters.
 //
 // One instance's block of EB doubles holds the phases one after the other, each phase time (M), state (M nx), control (M nu),
 // costate (M nx), pathmult (M nc), hamiltonian (M), mayer_cost (1), lagrange_cost (1), M = N + 1, every array column-major with
 // M rows: the arrays rpm_nlp2op_control returns.
-#include <mutex>
-
-#include "rpm_device_internal.hpp"
+#include "rpm_post_device.hpp"
 
 namespace rpm {
 
@@ -107,7 +104,7 @@ rpm_extract_kernel(const KParams K, int B, int TB, int fused, long long EB, cons
                    const double* __restrict__ lam, const double* ends_ws, int ET, int ecols, double* lag_ws, int NT,
                    double* __restrict__ out) {
   constexpr int NX = Prob::NX, NU = Prob::NU, NC = Prob::NC;
-  constexpr int NXs = NX > 0 ? NX : 1, NUs = NU > 0 ? NU : 1, NCs = NC > 0 ? NC : 1;
+  constexpr int NXs = NX > 0 ? NX : 1;
   extern __shared__ __align__(16) double extract_sm[];
   const int p = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
   const PhaseDev ph = K.phases[p];
@@ -121,92 +118,37 @@ rpm_extract_kernel(const KParams K, int B, int TB, int fused, long long EB, cons
   if (fused && ncols > 0)
     extract_spline_ends(K, ph, 0, ncols, b0, nb, x, lam, extract_sm + L.pts, extract_sm + L.w, extract_sm + L.cols, L.Np,
                         extract_sm + L.ends);
-  // ---- end-point costates -trans(D(:,N)) * lambda: only the rows of the last mesh interval reach the last column, summed in
-  // ascending row order.  One lane per (instance, state), taken from the top of the workgroup so that they run beside the
-  // spline lanes instead of behind them; inside the node loop the one lane of k = N would walk nx chains of dependent loads.
-  // Parked in `red`, which the cost reduction needs only after the node loop.
+  // ---- end-point costates (post_end_costate).  One lane per (instance, state), taken from the top of the workgroup so that
+  // they run beside the spline lanes instead of behind them; inside the node loop the one lane of k = N would walk nx chains
+  // of dependent loads.  Parked in `red`, which the cost reduction needs only after the node loop.
   static_assert(NX <= 256, "the end-point costates of an instance are parked in its 256 partial sums");
   for (int idx = nt - 1 - tid; idx < nb * NX; idx += nt) {
     const int s = idx % NXs, bi = idx / NXs;
-    const double* lp = lam + size_t(b0 + bi) * K.m + ph.g0;
-    const NodeDev last = K.nodes[ph.node0 + N - 1];
-    double acc = 0.0;
-    for (int r = last.dcol0; r < N; ++r) {
-      const NodeDev nr = K.nodes[ph.node0 + r];
-      acc += K.dvals[nr.drow_off + nr.dlen - 1] * lp[s * N + r];
-    }
-    red[bi * 256 + s] = -acc;
+    red[bi * 256 + s] = post_end_costate(K, ph, lam + size_t(b0 + bi) * K.m + ph.g0, s);
   }
   __syncthreads();
   const long long o_state = M, o_control = o_state + (long long)M * NX, o_costate = o_control + (long long)M * NU,
                   o_pathmult = o_costate + (long long)M * NX, o_ham = o_pathmult + (long long)M * NC, o_mayer = o_ham + M;
 
-  // ---- per node: rpm_post_kernel's body, statement by statement (the end-point costate comes from above) ---------
+  // ---- per node: post_node, the end-point costate coming from above --------------------------------------------
   for (int idx = tid; idx < nb * M; idx += nt) {
     const int k = idx % M, bi = idx / M;
     const size_t b = size_t(b0 + bi);
-    const double* xb = x + b * K.n;
-    const double* lb = lam + b * K.m;   // the base of the instance's own multipliers
-    const double* cb = K.consts + b * K.consts_stride;
     const double* u_end = fused ? extract_sm + L.ends + bi * ncols : ends_ws + b * ET + p * ecols;
-    const double* pm_end = u_end + NU;
     double* lag = fused ? extract_sm + L.lag + bi * L.Np : lag_ws + b * NT + ph.node0;
     double* ob = out + b * EB + base;
-    const double t0 = xb[ph.x_t0], tf = xb[ph.x_t0 + 1];
-    const double tau = k < N ? K.points[ph.node0 + k] : 1.0;
-    const double t = (tf - t0) * (tau + 1) / 2 + t0;                        // :49
-    ob[k] = t;
-    double xs[NXs], us[NUs], cst[NXs];
-#pragma unroll
-    for (int s = 0; s < NX; ++s) {
-      xs[s] = xb[ph.x_state0 + s * M + k];
-      ob[o_state + s * M + k] = xs[s];
-    }
-#pragma unroll
-    for (int j = 0; j < NU; ++j) {
-      us[j] = k < N ? xb[ph.x_control0 + j * N + k] : u_end[j];             // :53-64
-      ob[o_control + j * M + k] = us[j];
-    }
-    const double* lp = lb + ph.g0;                                          // this phase's multipliers, :73
-#pragma unroll
-    for (int s = 0; s < NX; ++s) {
-      cst[s] = k < N ? -((1 / K.weights[ph.node0 + k]) * lp[s * N + k]) : red[bi * 256 + s];   // -(W^-1 lambda), :75-79
-      ob[o_costate + s * M + k] = cst[s];
-    }
-#pragma unroll
-    for (int j = 0; j < NC; ++j)   // lambda WITHOUT the phase offset, exactly as Nlp2OPConverter.cpp:88 reads it
-      ob[o_pathmult + j * M + k] = k < N ? 2 * ((1 / K.weights[ph.node0 + k]) * lb[N * NX + j * N + k]) / (tf - t0) : pm_end[j];
-    double f[NXs], cp[NCs];
-    pf_dae<Prob>(ph.phase_num, t, xs, us, xb + ph.x_t0 + 2, cb, f, cp);
-    const double Lk = pf_lagrange<Prob>(ph.phase_num, t, xs, us, xb + ph.x_t0 + 2, cb);
-    double sum = 0.0;
-#pragma unroll
-    for (int s = 0; s < NX; ++s) {
-      const double term = cst[s] * f[s];
-      sum = (s == 0) ? term : sum + term;
-    }
-    ob[o_ham + k] = Lk + sum;                                               // :146
-    if (k < N) lag[k] = Lk;
-    if (k == 0) {
-      double x0[NXs], xf[NXs];
-#pragma unroll
-      for (int s = 0; s < NX; ++s) {
-        x0[s] = xb[ph.x_state0 + s * M];
-        xf[s] = xb[ph.x_state0 + s * M + N];
-      }
-      ob[o_mayer] = pf_mayer<Prob>(ph.phase_num, t0, x0, tf, xf, xb + ph.x_t0 + 2, cb);
-    }
+    post_node<Prob>(K, ph, k, x + b * K.n, lam + b * K.m, K.consts + b * K.consts_stride, u_end, u_end + NU,
+                    [&](int s) { return red[bi * 256 + s]; },
+                    PostOut{ob, ob + o_state, ob + o_control, ob + o_costate, ob + o_pathmult, ob + o_ham, ob + o_mayer},
+                    k < N ? lag + k : nullptr);
   }
   __syncthreads();
 
-  // ---- lagrange_cost = (tf - t0) (w . L[0..N-1]) / 2 (:134) in rpm_post_cost_kernel's order, per instance: 256 partial sums over
-  // k = t (mod 256) in ascending k, the halving tree 128 .. 1, then the scaling
+  // ---- lagrange_cost per instance: post_cost_partial, the halving tree over every instance's 256 partial sums, post_cost_scaled
   for (int idx = tid; idx < nb * 256; idx += nt) {
     const int t = idx & 255, bi = idx >> 8;
     const double* lag = fused ? extract_sm + L.lag + bi * L.Np : lag_ws + size_t(b0 + bi) * NT + ph.node0;
-    double s = 0.0;
-    for (int k = t; k < N; k += 256) s += K.weights[ph.node0 + k] * lag[k];
-    red[idx] = s;
+    red[idx] = post_cost_partial(N, K.weights + ph.node0, lag, t);
   }
   __syncthreads();
   for (int st = 128; st > 0; st >>= 1) {
@@ -219,29 +161,13 @@ rpm_extract_kernel(const KParams K, int B, int TB, int fused, long long EB, cons
   for (int bi = tid; bi < nb; bi += nt) {
     const size_t b = size_t(b0 + bi);
     const double* xb = x + b * K.n;
-    out[b * EB + base + o_mayer + 1] = (xb[ph.x_t0 + 1] - xb[ph.x_t0]) * red[bi * 256] / 2.0;
+    out[b * EB + base + o_mayer + 1] = post_cost_scaled(xb[ph.x_t0], xb[ph.x_t0 + 1], red[bi * 256]);
   }
-}
-
-// nonfinite[b] = 1 when instance b's finished block holds a NaN or Inf: one workgroup per instance, a block-wide OR, no atomics
-__global__ void __launch_bounds__(256) rpm_extract_flag_kernel(long long EB, const double* __restrict__ out, int* __restrict__ nonfinite) {
-  const double* ob = out + size_t(blockIdx.x) * EB;
-  bool bad = false;
-  for (long long i = threadIdx.x; i < EB; i += blockDim.x) bad |= !(fabs(ob[i]) <= 1.7976931348623157e308);
-  const int any = __syncthreads_or(bad ? 1 : 0);
-  if (threadIdx.x == 0) nonfinite[blockIdx.x] = any ? 1 : 0;
 }
 
 namespace {
 
-constexpr size_t kExtractLdsLimit = 160 * 1024;   // LDS of one CU of the MI355X
 constexpr int kExtractAutoTile = 1;               // the fastest of 1, 2, 4, 8 in profiles/sweep_extract.json (tools/bench_sweep_extract.py)
-
-struct DeviceRestore {   // the calling thread's current device, put back on every exit path
-  int prev = -1;
-  DeviceRestore() { if (hipGetDevice(&prev) != hipSuccess) prev = -1; }
-  ~DeviceRestore() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
 
 struct ExtractPlan {
   int tile_opt = 0, lds_opt = 0;   // the options the plan was made under
@@ -252,15 +178,13 @@ struct ExtractPlan {
 struct ExtractState {
   std::vector<ExtractPlan> plans;
   double *ends_ws = nullptr, *lag_ws = nullptr;   // the split plans' workspace
-  // host-pointer form: the device output block and a page-locked mirror of the verdicts
-  double* out = nullptr;
-  int *out_flag = nullptr, *h_flag = nullptr;
+  HostForm host;   // host-pointer form: the instances' blocks
 };
 
 // doubles the staged arrays of one workgroup may take: what the device offers less the partial sums of the largest tile, or
 // the option when that is smaller
 size_t extract_budget(const Engine& e) {
-  const size_t most = kExtractLdsLimit - 8 * 256 * sizeof(double);
+  const size_t most = kCuLdsBytes - 8 * 256 * sizeof(double);
   return (e.opt_extract_lds > 0 ? std::min(size_t(e.opt_extract_lds), most) : most) / sizeof(double);
 }
 
@@ -269,8 +193,7 @@ size_t extract_budget(const Engine& e) {
 // again halving the tile first, and only a single column that does not fit is refused.
 bool extract_plan(const Engine& e, ExtractPlan* plan, std::vector<ExtractGroup>* groups) {
   const size_t budget = extract_budget(e);
-  int TB0 = e.opt_extract_tile > 0 ? e.opt_extract_tile : kExtractAutoTile;
-  while (TB0 > 1 && TB0 / 2 >= e.n_instances) TB0 >>= 1;
+  const int TB0 = clamp_tile(e.opt_extract_tile > 0 ? e.opt_extract_tile : kExtractAutoTile, e.n_instances);
   ExtractPlan pl;
   pl.tile_opt = e.opt_extract_tile;
   pl.lds_opt = e.opt_extract_lds;
@@ -307,7 +230,7 @@ bool extract_plan(const Engine& e, ExtractPlan* plan, std::vector<ExtractGroup>*
     if (cols == 0) continue;
     int most = 1;   // the most columns of TB instances that fit
     while (most < cols && size_t(ExtractLds(p.N, TB, most + 1, 0, 0).total) <= budget) ++most;
-    const int n_groups = (cols + most - 1) / most, per = (cols + n_groups - 1) / n_groups;
+    const int per = deal_columns(cols, most).second;
     for (int col0 = 0; col0 < cols; col0 += per) {
       const ExtractGroup g{int(ip), col0, std::min(per, cols - col0)};
       pl.lds_spline = std::max(pl.lds_spline, size_t(ExtractLds(p.N, TB, g.ncols, 0, 0).total) * sizeof(double));
@@ -330,9 +253,6 @@ int extract_nodes(const Engine& e) {
   return n;
 }
 
-// hipFuncAttributeMaxDynamicSharedMemorySize is per device and only ever raised here
-std::mutex g_extract_attr_mutex;
-
 ExtractState& extract_state(Device& d) {
   if (!d.extract) d.extract = new ExtractState();
   return *static_cast<ExtractState*>(d.extract);
@@ -341,15 +261,6 @@ ExtractState& extract_state(Device& d) {
 int extract_fail(Engine& e, int code, const std::string& msg) {
   e.err = msg;
   return code;
-}
-
-int extract_device(Engine& e) {
-  if (!e.dev) {
-    const int rc = device_init(e, 0);
-    if (rc) return rc;
-  }
-  HIP_TRY(e, hipSetDevice(e.dev->device_id));
-  return RPM_OK;
 }
 
 int extract_launch(Engine& e, const double* d_x, const double* d_lambda, double* d_out, int* d_nonfinite, hipStream_t st) {
@@ -371,20 +282,13 @@ int extract_launch(Engine& e, const double* d_x, const double* d_lambda, double*
         HIP_TRY(e, hipMalloc(reinterpret_cast<void**>(&es.lag_ws), std::max<size_t>(B * NT, 1) * sizeof(double)));
       }
     }
-    if (std::max(p.lds_node, p.lds_spline) > 64 * 1024) {
-      std::lock_guard<std::mutex> lock(g_extract_attr_mutex);
-      hipError_t s = hipSuccess;
-      if (p.lds_node > 64 * 1024)
-        with_problem(e.problem_id, [&](auto prob) {
-          using P = decltype(prob);
-          s = hipFuncSetAttribute(reinterpret_cast<const void*>(rpm_extract_kernel<P>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  int(kExtractLdsLimit));
-        });
-      if (s == hipSuccess && p.lds_spline > 64 * 1024)
-        s = hipFuncSetAttribute(reinterpret_cast<const void*>(rpm_extract_spline_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                int(kExtractLdsLimit));
-      HIP_TRY(e, s);
-    }
+    hipError_t s = hipSuccess;
+    with_problem(e.problem_id, [&](auto prob) {
+      using P = decltype(prob);
+      s = raise_dynamic_lds(reinterpret_cast<const void*>(rpm_extract_kernel<P>), p.lds_node);
+    });
+    if (s == hipSuccess) s = raise_dynamic_lds(reinterpret_cast<const void*>(rpm_extract_spline_kernel), p.lds_spline);
+    HIP_TRY(e, s);
     es.plans.push_back(p);
     plan = &es.plans.back();
   }
@@ -401,7 +305,7 @@ int extract_launch(Engine& e, const double* d_x, const double* d_lambda, double*
                        EB, d_x, d_lambda, es.ends_ws, ET, extract_ecols(e), es.lag_ws, NT, d_out);
   });
   if (!known) return extract_fail(e, RPM_E_UNSUPPORTED, "nlp2op_batch: this library has no kernels for the engine's problem");
-  if (d_nonfinite) hipLaunchKernelGGL(rpm_extract_flag_kernel, dim3(unsigned(Bi)), dim3(256), 0, st, EB, d_out, d_nonfinite);
+  if (d_nonfinite) flag_launch(EB, d_out, d_nonfinite, Bi, st);
   const hipError_t s = hipGetLastError();
   if (s != hipSuccess) return extract_fail(e, RPM_E_DEVICE, std::string("nlp2op_batch launch: ") + hipGetErrorString(s));
   return RPM_OK;
@@ -414,9 +318,9 @@ void extract_destroy(Device* d) {
   if (!es) return;
   for (ExtractPlan& p : es->plans)
     if (p.d_groups) (void)hipFree(p.d_groups);
-  for (void* p : {static_cast<void*>(es->ends_ws), static_cast<void*>(es->lag_ws), static_cast<void*>(es->out), static_cast<void*>(es->out_flag)})
+  for (double* p : {es->ends_ws, es->lag_ws})
     if (p) (void)hipFree(p);
-  if (es->h_flag) (void)hipHostFree(es->h_flag);
+  es->host.release();
   delete es;
   d->extract = nullptr;
 }
@@ -451,7 +355,7 @@ int extract_group_count(const Engine& e) {
 // every error of the engine's state, decided on the host before a device is touched
 int extract_check(Engine& e) {
   const std::string who = "nlp2op_batch: ";
-  if (e.shard_mode == RPM_SHARD_INTERVALS && e.shard_world > 1) return extract_fail(e, RPM_E_UNSUPPORTED, who + "not with interval sharding");
+  if (sharded(e)) return extract_fail(e, RPM_E_UNSUPPORTED, who + "not with interval sharding");
   for (const PhaseHost& p : e.ph)   // the path multipliers' unshifted index stays inside the instance's own lambda block
     if ((long long)p.N * (p.nx + p.nc) > e.m) return extract_fail(e, RPM_E_UNSUPPORTED, who + "a phase's path multipliers would be read past the instance's multipliers");
   ExtractPlan p;
@@ -469,7 +373,7 @@ int dev_nlp2op_batch(Engine& e, const double* d_x, const double* d_lambda, doubl
   int rc = extract_check(e);
   if (rc) return rc;
   DeviceRestore restore;
-  rc = extract_device(e);
+  rc = dev_bind(e);
   if (rc) return rc;
   return extract_launch(e, d_x, d_lambda, d_out, d_nonfinite, static_cast<hipStream_t>(stream));
 }
@@ -479,31 +383,24 @@ int host_nlp2op_batch(Engine& e, const double* x, const double* lambda, double* 
   int rc = extract_check(e);
   if (rc) return rc;
   DeviceRestore restore;
-  rc = extract_device(e);
+  rc = dev_bind(e);
   if (rc) return rc;
   Device& d = *e.dev;
   ExtractState& es = extract_state(d);
   const size_t B = size_t(e.n_instances);
   long long EB = 0;
   nlp2op_batch_layout(e, 0, nullptr, &EB);
-  if (!es.out) {
-    HIP_TRY(e, hipMalloc(reinterpret_cast<void**>(&es.out), B * size_t(EB) * sizeof(double)));
-    HIP_TRY(e, hipMalloc(reinterpret_cast<void**>(&es.out_flag), B * sizeof(int)));
-    HIP_TRY(e, hipHostMalloc(reinterpret_cast<void**>(&es.h_flag), B * sizeof(int), hipHostMallocDefault));
-  }
+  rc = es.host.ensure(e, B * size_t(EB), B);
+  if (rc) return rc;
   host_new_x(e);   // d_x is about to hold other values than the callbacks' last x
   rc = dev_upload(e, d.d_x, x, B * e.n, STAGE_X);
   if (rc == RPM_OK) rc = dev_upload(e, d.d_lambda, lambda, B * e.m, STAGE_LAMBDA);
   if (rc) return rc;
-  rc = extract_launch(e, d.d_x, d.d_lambda, es.out, nonfinite ? es.out_flag : nullptr, d.stream);
+  rc = extract_launch(e, d.d_x, d.d_lambda, es.host.out, nonfinite ? es.host.flags : nullptr, d.stream);
+  if (rc == RPM_OK) rc = es.host.fetch(e, nonfinite, B);
+  if (rc == RPM_OK) rc = dev_download(e, out, es.host.out, B * size_t(EB), STAGE_G);
   if (rc) return rc;
-  if (nonfinite) HIP_TRY(e, hipMemcpyAsync(es.h_flag, es.out_flag, B * sizeof(int), hipMemcpyDeviceToHost, d.stream));
-  rc = dev_download(e, out, es.out, B * size_t(EB), STAGE_G);
-  if (rc) return rc;
-  HIP_TRY(e, hipStreamSynchronize(d.stream));
-  dev_stage_synced(e);
-  if (nonfinite) std::memcpy(nonfinite, es.h_flag, B * sizeof(int));
-  return RPM_OK;
+  return es.host.finish(e, nonfinite, B);
 }
 
 }  // namespace rpm

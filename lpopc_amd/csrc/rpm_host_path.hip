@@ -170,7 +170,7 @@ static int delta_setup(Engine& e) {
   if (h.d_runs) return RPM_OK;
   const long long nnz = e.nnz_jac, B = e.n_instances;
   std::vector<std::pair<long long, long long>> ranges;   // owned ranges of one instance
-  if (e.shard_mode == RPM_SHARD_INTERVALS && e.shard_world > 1) {
+  if (sharded(e)) {
     for (const rpm_segment& s : shard_segments(e, 1, e.shard_rank, nullptr)) ranges.emplace_back(s.off, s.len);
   } else {
     ranges.emplace_back(0, nnz);
@@ -348,7 +348,7 @@ static int enqueue_values(Engine& e, double* values, bool* delta) {
     *delta = true;
     return delta_enqueue(e, values, static_cast<double*>(va));
   }
-  if (e.shard_mode == RPM_SHARD_INTERVALS && e.shard_world > 1) {
+  if (sharded(e)) {
     e.err = "host-pointer Jacobian delivery of an interval-sharded engine needs option delta_values = 1 (each rank stores only its own runs)";
     return RPM_E_UNSUPPORTED;
   }

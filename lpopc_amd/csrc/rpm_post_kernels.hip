@@ -1,6 +1,7 @@
-// rpm_post_kernels.hip — the steps after the NLP solve: solution extraction (Nlp2OpConverter) and the mesh-error
-// estimate (SolutionErrorChecker), kernels and host drivers.  Once per mesh, not on the metric.
-#include "rpm_device_internal.hpp"
+// rpm_post_kernels.hip — the steps after the NLP solve: solution extraction (Nlp2OpConverter) for one instance and the
+// mesh-error estimate (SolutionErrorChecker) for one instance and for a whole sweep, kernels and host drivers.  Once per mesh,
+// not on the metric.  The kernels here choose the work split; the rules they apply are in rpm_post_device.hpp, one copy each.
+#include "rpm_post_device.hpp"
 
 namespace rpm {
 
@@ -17,8 +18,7 @@ __global__ void rpm_mesh_err_kernel(const KParams K, int phase, const double* __
                                     const int* __restrict__ hit_c, const double* __restrict__ A,
                                     const double* __restrict__ ttem, int rows, double* __restrict__ fine_state,
                                     double* __restrict__ integ) {
-  constexpr int NX = Prob::NX, NU = Prob::NU, NC = Prob::NC;
-  constexpr int NXs = NX > 0 ? NX : 1, NUs = NU > 0 ? NU : 1, NCs = NC > 0 ? NC : 1;
+  constexpr int NX = Prob::NX, NU = Prob::NU;
   extern __shared__ double mesh_sm[];
   const MeshIvDev v = ivs[blockIdx.x];
   const int n = v.n, n1 = n + 1;
@@ -28,55 +28,24 @@ __global__ void rpm_mesh_err_kernel(const KParams K, int phase, const double* __
   const PhaseDev ph = K.phases[phase];
   const int N = ph.N, M = N + 1;
   const double t0 = x[ph.x_t0];
-  const double tf = (x[ph.x_t0 + 1] - t0) * (1.0 + 1) / 2 + t0;   // result->time's last entry, Nlp2OPConverter.cpp:58
+  const double tf = post_time(t0, x[ph.x_t0 + 1], 1.0);   // result->time's last entry
   for (int idx = threadIdx.x; idx < n1 * NX; idx += blockDim.x) {
     const int q = idx % n1, s = idx / n1;
-    const double* col = x + ph.x_state0 + s * M + v.istart;
-    const int hit = hit_s[v.q0 + q];
-    double val;
-    if (hit >= 0) {
-      val = col[hit];
-    } else {
-      double acc = 0.0;
-      for (int j = 0; j < n1; ++j) acc += Hs[v.hs + q + j * n1] * col[j];
-      val = acc / Ss[v.q0 + q];
-    }
+    const double val = mesh_interp(hit_s[v.q0 + q], Hs + v.hs + q, n1, n1, x + ph.x_state0 + s * M + v.istart, Ss + v.q0 + q);
     Xs[q * NX + s] = val;
     fine_state[(v.r0 + q) + size_t(s) * rows] = val;
   }
   for (int idx = threadIdx.x; idx < n1 * NU; idx += blockDim.x) {
     const int q = idx % n1, j = idx / n1;
-    const double* col = x + ph.x_control0 + j * N + v.istart;
-    const int hit = hit_c[v.q0 + q];
-    double val;
-    if (hit >= 0) {
-      val = col[hit];
-    } else {
-      double acc = 0.0;
-      for (int c = 0; c < n; ++c) acc += Hc[v.hc + q + c * n1] * col[c];
-      val = acc / Sc[v.q0 + q];
-    }
-    Us[q * NU + j] = val;
+    Us[q * NU + j] = mesh_interp(hit_c[v.q0 + q], Hc + v.hc + q, n1, n, x + ph.x_control0 + j * N + v.istart, Sc + v.q0 + q);
   }
   __syncthreads();
-  const double half = (tf - t0) / 2;
-  for (int q = threadIdx.x; q < n1; q += blockDim.x) {
-    double xs[NXs], us[NUs], f[NXs], cp[NCs];
-#pragma unroll
-    for (int s = 0; s < NX; ++s) xs[s] = Xs[q * NX + s];
-#pragma unroll
-    for (int j = 0; j < NU; ++j) us[j] = Us[q * NU + j];
-    const double t = half * ttem[v.q0 + q] + half;   // t0 is not added, LpSolutionError.cpp:124
-    pf_dae<Prob>(ph.phase_num, t, xs, us, x + ph.x_t0 + 2, K.consts, f, cp);
-#pragma unroll
-    for (int s = 0; s < NX; ++s) Fs[q * NX + s] = f[s] * ((tf - t0) / 2.0);
-  }
+  for (int q = threadIdx.x; q < n1; q += blockDim.x)
+    mesh_dynamics<Prob>(ph, t0, tf, ttem[v.q0 + q], Xs + q * NX, Us + q * NU, x + ph.x_t0 + 2, K.consts, Fs + q * NX);
   __syncthreads();
   for (int idx = threadIdx.x; idx < n1 * NX; idx += blockDim.x) {
     const int r = idx % n1, s = idx / n1;
-    double acc = 0.0;
-    for (int c = 0; c < n1; ++c) acc += A[v.a + r + c * n1] * Fs[c * NX + s];
-    integ[(1 + v.r0 + r) + size_t(s) * rows] = (0.0 + 1.0 * Xs[s]) + acc;
+    integ[(1 + v.r0 + r) + size_t(s) * rows] = mesh_integrate(A + v.a + r, n1, Fs, NX, s, Xs);
   }
   if (blockIdx.x == 0)
     for (int s = threadIdx.x; s < NX; s += blockDim.x) integ[size_t(s) * rows] = Xs[s];
@@ -85,7 +54,7 @@ __global__ void rpm_mesh_err_kernel(const KParams K, int phase, const double* __
       fine_state[(rows - 1) + size_t(s) * rows] = x[ph.x_state0 + s * M + N];
 }
 
-// relative_error(:, s) = |integrated - interpolated| / (1 + max(interpolated(:, s))), one workgroup per state (:148-157)
+// relative_error(:, s), one workgroup per state: the column's maximum, then mesh_rel_entry
 __global__ void rpm_mesh_rel_kernel(int rows, const double* __restrict__ fine_state, const double* __restrict__ integ,
                                     double* __restrict__ rel) {
   __shared__ double red[256];
@@ -100,7 +69,7 @@ __global__ void rpm_mesh_rel_kernel(int rows, const double* __restrict__ fine_st
   }
   const double den = 1 + red[0];
   for (int r = threadIdx.x; r < rows; r += blockDim.x)
-    rel[r + size_t(blockIdx.x) * rows] = fabs(integ[r + size_t(blockIdx.x) * rows] - col[r]) / den;
+    rel[r + size_t(blockIdx.x) * rows] = mesh_rel_entry(integ[r + size_t(blockIdx.x) * rows], col[r], den);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -126,95 +95,47 @@ __global__ void rpm_post_kernel(const KParams K, int phase, const double* __rest
                                 double* __restrict__ o_time, double* __restrict__ o_state, double* __restrict__ o_control,
                                 double* __restrict__ o_costate, double* __restrict__ o_pathmult,
                                 double* __restrict__ o_ham, double* __restrict__ o_lag, double* __restrict__ o_mayer) {
-  constexpr int NX = Prob::NX, NU = Prob::NU, NC = Prob::NC;
-  constexpr int NXs = NX > 0 ? NX : 1, NUs = NU > 0 ? NU : 1, NCs = NC > 0 ? NC : 1;
   const PhaseDev ph = K.phases[phase];
-  const int N = ph.N, M = N + 1;
   const int k = blockIdx.x * blockDim.x + threadIdx.x;
-  if (k >= M) return;
-  const double t0 = x[ph.x_t0], tf = x[ph.x_t0 + 1];
-  const double tau = k < N ? K.points[ph.node0 + k] : 1.0;
-  const double t = (tf - t0) * (tau + 1) / 2 + t0;                       // :49
-  o_time[k] = t;
-  double xs[NXs], us[NUs], cst[NXs];
-#pragma unroll
-  for (int s = 0; s < NX; ++s) {
-    xs[s] = x[ph.x_state0 + s * M + k];
-    o_state[s * M + k] = xs[s];
-  }
-#pragma unroll
-  for (int j = 0; j < NU; ++j) {
-    us[j] = k < N ? x[ph.x_control0 + j * N + k] : u_end[j];             // :53-64
-    o_control[j * M + k] = us[j];
-  }
-  const double* lp = lam + ph.g0;                                       // this phase's multipliers, :73
-#pragma unroll
-  for (int s = 0; s < NX; ++s) {
-    if (k < N) {
-      cst[s] = -((1 / K.weights[ph.node0 + k]) * lp[s * N + k]);         // -(W^-1 lambda), :75-79
-    } else {
-      // -trans(D(:,N)) * lambda: only the rows of the last mesh interval reach the last column
-      const NodeDev last = K.nodes[ph.node0 + N - 1];
-      double acc = 0.0;
-      for (int r = last.dcol0; r < N; ++r) {
-        const NodeDev nr = K.nodes[ph.node0 + r];
-        acc += K.dvals[nr.drow_off + nr.dlen - 1] * lp[s * N + r];
-      }
-      cst[s] = -acc;
-    }
-    o_costate[s * M + k] = cst[s];
-  }
-#pragma unroll
-  for (int j = 0; j < NC; ++j)   // lambda WITHOUT the phase offset, exactly as Nlp2OPConverter.cpp:88 reads it
-    o_pathmult[j * M + k] = k < N ? 2 * ((1 / K.weights[ph.node0 + k]) * lam[N * NX + j * N + k]) / (tf - t0) : pm_end[j];
-  double f[NXs], cp[NCs];
-  pf_dae<Prob>(ph.phase_num, t, xs, us, x + ph.x_t0 + 2, K.consts, f, cp);
-  const double L = pf_lagrange<Prob>(ph.phase_num, t, xs, us, x + ph.x_t0 + 2, K.consts);
-  double sum = 0.0;
-#pragma unroll
-  for (int s = 0; s < NX; ++s) {
-    const double term = cst[s] * f[s];
-    sum = (s == 0) ? term : sum + term;
-  }
-  o_ham[k] = L + sum;                                                    // :146
-  o_lag[k] = L;
-  if (k == 0) {
-    double x0[NXs], xf[NXs];
-#pragma unroll
-    for (int s = 0; s < NX; ++s) {
-      x0[s] = x[ph.x_state0 + s * M];
-      xf[s] = x[ph.x_state0 + s * M + N];
-    }
-    o_mayer[0] = pf_mayer<Prob>(ph.phase_num, t0, x0, tf, xf, x + ph.x_t0 + 2, K.consts);
-  }
+  if (k > ph.N) return;
+  const double* lp = lam + ph.g0;
+  post_node<Prob>(K, ph, k, x, lam, K.consts, u_end, pm_end, [&](int s) { return post_end_costate(K, ph, lp, s); },
+                  PostOut{o_time, o_state, o_control, o_costate, o_pathmult, o_ham, o_mayer}, o_lag + k);
 }
 
-// lagrange_cost = (tf-t0) * (w . L[0..N-1]) / 2  (:134), fixed-tree sum
+// lagrange_cost of one instance: post_cost_partial, the halving tree, post_cost_scaled
 __global__ void rpm_post_cost_kernel(const KParams K, int phase, const double* __restrict__ x,
                                      const double* __restrict__ lag, double* __restrict__ out) {
   __shared__ double red[256];
   const PhaseDev ph = K.phases[phase];
   const int tid = threadIdx.x;
-  double s = 0.0;
-  for (int k = tid; k < ph.N; k += 256) s += K.weights[ph.node0 + k] * lag[k];
-  red[tid] = s;
+  red[tid] = post_cost_partial(ph.N, K.weights + ph.node0, lag, tid);
   __syncthreads();
   for (int st = 128; st > 0; st >>= 1) {
     if (tid < st) red[tid] += red[tid + st];
     __syncthreads();
   }
-  if (tid == 0) out[0] = (x[ph.x_t0 + 1] - x[ph.x_t0]) * red[0] / 2.0;
+  if (tid == 0) out[0] = post_cost_scaled(x[ph.x_t0], x[ph.x_t0 + 1], red[0]);
+}
+
+// nonfinite[b] = 1 when block b of `len` doubles holds a NaN or Inf, else 0: one workgroup per block, a block-wide OR, no atomics
+__global__ void __launch_bounds__(256) rpm_flag_kernel(long long len, const double* __restrict__ v, int* __restrict__ verdicts) {
+  const double* vb = v + size_t(blockIdx.x) * len;
+  bool bad = false;
+  for (long long i = threadIdx.x; i < len; i += blockDim.x) bad |= nonfinite(vb[i]);
+  const int any = __syncthreads_or(bad ? 1 : 0);
+  if (threadIdx.x == 0) verdicts[blockIdx.x] = any ? 1 : 0;
+}
+void flag_launch(long long len, const double* v, int* nonfinite, int B, hipStream_t stream) {
+  hipLaunchKernelGGL(rpm_flag_kernel, dim3(unsigned(B)), dim3(256), 0, stream, len, v, nonfinite);
 }
 
 // Nlp2OpControl for one phase: host x / lambda in, (N+1)-row column-major host arrays out (any may be NULL)
 int dev_nlp2op(Engine& e, int phase, const double* x, const double* lambda, double* time, double* state, double* control,
                double* costate, double* pathmult, double* hamiltonian, double* mayer_cost, double* lagrange_cost) {
-  if (!e.dev) {
-    int rc = device_init(e, 0);
-    if (rc) return rc;
-  }
+  int rc = dev_bind(e);
+  if (rc) return rc;
   Device& d = *e.dev;
-  HIP_TRY(e, hipSetDevice(d.device_id));
   const PhaseHost& p = e.ph[phase];
   const int N = p.N, M = N + 1, nx = p.nx, nu = p.nu, nc = p.nc;
   const size_t out_doubles = size_t(M) * (3 + 2 * nx + nu + nc) + 8 + nu + nc;
@@ -230,7 +151,7 @@ int dev_nlp2op(Engine& e, int phase, const double* x, const double* lambda, doub
   double* o_scal = o_lag + M;          // [0] mayer, [1] lagrange cost
   double* u_end = o_scal + 8;
   double* pm_end = u_end + nu;
-  int rc = dev_upload(e, d.d_x, x, size_t(e.n), STAGE_X);
+  rc = dev_upload(e, d.d_x, x, size_t(e.n), STAGE_X);
   if (rc == RPM_OK) rc = dev_upload(e, d.d_lambda, lambda, size_t(e.m), STAGE_LAMBDA);
   hipError_t s = hipSuccess;
   if (rc == RPM_OK) {
@@ -274,12 +195,9 @@ int dev_nlp2op(Engine& e, int phase, const double* x, const double* lambda, doub
 
 // CheckSolutionDiffError for one phase: host x in, relative_error ((N + K + 1) x nx, column-major) out
 int dev_solution_error(Engine& e, int phase, const double* x, double* rel_err) {
-  if (!e.dev) {
-    int rc = device_init(e, 0);
-    if (rc) return rc;
-  }
+  int rc = dev_bind(e);
+  if (rc) return rc;
   Device& d = *e.dev;
-  HIP_TRY(e, hipSetDevice(d.device_id));
   const PhaseHost& p = e.ph[phase];
   if (e.mesh_err.size() != e.ph.size()) e.mesh_err.assign(e.ph.size(), MeshErrTables());
   MeshErrTables& t = e.mesh_err[phase];
@@ -324,7 +242,7 @@ int dev_solution_error(Engine& e, int phase, const double* x, double* rel_err) {
   put(d_hit_s, t.hit_s.data(), t.hit_s.size() * sizeof(int));
   put(d_hit_c, t.hit_c.data(), t.hit_c.size() * sizeof(int));
   put(d_iv, t.iv.data(), K * sizeof(MeshIvDev));
-  int rc = (s == hipSuccess) ? dev_upload(e, d.d_x, x, size_t(e.n), STAGE_X) : RPM_OK;
+  rc = (s == hipSuccess) ? dev_upload(e, d.d_x, x, size_t(e.n), STAGE_X) : RPM_OK;
   if (rc == RPM_OK && s == hipSuccess) {
     hipStream_t st = d.stream;
     with_problem(e.problem_id, [&](auto prob) {
@@ -349,8 +267,8 @@ int dev_solution_error(Engine& e, int phase, const double* x, double* rel_err) {
 // ------------------------------------------------------------------------------------------
 // The mesh-error estimate of a whole sweep: every phase and every instance of the engine in three launches, nothing but
 // the caller's arrays crossing the call.  Per instance b the arithmetic is that of rpm_mesh_err_kernel + rpm_mesh_rel_kernel
-// on x + b * n, sum by sum in the same order (-ffp-contract=off: same order, same bits), with the dynamics reading instance
-// b's constants and static parameters.  The interpolation / integration tables of all phases sit in one device block that
+// on x + b * n, the same mesh_* rules of rpm_post_device.hpp on other bases, with the dynamics reading instance b's constants
+// and static parameters.  The interpolation / integration tables of all phases sit in one device block that
 // lives as long as the engine's other tables (Device::mesh_batch).
 struct MeshIvBatch {   // one mesh interval of any phase: MeshIvDev with offsets into the engine-wide tables
   int n, istart, r0, q0, hs, hc, a;
@@ -369,8 +287,8 @@ __global__ void rpm_mesh_err_batch_kernel(const KParams K, int B, int TB, int st
                                           const int* ghit_s, const double* gHc, const double* gSc, const int* ghit_c,
                                           const double* gA, const double* gtt, double* __restrict__ fine_state,
                                           double* __restrict__ integ, int* __restrict__ nonfinite) {
-  constexpr int NX = Prob::NX, NU = Prob::NU, NC = Prob::NC;
-  constexpr int NXs = NX > 0 ? NX : 1, NUs = NU > 0 ? NU : 1, NCs = NC > 0 ? NC : 1;
+  constexpr int NX = Prob::NX, NU = Prob::NU;
+  constexpr int NXs = NX > 0 ? NX : 1, NUs = NU > 0 ? NU : 1;
   extern __shared__ __align__(16) double mesh_bsm[];
   const MeshIvBatch v = ivs[blockIdx.x];
   const int n = v.n, n1 = n + 1;
@@ -412,32 +330,14 @@ __global__ void rpm_mesh_err_batch_kernel(const KParams K, int B, int TB, int st
   for (int idx = threadIdx.x; idx < nb * n1 * NX; idx += blockDim.x) {
     const int q = idx % n1, s = (idx / n1) % NXs, bi = idx / (n1 * NXs);
     const size_t b = size_t(b0 + bi);
-    const double* col = x + b * K.n + ph.x_state0 + s * M + v.istart;
-    const int hit = hit_s[q];
-    double val;
-    if (hit >= 0) {
-      val = col[hit];
-    } else {
-      double acc = 0.0;
-      for (int j = 0; j < n1; ++j) acc += Hs[q + j * n1] * col[j];
-      val = acc / Ss[q];
-    }
+    const double val = mesh_interp(hit_s[q], Hs + q, n1, n1, x + b * K.n + ph.x_state0 + s * M + v.istart, Ss + q);
     inst[bi * per + q * NX + s] = val;
     fine_state[b * RT + v.base + (v.r0 + q) + size_t(s) * rows] = val;
   }
   for (int idx = threadIdx.x; idx < nb * n1 * NU; idx += blockDim.x) {
     const int q = idx % n1, j = (idx / n1) % NUs, bi = idx / (n1 * NUs);
-    const double* col = x + size_t(b0 + bi) * K.n + ph.x_control0 + j * N + v.istart;
-    const int hit = hit_c[q];
-    double val;
-    if (hit >= 0) {
-      val = col[hit];
-    } else {
-      double acc = 0.0;
-      for (int c = 0; c < n; ++c) acc += Hc[q + c * n1] * col[c];
-      val = acc / Sc[q];
-    }
-    inst[bi * per + n1 * NX + q * NU + j] = val;
+    inst[bi * per + n1 * NX + q * NU + j] =
+        mesh_interp(hit_c[q], Hc + q, n1, n, x + size_t(b0 + bi) * K.n + ph.x_control0 + j * N + v.istart, Sc + q);
   }
   __syncthreads();
   for (int idx = threadIdx.x; idx < nb * n1; idx += blockDim.x) {
@@ -447,26 +347,15 @@ __global__ void rpm_mesh_err_batch_kernel(const KParams K, int B, int TB, int st
     const double* Us = Xs + n1 * NX;
     double* Fs = inst + bi * per + n1 * (NX + NU);
     const double t0 = xb[ph.x_t0];
-    const double tf = (xb[ph.x_t0 + 1] - t0) * (1.0 + 1) / 2 + t0;   // result->time's last entry, Nlp2OPConverter.cpp:58
-    const double half = (tf - t0) / 2;
-    double xs[NXs], us[NUs], f[NXs], cp[NCs];
-#pragma unroll
-    for (int s = 0; s < NX; ++s) xs[s] = Xs[q * NX + s];
-#pragma unroll
-    for (int j = 0; j < NU; ++j) us[j] = Us[q * NU + j];
-    const double t = half * tt[q] + half;   // t0 is not added, LpSolutionError.cpp:124
-    pf_dae<Prob>(ph.phase_num, t, xs, us, xb + ph.x_t0 + 2, K.consts + size_t(b0 + bi) * K.consts_stride, f, cp);
-#pragma unroll
-    for (int s = 0; s < NX; ++s) Fs[q * NX + s] = f[s] * ((tf - t0) / 2.0);
+    mesh_dynamics<Prob>(ph, t0, post_time(t0, xb[ph.x_t0 + 1], 1.0), tt[q], Xs + q * NX, Us + q * NU, xb + ph.x_t0 + 2,
+                        K.consts + size_t(b0 + bi) * K.consts_stride, Fs + q * NX);
   }
   __syncthreads();
   for (int idx = threadIdx.x; idx < nb * n1 * NX; idx += blockDim.x) {
     const int r = idx % n1, s = (idx / n1) % NXs, bi = idx / (n1 * NXs);
     const double* Xs = inst + bi * per;
     const double* Fs = Xs + n1 * (NX + NU);
-    double acc = 0.0;
-    for (int c = 0; c < n1; ++c) acc += A[r + c * n1] * Fs[c * NX + s];
-    integ[size_t(b0 + bi) * RT + v.base + (1 + v.r0 + r) + size_t(s) * rows] = (0.0 + 1.0 * Xs[s]) + acc;
+    integ[size_t(b0 + bi) * RT + v.base + (1 + v.r0 + r) + size_t(s) * rows] = mesh_integrate(A + r, n1, Fs, NX, s, Xs);
   }
   if (v.first)
     for (int idx = threadIdx.x; idx < nb * NX; idx += blockDim.x) {
@@ -488,7 +377,7 @@ __global__ void rpm_mesh_err_batch_kernel(const KParams K, int B, int TB, int st
 __global__ void rpm_mesh_rel_batch_kernel(const PhaseDev* __restrict__ phases, const MeshIvBatch* __restrict__ ivs,
                                           const int* __restrict__ ph_iv0, long long RT, int KT, const double* __restrict__ fine_state,
                                           const double* __restrict__ integ, double* __restrict__ rel,
-                                          double* __restrict__ interval_error, int* nonfinite, int nx_max, int keep) {
+                                          double* __restrict__ interval_error, int* verdicts, int nx_max, int keep) {
   extern __shared__ __align__(16) double mesh_den[];   // [nx_max + 2] denominators, then (keep) the phase's matrix
   double* kept = mesh_den + nx_max + 2;
   const int p = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6, waves = blockDim.x >> 6;
@@ -507,12 +396,12 @@ __global__ void rpm_mesh_rel_batch_kernel(const PhaseDev* __restrict__ phases, c
   __syncthreads();
   bool bad = false;
   for (int idx = threadIdx.x; idx < rows * nx; idx += blockDim.x) {
-    const double val = fabs(in[idx] - fs[idx]) / mesh_den[idx / rows];
+    const double val = mesh_rel_entry(in[idx], fs[idx], mesh_den[idx / rows]);
     if (rel) rel[b * RT + ivs[iv0].base + idx] = val;
     if (keep) kept[idx] = val;
-    bad |= !(fabs(val) <= 1.7976931348623157e308);
+    bad |= nonfinite(val);
   }
-  if (nonfinite && bad) atomicOr(nonfinite + b, 1);
+  if (verdicts && bad) atomicOr(verdicts + b, 1);
   if (keep) __syncthreads();
   if (interval_error)
     for (int k = threadIdx.x; k < Kp; k += blockDim.x) {
@@ -520,7 +409,7 @@ __global__ void rpm_mesh_rel_batch_kernel(const PhaseDev* __restrict__ phases, c
       const int istart = v.r0, ifinish = v.r0 + v.n + 1;
       // the chain is sequential: it reads the matrix from LDS when it fits there, else recomputes the entries (same bits)
       auto at = [&](int r, int s) {
-        return keep ? kept[r + size_t(s) * rows] : fabs(in[r + size_t(s) * rows] - fs[r + size_t(s) * rows]) / mesh_den[s];
+        return keep ? kept[r + size_t(s) * rows] : mesh_rel_entry(in[r + size_t(s) * rows], fs[r + size_t(s) * rows], mesh_den[s]);
       };
       double emax = at(istart, 0);
       for (int s = 0; s < nx; ++s)
@@ -575,18 +464,17 @@ struct MeshBatch {
   long long RT = 0;
   size_t tab_doubles = 0, inst_doubles = 0;   // LDS of the largest interval: its tables / one instance's arrays
   size_t block_max = 0;                       // doubles of the largest phase's rows x nx matrix
-  // host-pointer form: device outputs and a page-locked block for the two int arrays (mask in, verdicts out)
-  char* out = nullptr;
-  double *o_iv, *o_max;
-  int *o_flag, *o_mask, *h_ints = nullptr;
+  HostForm host;                           // host-pointer form: interval errors (B x KT), then the maximum (RT); the verdicts
+  int *o_mask = nullptr, *h_mask = nullptr;   // its instance mask on the device and the page-locked block it is uploaded from
 };
 
 void mesh_batch_destroy(Device* d) {
   MeshBatch* mb = static_cast<MeshBatch*>(d->mesh_batch);
   if (!mb) return;
   if (mb->block) (void)hipFree(mb->block);
-  if (mb->out) (void)hipFree(mb->out);
-  if (mb->h_ints) (void)hipHostFree(mb->h_ints);
+  mb->host.release();
+  if (mb->o_mask) (void)hipFree(mb->o_mask);
+  if (mb->h_mask) (void)hipHostFree(mb->h_mask);
   delete mb;
   d->mesh_batch = nullptr;
 }
@@ -606,12 +494,6 @@ namespace {
 
 constexpr size_t kMeshLdsLimit = 60 * 1024;
 constexpr int kMaxChunks = 32;   // rpm_mesh_max_kernel's first pass over a large sweep
-
-struct DeviceRestore {   // the calling thread's current device, put back on every exit path
-  int prev = -1;
-  DeviceRestore() { if (hipGetDevice(&prev) != hipSuccess) prev = -1; }
-  ~DeviceRestore() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
 
 // first use on an engine: tables of all phases into one device block, workspace behind them (the only allocation and the
 // only blocking copies of the batched estimate)
@@ -706,14 +588,10 @@ int mesh_batch_setup(Engine& e) {
 int dev_solution_error_batch(Engine& e, const double* d_x, const int* d_mask, double* d_interval_error, double* d_rel_err_max,
                              double* d_rel_err, int* d_nonfinite, void* stream) {
   DeviceRestore restore;
-  if (!e.dev) {
-    int rc = device_init(e, 0);
-    if (rc) return rc;
-  }
-  Device& d = *e.dev;
-  HIP_TRY(e, hipSetDevice(d.device_id));
-  int rc = mesh_batch_setup(e);
+  int rc = dev_bind(e);
+  if (rc == RPM_OK) rc = mesh_batch_setup(e);
   if (rc) return rc;
+  Device& d = *e.dev;
   const MeshBatch& m = *static_cast<MeshBatch*>(d.mesh_batch);
   const int B = e.n_instances;
   // instances per workgroup: the largest of 8, 4, 2, 1 (or the option) whose arrays fit next to the staged tables
@@ -721,7 +599,7 @@ int dev_solution_error_batch(Engine& e, const double* d_x, const int* d_mask, do
   const int stage = (m.tab_doubles + m.inst_doubles) * sizeof(double) <= kMeshLdsLimit ? 1 : 0;
   const size_t tab = stage ? m.tab_doubles : 0;
   while (TB > 1 && (tab + size_t(TB) * m.inst_doubles) * sizeof(double) > kMeshLdsLimit) TB >>= 1;
-  while (TB > 1 && TB / 2 >= B) TB >>= 1;
+  TB = clamp_tile(TB, B);
   const size_t lds = (tab + size_t(TB) * m.inst_doubles) * sizeof(double);
   hipStream_t st = static_cast<hipStream_t>(stream);
   double* rel = d_rel_err ? d_rel_err : (d_rel_err_max ? m.rel : nullptr);
@@ -759,43 +637,35 @@ int dev_solution_error_batch(Engine& e, const double* d_x, const int* d_mask, do
 int host_solution_error_batch(Engine& e, const double* x, const int* mask, double* interval_error, double* rel_err_max,
                               double* rel_err, int* nonfinite) {
   DeviceRestore restore;
-  if (!e.dev) {
-    int rc = device_init(e, 0);
-    if (rc) return rc;
-  }
-  Device& d = *e.dev;
-  HIP_TRY(e, hipSetDevice(d.device_id));
-  int rc = mesh_batch_setup(e);
+  int rc = dev_bind(e);
+  if (rc == RPM_OK) rc = mesh_batch_setup(e);
   if (rc) return rc;
+  Device& d = *e.dev;
   MeshBatch& m = *static_cast<MeshBatch*>(d.mesh_batch);
   const size_t B = size_t(e.n_instances);
-  if (!m.out) {
-    HIP_TRY(e, hipMalloc(reinterpret_cast<void**>(&m.out), (B * m.KT + size_t(m.RT)) * sizeof(double) + 2 * B * sizeof(int)));
-    m.o_iv = reinterpret_cast<double*>(m.out);
-    m.o_max = m.o_iv + B * m.KT;
-    m.o_flag = reinterpret_cast<int*>(m.o_max + m.RT);
-    m.o_mask = m.o_flag + B;
-    HIP_TRY(e, hipHostMalloc(reinterpret_cast<void**>(&m.h_ints), 2 * B * sizeof(int), hipHostMallocDefault));
+  rc = m.host.ensure(e, B * m.KT + size_t(m.RT), B);
+  if (rc) return rc;
+  double *o_iv = m.host.out, *o_max = o_iv + B * m.KT;
+  if (mask && !m.o_mask) {   // sized once, unlike `host`: an engine's n_instances never changes
+    HIP_TRY(e, hipMalloc(reinterpret_cast<void**>(&m.o_mask), B * sizeof(int)));
+    HIP_TRY(e, hipHostMalloc(reinterpret_cast<void**>(&m.h_mask), B * sizeof(int), hipHostMallocDefault));
   }
   rc = dev_upload(e, d.d_x, x, B * e.n, STAGE_X);
   if (rc) return rc;
   if (mask) {
-    std::memcpy(m.h_ints, mask, B * sizeof(int));
-    HIP_TRY(e, hipMemcpyAsync(m.o_mask, m.h_ints, B * sizeof(int), hipMemcpyHostToDevice, d.stream));
+    std::memcpy(m.h_mask, mask, B * sizeof(int));
+    HIP_TRY(e, hipMemcpyAsync(m.o_mask, m.h_mask, B * sizeof(int), hipMemcpyHostToDevice, d.stream));
   }
-  rc = dev_solution_error_batch(e, d.d_x, mask ? m.o_mask : nullptr, interval_error ? m.o_iv : nullptr,
-                                rel_err_max ? m.o_max : nullptr, rel_err ? m.rel : nullptr, nonfinite ? m.o_flag : nullptr, d.stream);
+  rc = dev_solution_error_batch(e, d.d_x, mask ? m.o_mask : nullptr, interval_error ? o_iv : nullptr,
+                                rel_err_max ? o_max : nullptr, rel_err ? m.rel : nullptr, nonfinite ? m.host.flags : nullptr, d.stream);
   if (rc) return rc;
-  HIP_TRY(e, hipSetDevice(d.device_id));
-  if (nonfinite) HIP_TRY(e, hipMemcpyAsync(m.h_ints + B, m.o_flag, B * sizeof(int), hipMemcpyDeviceToHost, d.stream));
-  if (interval_error) rc = dev_download(e, interval_error, m.o_iv, B * m.KT, STAGE_G);
-  if (rc == RPM_OK && rel_err_max) rc = dev_download(e, rel_err_max, m.o_max, size_t(m.RT), STAGE_V);
+  HIP_TRY(e, hipSetDevice(d.device_id));   // dev_solution_error_batch put the caller's device back
+  rc = m.host.fetch(e, nonfinite, B);
+  if (rc == RPM_OK && interval_error) rc = dev_download(e, interval_error, o_iv, B * m.KT, STAGE_G);
+  if (rc == RPM_OK && rel_err_max) rc = dev_download(e, rel_err_max, o_max, size_t(m.RT), STAGE_V);
   if (rc == RPM_OK && rel_err) rc = dev_download(e, rel_err, m.rel, B * size_t(m.RT), STAGE_HESS);
   if (rc) return rc;
-  HIP_TRY(e, hipStreamSynchronize(d.stream));
-  dev_stage_synced(e);
-  if (nonfinite) std::memcpy(nonfinite, m.h_ints + B, B * sizeof(int));
-  return RPM_OK;
+  return m.host.finish(e, nonfinite, B);
 }
 
 }  // namespace rpm

@@ -10,6 +10,7 @@
 #include <thread>
 #include <vector>
 
+#include "rpm_device_restore.hpp"
 #include "rpm_engine.hpp"
 
 struct rpm_sweep {
@@ -21,6 +22,32 @@ struct rpm_sweep {
 };
 
 static std::string g_sweep_create_error;
+
+static int sfail(rpm_sweep* s, size_t r, int rc, const char* why) {
+  s->err = "share " + std::to_string(r) + " (device " + std::to_string(s->dev[r]) + "): " + why;
+  return rc;
+}
+
+// fn(r) on every share side by side, each on a host thread of its own with the share's device current (the current device is per
+// host thread), share 0 on the caller's; the caller's current device is put back.  The first share whose fn failed is reported
+// with why(r).
+template <class Fn, class Why>
+static int for_each_share(rpm_sweep* s, Fn fn, Why why) {
+  const size_t N = s->eng.size();
+  rpm::DeviceRestore restore;
+  std::vector<int> rcs(N, RPM_OK);
+  auto run = [&](size_t r) {
+    (void)hipSetDevice(s->dev[r]);
+    rcs[r] = fn(r);
+  };
+  std::vector<std::thread> th;
+  for (size_t r = 1; r < N; ++r) th.emplace_back(run, r);
+  run(0);
+  for (std::thread& t : th) t.join();
+  for (size_t r = 0; r < N; ++r)
+    if (rcs[r]) return sfail(s, r, rcs[r], why(r));
+  return RPM_OK;
+}
 
 extern "C" {
 
@@ -82,16 +109,11 @@ int rpm_sweep_share(const rpm_sweep* s, int share, int* first_instance, int* n_i
   return RPM_OK;
 }
 
-static int sfail(rpm_sweep* s, int r, int rc) {
-  s->err = "share " + std::to_string(r) + " (device " + std::to_string(s->dev[size_t(r)]) + "): " + rpm_ipm_last_error(s->ipm[size_t(r)]);
-  return rc;
-}
-
 int rpm_sweep_set_option(rpm_sweep* s, const char* key, double value) {
   if (!s || !key) return RPM_E_INVALID;
   for (size_t r = 0; r < s->ipm.size(); ++r) {
     const int rc = rpm_ipm_set_option(s->ipm[r], key, value);
-    if (rc) return sfail(s, int(r), rc);
+    if (rc) return sfail(s, r, rc, rpm_ipm_last_error(s->ipm[r]));
   }
   return RPM_OK;
 }
@@ -100,9 +122,10 @@ int rpm_sweep_set_bounds(rpm_sweep* s, int instance, const double* x_l, const do
   if (!s || instance < 0 || instance >= s->B) return RPM_E_INVALID;
   for (size_t r = 0; r < s->ipm.size(); ++r)
     if (instance < s->first[r] + s->count[r]) {
+      rpm::DeviceRestore restore;
       (void)hipSetDevice(s->dev[r]);
       const int rc = rpm_ipm_set_bounds(s->ipm[r], instance - s->first[r], x_l, x_u);
-      return rc ? sfail(s, int(r), rc) : RPM_OK;
+      return rc ? sfail(s, r, rc, rpm_ipm_last_error(s->ipm[r])) : RPM_OK;
     }
   return RPM_E_INVALID;
 }
@@ -111,21 +134,14 @@ int rpm_sweep_set_bounds(rpm_sweep* s, int instance, const double* x_l, const do
  * iteration count, scaled KKT error — as rpm_ipm_solve, over all shares at once */
 int rpm_sweep_solve(rpm_sweep* s, double* x, double* lambda, double* obj, int* status, int* iterations, double* kkt_error) {
   if (!s || !x) return RPM_E_INVALID;
-  const size_t N = s->ipm.size();
-  std::vector<int> rcs(N, RPM_OK);
-  auto run = [&](size_t r) {
-    (void)hipSetDevice(s->dev[r]);       // the current device is per host thread
-    const size_t i0 = size_t(s->first[r]);
-    rcs[r] = rpm_ipm_solve(s->ipm[r], x + i0 * s->n, lambda ? lambda + i0 * s->m : nullptr, obj ? obj + i0 : nullptr,
-                           status ? status + i0 : nullptr, iterations ? iterations + i0 : nullptr, kkt_error ? kkt_error + i0 : nullptr);
-  };
-  std::vector<std::thread> th;
-  for (size_t r = 1; r < N; ++r) th.emplace_back(run, r);
-  run(0);
-  for (std::thread& t : th) t.join();
-  for (size_t r = 0; r < N; ++r)
-    if (rcs[r]) return sfail(s, int(r), rcs[r]);
-  return RPM_OK;
+  return for_each_share(
+      s,
+      [&](size_t r) {
+        const size_t i0 = size_t(s->first[r]);
+        return rpm_ipm_solve(s->ipm[r], x + i0 * s->n, lambda ? lambda + i0 * s->m : nullptr, obj ? obj + i0 : nullptr,
+                             status ? status + i0 : nullptr, iterations ? iterations + i0 : nullptr, kkt_error ? kkt_error + i0 : nullptr);
+      },
+      [&](size_t r) { return rpm_ipm_last_error(s->ipm[r]); });
 }
 
 /* The mesh-error estimate of the whole sweep (rpm_solution_error_batch on every share, side by side).  x: B x n; instance_mask:
@@ -152,29 +168,19 @@ int rpm_sweep_solution_error(rpm_sweep* s, const double* x, const int* instance_
       return RPM_E_INVALID;
     }
   }
-  int prev = -1;
-  if (hipGetDevice(&prev) != hipSuccess) prev = -1;
   std::vector<std::vector<double>> part(N);
-  std::vector<int> rcs(N, RPM_OK);
-  auto run = [&](size_t r) {
-    (void)hipSetDevice(s->dev[r]);
-    const size_t i0 = size_t(s->first[r]);
-    const bool want_max = rel_err_max && included[r];
-    if (want_max) part[r].resize(size_t(RT));
-    rcs[r] = rpm_solution_error_batch(s->eng[r], x + i0 * s->n, instance_mask ? instance_mask + i0 : nullptr,
-                                      interval_error ? interval_error + i0 * KT : nullptr, want_max ? part[r].data() : nullptr,
-                                      rel_err ? rel_err + i0 * size_t(RT) : nullptr, nonfinite ? nonfinite + i0 : nullptr);
-  };
-  std::vector<std::thread> th;
-  for (size_t r = 1; r < N; ++r) th.emplace_back(run, r);
-  run(0);
-  for (std::thread& t : th) t.join();
-  if (prev >= 0) (void)hipSetDevice(prev);
-  for (size_t r = 0; r < N; ++r)
-    if (rcs[r]) {
-      s->err = "share " + std::to_string(r) + " (device " + std::to_string(s->dev[r]) + "): " + rpm_last_error(s->eng[r]);
-      return rcs[r];
-    }
+  const int rc = for_each_share(
+      s,
+      [&](size_t r) {
+        const size_t i0 = size_t(s->first[r]);
+        const bool want_max = rel_err_max && included[r];
+        if (want_max) part[r].resize(size_t(RT));
+        return rpm_solution_error_batch(s->eng[r], x + i0 * s->n, instance_mask ? instance_mask + i0 : nullptr,
+                                        interval_error ? interval_error + i0 * KT : nullptr, want_max ? part[r].data() : nullptr,
+                                        rel_err ? rel_err + i0 * size_t(RT) : nullptr, nonfinite ? nonfinite + i0 : nullptr);
+      },
+      [&](size_t r) { return rpm_last_error(s->eng[r]); });
+  if (rc) return rc;
   if (rel_err_max) {
     bool has = false;
     for (size_t r = 0; r < N; ++r) {
@@ -198,26 +204,13 @@ int rpm_sweep_carry_solution(rpm_sweep* from, rpm_sweep* to, const double* x_fro
     from->err = "rpm_sweep_carry_solution: the sweeps have different shares (devices or instance counts)";
     return RPM_E_INVALID;
   }
-  const size_t N = from->eng.size();
-  int prev = -1;
-  if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-  std::vector<int> rcs(N, RPM_OK);
-  auto run = [&](size_t r) {
-    (void)hipSetDevice(from->dev[r]);
-    const size_t i0 = size_t(from->first[r]);
-    rcs[r] = rpm_carry_solution_batch(from->eng[r], to->eng[r], x_from + i0 * from->n, x_to + i0 * to->n, nonfinite ? nonfinite + i0 : nullptr);
-  };
-  std::vector<std::thread> th;
-  for (size_t r = 1; r < N; ++r) th.emplace_back(run, r);
-  run(0);
-  for (std::thread& t : th) t.join();
-  if (prev >= 0) (void)hipSetDevice(prev);
-  for (size_t r = 0; r < N; ++r)
-    if (rcs[r]) {
-      from->err = "share " + std::to_string(r) + " (device " + std::to_string(from->dev[r]) + "): " + rpm_last_error(from->eng[r]);
-      return rcs[r];
-    }
-  return RPM_OK;
+  return for_each_share(
+      from,
+      [&](size_t r) {
+        const size_t i0 = size_t(from->first[r]);
+        return rpm_carry_solution_batch(from->eng[r], to->eng[r], x_from + i0 * from->n, x_to + i0 * to->n, nonfinite ? nonfinite + i0 : nullptr);
+      },
+      [&](size_t r) { return rpm_last_error(from->eng[r]); });
 }
 
 /* rpm_nlp2op_batch on every share, side by side: x B x n, lambda B x m, out B x EB, nonfinite B or NULL */
@@ -227,28 +220,15 @@ int rpm_sweep_nlp2op(rpm_sweep* s, const double* x, const double* lambda, double
     s->err = "rpm_sweep_nlp2op: x, lambda or out is NULL";
     return RPM_E_INVALID;
   }
-  const size_t N = s->eng.size();
   long long EB = 0;
   rpm_nlp2op_batch_layout(s->eng[0], 0, nullptr, &EB);
-  int prev = -1;
-  if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-  std::vector<int> rcs(N, RPM_OK);
-  auto run = [&](size_t r) {
-    (void)hipSetDevice(s->dev[r]);
-    const size_t i0 = size_t(s->first[r]);
-    rcs[r] = rpm_nlp2op_batch(s->eng[r], x + i0 * s->n, lambda + i0 * s->m, out + i0 * size_t(EB), nonfinite ? nonfinite + i0 : nullptr);
-  };
-  std::vector<std::thread> th;
-  for (size_t r = 1; r < N; ++r) th.emplace_back(run, r);
-  run(0);
-  for (std::thread& t : th) t.join();
-  if (prev >= 0) (void)hipSetDevice(prev);
-  for (size_t r = 0; r < N; ++r)
-    if (rcs[r]) {
-      s->err = "share " + std::to_string(r) + " (device " + std::to_string(s->dev[r]) + "): " + rpm_last_error(s->eng[r]);
-      return rcs[r];
-    }
-  return RPM_OK;
+  return for_each_share(
+      s,
+      [&](size_t r) {
+        const size_t i0 = size_t(s->first[r]);
+        return rpm_nlp2op_batch(s->eng[r], x + i0 * s->n, lambda + i0 * s->m, out + i0 * size_t(EB), nonfinite ? nonfinite + i0 : nullptr);
+      },
+      [&](size_t r) { return rpm_last_error(s->eng[r]); });
 }
 
 /* totals over the shares of the last solve: batched iterations (the largest share's count), factorisations and trial points (sums) */
