@@ -240,7 +240,7 @@ int rpm_solution_error_batch(rpm_engine* e, const double* x, const int* instance
  * 2 (time[k] - time[0]) / (time[N] - time[0]) - 1, the natural cubic spline of LpGuessChecker through the N + 1 knots evaluated
  * at the target's points (states also at 1), t0 = time[0], tf = time[N], static parameters copied.  Only the spline's cubes
  * differ: A * A * A on the device, pow(A, 3) on the host, so the two routes agree to rounding, not to the bit; t0, tf and the
- * parameters agree to the bit.  Multipliers are not carried (rpm_ipm_solve takes no starting lambda).  The caller builds the
+ * parameters agree to the bit.  Multipliers are carried by rpm_carry_multipliers_batch below.  The caller builds the
  * next engine and re-applies per-instance constants and bounds.
  * Argument errors are decided on the host before anything is queued: NULL arrays, engines that do not match, engines bound
  * to different devices, overlapping x_from / x_to: RPM_E_INVALID; interval-sharded engines, a column that does not fit one
@@ -254,6 +254,29 @@ int rpm_solution_error_batch(rpm_engine* e, const double* x, const int* instance
 int rpm_carry_solution_batch_dev(rpm_engine* from, rpm_engine* to, const double* d_x_from, double* d_x_to, int* d_nonfinite,
                                  void* stream);
 int rpm_carry_solution_batch(rpm_engine* from, rpm_engine* to, const double* x_from, double* x_to, int* nonfinite);
+/* The constraint multipliers of a sweep carried onto another mesh, as costates: the starting lambda of rpm_ipm_solve_warm on the
+ * next mesh.  lambda_from: n_instances x from.m, lambda_to: n_instances x to.m, instance-major; x_from (n_instances x from.n)
+ * supplies every phase's t0 and tf, so the knots are those of the solution carry.  Per instance and phase, rows read with the
+ * phase's own first row g0:
+ *   defect rows of state s:     c_k = -(1 / w_k) lambda[g0 + s N + k], k < N, c_N = the end-point costate -D(:,N)' lambda_s
+ *                               (rpm_nlp2op_control's); splined through the N + 1 knots like a state column, evaluated at the
+ *                               target's N' points; lambda'[g0' + s N' + j] = -w'_j c(tau'_j)
+ *   path rows of constraint j:  p_k = (1 / w_k) lambda[g0 + N nx + j N + k]; the value at tau = 1 by the spline of a control;
+ *                               lambda'[g0' + N' nx + j N' + q] = w'_q p(tau'_q)
+ *   event rows of the phase, linkage and linear rows after the last phase: copied.
+ * The spline, its recurrences and its evaluation are the solution carry's own code (one kernel, columns with a transform before
+ * and after).  Bound multipliers are not carried: on a new mesh rpm_ipm_solve_warm with z_L = z_U = NULL forms them from mu_init.
+ * Engine matching, argument errors (lambda_from / lambda_to take the place of x_from / x_to in the overlap test; NULL x_from,
+ * lambda_from or lambda_to: RPM_E_INVALID), LDS limits, the column split, option "carry_tile", nonfinite, "nothing allocated
+ * after the first call on a pair of engines" and graph capture: as rpm_carry_solution_batch[_dev]. */
+int rpm_carry_multipliers_batch_dev(rpm_engine* from, rpm_engine* to, const double* d_x_from, const double* d_lambda_from,
+                                    double* d_lambda_to, int* d_nonfinite, void* stream);
+int rpm_carry_multipliers_batch(rpm_engine* from, rpm_engine* to, const double* x_from, const double* lambda_from, double* lambda_to,
+                                int* nonfinite);
+/* the row map that carry uses (host only, no device needed): phase < n_phases: rows = {first defect row, first path row, first
+ * event row, one past the phase's last row}; phase == n_phases: the rows after the phases, {first, first, first, m}.  A phase
+ * out of range: RPM_E_INVALID. */
+int rpm_carry_multipliers_layout(rpm_engine* e, int phase, int rows[4]);
 
 /* Solution extraction for a whole sweep: Nlp2OpConverter::Nlp2OpControl, Core/Nlp2OPConverter.cpp:13-196, for all phases and all
  * n_instances instances of the engine at once, every instance with its own constants (rpm_set_instance_constants) and static
@@ -341,7 +364,10 @@ int rpm_hpliu_refine(rpm_hpliu* h, rpm_engine* e, const double* x, const double*
  *                       multipliers and the objective come back unscaled; DESIGN.md f-2 on why it is off here),
  *                       "ic_hot_start" (0; 1 = an iteration whose predecessor needed delta_w > 0 starts the inertia correction
  *                       at kappa_w^- * delta_w_last instead of 0 while that is >= "ic_hot_min" (1e-10): not Ipopt's rule, an
- *                       experiment)
+ *                       experiment),
+ *                       the warm start's (rpm_ipm_solve_warm), with Ipopt's names and defaults: "warm_start_bound_push",
+ *                       "warm_start_bound_frac", "warm_start_slack_bound_push", "warm_start_slack_bound_frac",
+ *                       "warm_start_mult_bound_push" (1e-3 each), "warm_start_mult_init_max" (1e6)
  *   rpm_ipm_set_bounds: variable bounds of one instance (default: the engine's); the fixed/free pattern is shared
  *   rpm_ipm_solve[_dev]: x (n_instances x n, in: starting points, out: solutions; host resp. device pointer),
  *                       lambda (n_instances x m, may be NULL); per instance on the host, any may be NULL: objective,
@@ -381,6 +407,40 @@ int rpm_ipm_solve(rpm_ipm* s, double* x, double* lambda, double* obj, int* statu
  * results in d_x / d_lambda are complete for the host and for work queued later on any stream. */
 int rpm_ipm_solve_dev(rpm_ipm* s, double* d_x, double* d_lambda, double* obj, int* status, int* iterations,
                       double* kkt_error, void* stream);
+/* Warm start in the primal and the dual (Ipopt's warm_start_init_point; not its warm_start_target_mu / _entire_iterate).  x
+ * (n_instances x n), lambda (n_instances x m, required) and z_L / z_U (n_instances x n: the multipliers of the variables' lower /
+ * upper bounds; both given or both NULL) are in/out, instance-major, values of the caller's unscaled problem.  Everything not
+ * named here is as in rpm_ipm_solve: bound relaxation, the fixed / free pattern, fresh instance records, an emptied
+ * limited-memory store, mu = mu_init; "init_ls_multipliers" is ignored.  Per instance:
+ *   x        pushed inside its relaxed bounds by warm_start_bound_push / _bound_frac (in place of bound_push / bound_frac); fixed
+ *            variables sit at their bound
+ *   slacks   g(x) pushed inside the relaxed row bounds by warm_start_slack_bound_push / _slack_bound_frac
+ *   lambda   clipped to +-warm_start_mult_init_max
+ *   z        max(z, warm_start_mult_bound_push) where the bound exists and the variable is free, else 0.  z_L = z_U = NULL:
+ *            mu_init / (x - l), mu_init / (u - x) at the pushed x and the relaxed bounds (the start on a new mesh, where no bound
+ *            multipliers exist), and none are returned
+ *   slack z  from the slack's stationarity -lambda_r - zL + zU = 0: zL = max(-lambda_r, warm_start_mult_bound_push) where the
+ *            row has a lower bound, zU = max(lambda_r, ...) where it has an upper one
+ *   nlp_scaling = 1: the clipped / floored values go into the scaled problem, lambda~ = (lambda sf) / sc, z~ = z sf (the inverse
+ *            of what the solve returns), the slack multipliers from lambda~
+ *   a NaN or Inf in an instance's x, lambda or z ends that instance with status 5 and touches no other.
+ * rpm_ipm_get_bound_multipliers[_dev]: z_L, z_U (n_instances x n) after the last solve of either kind, unscaled, 0 where there is
+ * no bound or the variable is fixed; what rpm_ipm_solve_warm returns in z_L / z_U, bit for bit.  Before any solve: RPM_E_INVALID.
+ * The _dev form queues one launch on `stream`.  Ordering contract of rpm_ipm_solve_warm_dev: that of rpm_ipm_solve_dev, for all
+ * four arrays.  NULL lambda, exactly one NULL z: RPM_E_INVALID with a message. */
+int rpm_ipm_solve_warm(rpm_ipm* s, double* x, double* lambda, double* z_L, double* z_U, double* obj, int* status, int* iterations,
+                       double* kkt_error);
+int rpm_ipm_solve_warm_dev(rpm_ipm* s, double* d_x, double* d_lambda, double* d_z_L, double* d_z_U, double* obj, int* status,
+                           int* iterations, double* kkt_error, void* stream);
+int rpm_ipm_get_bound_multipliers(rpm_ipm* s, double* z_L, double* z_U);
+int rpm_ipm_get_bound_multipliers_dev(rpm_ipm* s, double* d_z_L, double* d_z_U, void* stream);
+/* test hook (host pointers): exactly the launches that precede the iteration loop — warm = 0 the cold start (lambda, z_L, z_U
+ * ignored), else the warm start above — then the state: v (n_instances x nv: x, then the slacks), zL, zU (n_instances x nv),
+ * lambda (n_instances x m), mu and status (n_instances; status 0, or 5 after a non-finite input), all in the solver's (scaled)
+ * problem; any output may be NULL.  No step is taken; the last solve's bound multipliers are gone afterwards
+ * (rpm_ipm_get_bound_multipliers: RPM_E_INVALID until the next solve). */
+int rpm_ipm_debug_start(rpm_ipm* s, int warm, const double* x, const double* lambda, const double* z_L, const double* z_U,
+                        double* v_out, double* zL_out, double* zU_out, double* lam_out, double* mu_out, int* status_out);
 /* test hooks: KKT position of every unknown ([0,n) variables, slacks, then the m multipliers); factor + solve the
  * caller's matrices given in the band + border storage (host pointers, n_instances of each) */
 int rpm_ipm_get_permutation(rpm_ipm* s, int* pos, int capacity);
@@ -615,6 +675,13 @@ int rpm_sweep_solution_error(rpm_sweep* s, const double* x, const int* instance_
  * sweeps must deal their instances alike (same device list, same n_instances), else RPM_E_INVALID; the message is
  * rpm_sweep_last_error(from). */
 int rpm_sweep_carry_solution(rpm_sweep* from, rpm_sweep* to, const double* x_from, double* x_to, int* nonfinite);
+/* rpm_carry_multipliers_batch on every share side by side (lambda_from: B x from.m, lambda_to: B x to.m), sweeps dealt alike */
+int rpm_sweep_carry_multipliers(rpm_sweep* from, rpm_sweep* to, const double* x_from, const double* lambda_from, double* lambda_to,
+                                int* nonfinite);
+/* rpm_ipm_solve_warm / rpm_ipm_get_bound_multipliers over all shares at once (x, z_L, z_U: B x n, lambda: B x m) */
+int rpm_sweep_solve_warm(rpm_sweep* s, double* x, double* lambda, double* z_L, double* z_U, double* obj, int* status, int* iterations,
+                         double* kkt_error);
+int rpm_sweep_get_bound_multipliers(rpm_sweep* s, double* z_L, double* z_U);
 /* rpm_nlp2op_batch on every share side by side (x: B x n, lambda: B x m, out: B x EB, nonfinite: B or NULL): what one engine
  * holding all B instances returns, bit for bit. */
 int rpm_sweep_nlp2op(rpm_sweep* s, const double* x, const double* lambda, double* out, int* nonfinite);

@@ -403,6 +403,38 @@ int rpm_carry_solution_batch(rpm_engine* from, rpm_engine* to, const double* x_f
   RPM_GUARD_END(e)
 }
 
+int rpm_carry_multipliers_batch_dev(rpm_engine* from, rpm_engine* to, const double* d_x_from, const double* d_lambda_from,
+                                    double* d_lambda_to, int* d_nonfinite, void* stream) {
+  if (!from) return RPM_E_INVALID;
+  Engine& e = from->e;
+  RPM_GUARD_BEGIN
+  if (!to) return fail(e, RPM_E_INVALID, "carry_multipliers_batch_dev: the target engine is NULL");
+  if (!d_x_from) return fail(e, RPM_E_INVALID, "carry_multipliers_batch_dev: d_x_from is NULL");
+  if (!d_lambda_from) return fail(e, RPM_E_INVALID, "carry_multipliers_batch_dev: d_lambda_from is NULL");
+  if (!d_lambda_to) return fail(e, RPM_E_INVALID, "carry_multipliers_batch_dev: d_lambda_to is NULL");
+  return rpm::dev_carry_mult_batch(e, to->e, d_x_from, d_lambda_from, d_lambda_to, d_nonfinite, stream);
+  RPM_GUARD_END(e)
+}
+
+int rpm_carry_multipliers_batch(rpm_engine* from, rpm_engine* to, const double* x_from, const double* lambda_from, double* lambda_to,
+                                int* nonfinite) {
+  if (!from) return RPM_E_INVALID;
+  Engine& e = from->e;
+  RPM_GUARD_BEGIN
+  if (!to) return fail(e, RPM_E_INVALID, "carry_multipliers_batch: the target engine is NULL");
+  if (!x_from) return fail(e, RPM_E_INVALID, "carry_multipliers_batch: x_from is NULL");
+  if (!lambda_from) return fail(e, RPM_E_INVALID, "carry_multipliers_batch: lambda_from is NULL");
+  if (!lambda_to) return fail(e, RPM_E_INVALID, "carry_multipliers_batch: lambda_to is NULL");
+  return rpm::host_carry_mult_batch(e, to->e, x_from, lambda_from, lambda_to, nonfinite);
+  RPM_GUARD_END(e)
+}
+
+int rpm_carry_multipliers_layout(rpm_engine* h, int phase, int rows[4]) {
+  if (!h || !rows) return RPM_E_INVALID;
+  if (rpm::carry_multipliers_layout(h->e, phase, rows)) return fail(h->e, RPM_E_INVALID, "carry_multipliers_layout: the phase index is out of range");
+  return RPM_OK;
+}
+
 // ---- solution extraction for every phase and every instance of the engine (a sweep), rpm_extract_kernels.hip ---------
 int rpm_nlp2op_batch_layout(rpm_engine* h, int phase, long long field_offset[8], long long* block_doubles) {
   if (!h) return RPM_E_INVALID;

@@ -36,6 +36,23 @@ struct CarryLds {
 static_assert(CarryLds(65, 8, 16).Mp == 65 && CarryLds(64, 1, 1).Mp == 65 && CarryLds(65, 8, 16).total == 65 * (1 + 16 + 2 * 128),
               "CarryLds: an array overlaps its neighbour or the total changed");
 
+// A phase's rows of g / lambda: defects (nx x N, state-major), path rows (nc x N), events (ne); after the last phase's: the tail.
+struct CarryRows {
+  int defect0, path0, event0, end;
+  __host__ __device__ constexpr CarryRows(int g0, int N, int nx, int nc, int ne)
+      : defect0(g0), path0(g0 + N * nx), event0(path0 + N * nc), end(event0 + ne) {}
+};
+static_assert(CarryRows(7, 5, 3, 2, 4).path0 == 22 && CarryRows(7, 5, 3, 2, 4).event0 == 32 && CarryRows(7, 5, 3, 2, 4).end == 36, "CarryRows");
+
+// What the multipliers' carry needs beyond the solutions': lam_from NULL = the solution carry, which reads nothing else of this.
+struct CarryMult {
+  const double* lam_from;   // n_instances x m_from
+  double* lam_to;           // n_instances x m_to
+  KParams K;                // the source engine's tables (weights, nodes, D rows: post_end_costate)
+  const double* tw;         // the target engine's weights
+  int m_from, m_to, P;
+};
+
 // spline_eval's tail (rpm_setup.cpp): binary search for the knot interval, then A, B, Cc, Dd as written there.  The search
 // halves kr - kl whatever the comparisons say, and its trip count is bounded besides: NaN knots cannot spin it.
 __device__ __forceinline__ double carry_eval(double x, const double* xd, const double* yd, const double* c, int n) {
@@ -56,11 +73,17 @@ __device__ __forceinline__ double carry_eval(double x, const double* xd, const d
 __global__ void __launch_bounds__(256)
 rpm_carry_kernel(const PhaseDev* __restrict__ fph, const double* __restrict__ fpts, int n_from, const PhaseDev* __restrict__ tph,
                  const double* __restrict__ tpts, int n_to, const CarryGroup* __restrict__ groups, int B, int TB,
-                 const double* __restrict__ x_from, double* __restrict__ x_to) {
+                 const double* __restrict__ x_from, double* __restrict__ x_to, CarryMult mu_) {
   extern __shared__ __align__(16) double carry_sm[];
   const CarryGroup v = groups[blockIdx.x];
   const PhaseDev pf = fph[v.phase], pt = tph[v.phase];
   const int N = pf.N, M = N + 1, Nt = pt.N, nx = pf.nx, ncols = v.ncols;
+  const bool mult = mu_.lam_from != nullptr;
+  const KParams& K = mu_.K;
+  const double *__restrict__ lam_from = mu_.lam_from, *__restrict__ tw = mu_.tw;
+  double* __restrict__ lam_to = mu_.lam_to;
+  const int m_from = mu_.m_from, m_to = mu_.m_to, P = mu_.P;
+  const CarryRows rf(pf.g0, N, nx, pf.nc, pf.ne), rt(pt.g0, Nt, nx, pt.nc, pt.ne);
   const CarryLds L(M, TB, ncols);
   const int Mp = L.Mp;
   double* pts = carry_sm + L.pts;
@@ -88,7 +111,11 @@ rpm_carry_kernel(const PhaseDev* __restrict__ fph, const double* __restrict__ fp
     const double* xb = x_from + size_t(b0 + bi) * n_from;
     const int col = v.col0 + cl;
     double val = 0.0;   // a control's entry at tau = 1 is computed below
-    if (col < nx) val = xb[pf.x_state0 + col * M + k];
+    if (mult) {
+      const double* lb = lam_from + size_t(b0 + bi) * m_from;
+      if (col < nx) val = k < N ? -((1 / K.weights[pf.node0 + k]) * lb[rf.defect0 + col * N + k]) : post_end_costate(K, pf, lb + pf.g0, col);
+      else if (k < N) val = (1 / K.weights[pf.node0 + k]) * lb[rf.path0 + (col - nx) * N + k];
+    } else if (col < nx) val = xb[pf.x_state0 + col * M + k];
     else if (k < N) val = xb[pf.x_control0 + (col - nx) * N + k];
     ys[(bi * ncols + cl) * Mp + k] = val;
   }
@@ -143,20 +170,28 @@ rpm_carry_kernel(const PhaseDev* __restrict__ fph, const double* __restrict__ fp
   // ---- evaluate and store: states at the target's points and at 1.0, controls at the points ---------------------
   const double* tp = tpts + pt.node0;
   const int ns = nx - v.col0 < 0 ? 0 : (nx - v.col0 < ncols ? nx - v.col0 : ncols);   // state columns of this group
-  const int nc = ncols - ns, Q = Nt + 1;
+  const int nc = ncols - ns, Q = mult ? Nt : Nt + 1;
   for (int idx = tid; idx < nb * ns * Q; idx += nt) {
     const int q = idx % Q, cl = (idx / Q) % ns, bi = idx / (Q * ns);
     const int r = bi * ncols + cl;
-    x_to[size_t(b0 + bi) * n_to + pt.x_state0 + (v.col0 + cl) * Q + q] =
-        carry_eval(q < Nt ? tp[q] : 1.0, tau + bi * Mp, ys + r * Mp, cs + r * Mp, M);
+    const double val = carry_eval(q < Nt ? tp[q] : 1.0, tau + bi * Mp, ys + r * Mp, cs + r * Mp, M);
+    if (mult) lam_to[size_t(b0 + bi) * m_to + rt.defect0 + (v.col0 + cl) * Nt + q] = -(tw[pt.node0 + q] * val);
+    else x_to[size_t(b0 + bi) * n_to + pt.x_state0 + (v.col0 + cl) * Q + q] = val;
   }
   for (int idx = tid; idx < nb * nc * Nt; idx += nt) {
     const int q = idx % Nt, cl = ns + (idx / Nt) % nc, bi = idx / (Nt * nc);
     const int r = bi * ncols + cl;
-    x_to[size_t(b0 + bi) * n_to + pt.x_control0 + (v.col0 + cl - nx) * Nt + q] =
-        carry_eval(tp[q], tau + bi * Mp, ys + r * Mp, cs + r * Mp, M);
+    const double val = carry_eval(tp[q], tau + bi * Mp, ys + r * Mp, cs + r * Mp, M);
+    if (mult) lam_to[size_t(b0 + bi) * m_to + rt.path0 + (v.col0 + cl - nx) * Nt + q] = tw[pt.node0 + q] * val;
+    else x_to[size_t(b0 + bi) * n_to + pt.x_control0 + (v.col0 + cl - nx) * Nt + q] = val;
   }
-  if (v.first)
+  if (v.first && mult) {   // the phase's event rows; the last phase's first group: the rows after the phases too
+    const int tail = v.phase == P - 1 ? m_from - rf.end : 0, cnt = pf.ne + tail;
+    for (int idx = tid; idx < nb * cnt; idx += nt) {
+      const int j = idx % cnt, bi = idx / cnt;
+      lam_to[size_t(b0 + bi) * m_to + rt.event0 + j] = lam_from[size_t(b0 + bi) * m_from + rf.event0 + j];
+    }
+  } else if (v.first)
     for (int idx = tid; idx < nb * (2 + pf.nq); idx += nt) {
       const int j = idx % (2 + pf.nq), bi = idx / (2 + pf.nq);
       const double* xb = x_from + size_t(b0 + bi) * n_from;
@@ -169,11 +204,17 @@ rpm_carry_kernel(const PhaseDev* __restrict__ fph, const double* __restrict__ fp
     }
 }
 
+static CarryRows carry_rows(const Engine& e, int phase) {
+  const PhaseHost& p = e.ph[size_t(phase)];
+  return CarryRows(p.con0, p.N, p.nx, p.nc, p.ne);
+}
+
 namespace {
 
 struct CarryPlan {
   long long to_serial = 0;
   int tile_opt = 0, lds_opt = 0;   // the options the plan was made under
+  int mult = 0;                    // 1: the plan of the multipliers' columns (nx + nc per phase), 0: the solution's (nx + nu)
   int TB = 1, n_groups = 0;
   size_t lds = 0;
   CarryGroup* d_groups = nullptr;
@@ -189,7 +230,7 @@ size_t carry_budget(const Engine& from) {
 
 // Host planner: instances per workgroup and the split of every phase's columns over workgroups.  Columns are independent,
 // so a phase whose columns do not fit one workgroup's LDS is dealt over several; the tile shrinks before one column is refused.
-bool carry_plan(const Engine& from, int* TB_out, std::vector<CarryGroup>* groups, size_t* lds_out) {
+bool carry_plan(const Engine& from, int mult, int* TB_out, std::vector<CarryGroup>* groups, size_t* lds_out) {
   const size_t budget = carry_budget(from) / sizeof(double);
   // automatic: 2 instances per workgroup (reasoned; tools/bench_sweep_carry.py measures every value)
   int TB = clamp_tile(from.opt_carry_tile > 0 ? from.opt_carry_tile : 2, from.n_instances);
@@ -203,7 +244,7 @@ bool carry_plan(const Engine& from, int* TB_out, std::vector<CarryGroup>* groups
   if (groups) groups->clear();
   for (size_t ip = 0; ip < from.ph.size(); ++ip) {
     const PhaseHost& p = from.ph[ip];
-    const int cols = p.nx + p.nu;
+    const int cols = p.nx + (mult ? p.nc : p.nu);
     int most = 1;   // the most columns that fit next to the per-instance rows
     while (most < cols && size_t(CarryLds(p.N + 1, TB, most + 1).total) <= budget) ++most;
     const auto [n_groups, per] = deal_columns(cols, most);
@@ -239,20 +280,24 @@ CarryState& carry_state(Device& d) {
   return *static_cast<CarryState*>(d.carry);
 }
 
-int carry_launch(Engine& from, Engine& to, const double* d_x_from, double* d_x_to, int* d_nonfinite, hipStream_t st) {
+// d_lam_from NULL: the solutions, x_from -> x_to; else the multipliers, lam_from -> lam_to with x_from's t0 / tf for the knots
+int carry_launch(Engine& from, Engine& to, const double* d_x_from, double* d_x_to, const double* d_lam_from, double* d_lam_to,
+                 int* d_nonfinite, hipStream_t st) {
   Device& d = *from.dev;
   HIP_TRY(from, hipSetDevice(d.device_id));
   CarryState& cs = carry_state(d);
   const CarryPlan* plan = nullptr;
+  const int mult = d_lam_from ? 1 : 0;
   for (const CarryPlan& p : cs.plans)
-    if (p.to_serial == to.serial && p.tile_opt == from.opt_carry_tile && p.lds_opt == from.opt_carry_lds) plan = &p;
+    if (p.to_serial == to.serial && p.tile_opt == from.opt_carry_tile && p.lds_opt == from.opt_carry_lds && p.mult == mult) plan = &p;
   if (!plan) {   // first call on this pair of engines: the only allocation and the only blocking copy
     CarryPlan p;
     std::vector<CarryGroup> groups;
-    if (!carry_plan(from, &p.TB, &groups, &p.lds)) {
-      from.err = "carry_solution_batch: a column does not fit one workgroup's LDS";
+    if (!carry_plan(from, mult, &p.TB, &groups, &p.lds)) {
+      from.err = std::string(mult ? "carry_multipliers_batch" : "carry_solution_batch") + ": a column does not fit one workgroup's LDS";
       return RPM_E_UNSUPPORTED;
     }
+    p.mult = mult;
     p.to_serial = to.serial;
     p.tile_opt = from.opt_carry_tile;
     p.lds_opt = from.opt_carry_lds;
@@ -263,13 +308,15 @@ int carry_launch(Engine& from, Engine& to, const double* d_x_from, double* d_x_t
     plan = &cs.plans.back();
   }
   const int B = from.n_instances;
+  CarryMult cm{};
+  if (mult) cm = CarryMult{d_lam_from, d_lam_to, d.kp, to.dev->d_weights, from.m, to.m, from.P};
   hipLaunchKernelGGL(rpm_carry_kernel, dim3(unsigned(plan->n_groups), unsigned((B + plan->TB - 1) / plan->TB)), dim3(256), plan->lds, st,
                      d.d_phases, d.d_points, from.n, to.dev->d_phases, to.dev->d_points, to.n, plan->d_groups, B, plan->TB, d_x_from,
-                     d_x_to);
-  if (d_nonfinite) flag_launch(to.n, d_x_to, d_nonfinite, B, st);
+                     d_x_to, cm);
+  if (d_nonfinite) flag_launch(mult ? to.m : to.n, mult ? d_lam_to : d_x_to, d_nonfinite, B, st);
   const hipError_t s = hipGetLastError();
   if (s != hipSuccess) {
-    from.err = std::string("carry_solution_batch launch: ") + hipGetErrorString(s);
+    from.err = std::string(mult ? "carry_multipliers_batch" : "carry_solution_batch") + " launch: " + hipGetErrorString(s);
     return RPM_E_DEVICE;
   }
   return RPM_OK;
@@ -296,18 +343,21 @@ int carry_group_count(const Engine& from) {
   int TB = 0;
   size_t lds = 0;
   std::vector<CarryGroup> groups;
-  return carry_plan(from, &TB, &groups, &lds) ? int(groups.size()) : 0;
+  return carry_plan(from, 0, &TB, &groups, &lds) ? int(groups.size()) : 0;
 }
 
-// every argument error, decided on the host before a device is touched (x_from / x_to: both host or both device pointers)
-int carry_check(Engine& from, const Engine& to, const void* x_from, const void* x_to) {
-  const std::string who = "carry_solution_batch: ";
+// every argument error, decided on the host before a device is touched (x_from / x_to: both host or both device pointers;
+// mult: the multipliers' arrays, n_instances x m, and the multipliers' columns)
+int carry_check(Engine& from, const Engine& to, const void* x_from, const void* x_to, int mult) {
+  const std::string who = mult ? "carry_multipliers_batch: " : "carry_solution_batch: ";
   for (int i = 0; i < std::min(from.P, to.P); ++i) {   // the sizes first: they say more than "another problem"
     const PhaseHost &a = from.ph[size_t(i)], &b = to.ph[size_t(i)];
     const std::string tag = " differs in phase " + std::to_string(i + 1);
     if (a.nx != b.nx) return carry_fail(from, RPM_E_INVALID, who + "nx" + tag);
     if (a.nu != b.nu) return carry_fail(from, RPM_E_INVALID, who + "nu" + tag);
     if (a.nq != b.nq) return carry_fail(from, RPM_E_INVALID, who + "nq" + tag);
+    if (mult && a.nc != b.nc) return carry_fail(from, RPM_E_INVALID, who + "nc" + tag);
+    if (mult && a.ne != b.ne) return carry_fail(from, RPM_E_INVALID, who + "ne" + tag);
   }
   if (from.P != to.P) return carry_fail(from, RPM_E_INVALID, who + "the engines have different phase counts");
   if (from.problem_id != to.problem_id) return carry_fail(from, RPM_E_INVALID, who + "the engines hold different problems");
@@ -318,12 +368,16 @@ int carry_check(Engine& from, const Engine& to, const void* x_from, const void* 
     return carry_fail(from, RPM_E_INVALID, who + "the engines are bound to different devices");
   const char* a = static_cast<const char*>(x_from);
   const char* b = static_cast<const char*>(x_to);
-  const size_t na = size_t(from.n_instances) * from.n * sizeof(double), nb = size_t(to.n_instances) * to.n * sizeof(double);
-  if (a < b + nb && b < a + na) return carry_fail(from, RPM_E_INVALID, who + "x_from and x_to overlap");
+  const size_t na = size_t(from.n_instances) * (mult ? from.m : from.n) * sizeof(double);
+  const size_t nb = size_t(to.n_instances) * (mult ? to.m : to.n) * sizeof(double);
+  if (a < b + nb && b < a + na)
+    return carry_fail(from, RPM_E_INVALID, who + (mult ? "lambda_from and lambda_to overlap" : "x_from and x_to overlap"));
+  if (mult && from.P > 0 && from.m - carry_rows(from, from.P - 1).end != to.m - carry_rows(to, to.P - 1).end)
+    return carry_fail(from, RPM_E_INVALID, who + "the rows after the last phase differ in number");
   if (sharded(from) || sharded(to)) return carry_fail(from, RPM_E_UNSUPPORTED, who + "not with interval sharding");
   int TB = 0;
   size_t lds = 0;
-  if (!carry_plan(from, &TB, nullptr, &lds)) {
+  if (!carry_plan(from, mult, &TB, nullptr, &lds)) {
     int most = 0;
     for (const PhaseHost& p : from.ph) most = std::max(most, p.N + 1);
     return carry_fail(from, RPM_E_UNSUPPORTED, who + "a column of " + std::to_string(most) + " knots does not fit one workgroup's LDS");
@@ -338,7 +392,16 @@ int dev_carry_batch(Engine& from, Engine& to, const double* d_x_from, double* d_
   DeviceRestore restore;
   rc = carry_devices(from, to);
   if (rc) return rc;
-  return carry_launch(from, to, d_x_from, d_x_to, d_nonfinite, static_cast<hipStream_t>(stream));
+  return carry_launch(from, to, d_x_from, d_x_to, nullptr, nullptr, d_nonfinite, static_cast<hipStream_t>(stream));
+}
+int dev_carry_mult_batch(Engine& from, Engine& to, const double* d_x_from, const double* d_lam_from, double* d_lam_to, int* d_nonfinite,
+                         void* stream) {
+  int rc = carry_check(from, to, d_lam_from, d_lam_to, 1);
+  if (rc) return rc;
+  DeviceRestore restore;
+  rc = carry_devices(from, to);
+  if (rc) return rc;
+  return carry_launch(from, to, d_x_from, nullptr, d_lam_from, d_lam_to, d_nonfinite, static_cast<hipStream_t>(stream));
 }
 
 // the same through host arrays: x_from up through the staging slot, the carried block and the verdicts back; blocking
@@ -357,11 +420,48 @@ int host_carry_batch(Engine& from, Engine& to, const double* x_from, double* x_t
   host_new_x(from);   // d_x is about to hold other values than the callbacks' last x
   rc = dev_upload(from, d.d_x, x_from, B * from.n, STAGE_X);
   if (rc) return rc;
-  rc = carry_launch(from, to, d.d_x, cs.host.out, nonfinite ? cs.host.flags : nullptr, d.stream);
+  rc = carry_launch(from, to, d.d_x, cs.host.out, nullptr, nullptr, nonfinite ? cs.host.flags : nullptr, d.stream);
   if (rc == RPM_OK) rc = cs.host.fetch(from, nonfinite, B);
   if (rc == RPM_OK) rc = dev_download(from, x_to, cs.host.out, count, STAGE_G);
   if (rc) return rc;
   return cs.host.finish(from, nonfinite, B);
+}
+int host_carry_mult_batch(Engine& from, Engine& to, const double* x_from, const double* lam_from, double* lam_to, int* nonfinite) {
+  int rc = carry_check(from, to, lam_from, lam_to, 1);
+  if (rc) return rc;
+  DeviceRestore restore;
+  rc = carry_devices(from, to);
+  if (rc) return rc;
+  Device& d = *from.dev;
+  HIP_TRY(from, hipSetDevice(d.device_id));
+  CarryState& cs = carry_state(d);
+  const size_t B = size_t(from.n_instances), count = B * to.m;
+  rc = cs.host.ensure(from, count, B);
+  if (rc) return rc;
+  host_new_x(from);   // d_x is about to hold other values than the callbacks' last x
+  rc = dev_upload(from, d.d_x, x_from, B * from.n, STAGE_X);
+  if (rc == RPM_OK) rc = dev_upload(from, d.d_lambda, lam_from, B * from.m, STAGE_LAMBDA);
+  if (rc) return rc;
+  rc = carry_launch(from, to, d.d_x, nullptr, d.d_lambda, cs.host.out, nonfinite ? cs.host.flags : nullptr, d.stream);
+  if (rc == RPM_OK) rc = cs.host.fetch(from, nonfinite, B);
+  if (rc == RPM_OK) rc = dev_download(from, lam_to, cs.host.out, count, STAGE_G);
+  if (rc) return rc;
+  return cs.host.finish(from, nonfinite, B);
+}
+
+// the row map of the multiplier carry on the host: phase < P: {first defect row, first path row, first event row, one past the
+// phase's last row}; phase == P: the rows after the phases, {first, first, first, m}
+int carry_multipliers_layout(const Engine& e, int phase, int rows[4]) {
+  if (phase < 0 || phase > e.P) return RPM_E_INVALID;
+  if (phase == e.P) {
+    const int t0 = e.P > 0 ? carry_rows(e, e.P - 1).end : 0;
+    rows[0] = rows[1] = rows[2] = t0;
+    rows[3] = e.m;
+    return RPM_OK;
+  }
+  const CarryRows r = carry_rows(e, phase);
+  rows[0] = r.defect0; rows[1] = r.path0; rows[2] = r.event0; rows[3] = r.end;
+  return RPM_OK;
 }
 
 }  // namespace rpm

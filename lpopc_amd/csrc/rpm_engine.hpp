@@ -263,10 +263,15 @@ int host_solution_error_batch(Engine& e, const double* x, const int* mask, doubl
 
 // rpm_carry_kernels.hip: the solutions of all instances of `from` splined onto the mesh of `to` (the next mesh's starting
 // points).  carry_check decides every argument error on the host; the two drivers call it before they touch a device.
-int carry_check(Engine& from, const Engine& to, const void* x_from, const void* x_to);
+int carry_check(Engine& from, const Engine& to, const void* x_from, const void* x_to, int mult = 0);   // mult: the multipliers' arrays and columns
 int carry_group_count(const Engine& from);   // workgroups per tile of instances under the engine's options; 0: a column does not fit
 int dev_carry_batch(Engine& from, Engine& to, const double* d_x_from, double* d_x_to, int* d_nonfinite, void* stream);
 int host_carry_batch(Engine& from, Engine& to, const double* x_from, double* x_to, int* nonfinite);
+// the constraint multipliers as costates / path-multiplier densities through the same kernel; x_from supplies t0 and tf
+int dev_carry_mult_batch(Engine& from, Engine& to, const double* d_x_from, const double* d_lam_from, double* d_lam_to, int* d_nonfinite,
+                         void* stream);
+int host_carry_mult_batch(Engine& from, Engine& to, const double* x_from, const double* lam_from, double* lam_to, int* nonfinite);
+int carry_multipliers_layout(const Engine& e, int phase, int rows[4]);   // host only
 
 // rpm_extract_kernels.hip: Nlp2OpControl for all phases and all instances of the engine.  nlp2op_batch_layout is host only;
 // extract_check decides every error of the engine's state on the host, the two drivers call it before they touch a device.

@@ -19,6 +19,10 @@ constexpr int IPM_LB_SMALL = 8 + 2 * (2 * IPM_LB_H) * (2 * IPM_LB_H) + 2 * (2 * 
 struct IpmOpts {
   double tol = 1e-8, mu_init = 0.1, kappa_eps = 10.0, kappa_mu = 0.2, theta_mu = 1.5, tau_min = 0.99;
   double bound_push = 1e-2, bound_frac = 1e-2, kappa_sigma = 1e10, s_max = 100.0;
+  // the warm start (rpm_ipm_solve_warm): Ipopt's warm_start_bound_push / _bound_frac (x), _slack_bound_push / _slack_bound_frac
+  // (slacks), _mult_bound_push (floor of the bound multipliers), _mult_init_max (clip of lambda)
+  double ws_bound_push = 1e-3, ws_bound_frac = 1e-3, ws_slack_bound_push = 1e-3, ws_slack_bound_frac = 1e-3;
+  double ws_mult_bound_push = 1e-3, ws_mult_init_max = 1e6;
   double gamma_theta = 1e-5, gamma_phi = 1e-8, eta_phi = 1e-8, delta = 1.0, s_theta = 1.1, s_phi = 2.3, gamma_alpha = 0.05;
   double delta_c = 1e-9, delta_w_first = 1e-4, delta_w_min = 1e-20, delta_w_max = 1e40, kw_inc_first = 100.0, kw_inc = 8.0,
          kw_dec = 1.0 / 3.0;
@@ -169,8 +173,11 @@ constexpr int IPM_VEC_PART = 24;     // doubles of partial results per workgroup
 constexpr int IPM_MT = 8;   // most 16-row tiles per wave of the factorisation: block columns of up to 4 x 8 x 16 = 512 rows
 
 // launchers (rpm_ipm_step_kernels.hip; assemble: rpm_kkt_factor.hip, inertia: rpm_kkt_solve.hip); all asynchronous on `st`
-void ipm_launch_init(const IpmDev& D, const double* d_x0, hipStream_t st);
-void ipm_launch_init_slack(const IpmDev& D, hipStream_t st);
+void ipm_launch_init(const IpmDev& D, const double* d_x0, hipStream_t st, int warm = 0);    // warm: the warm_start_* pushes, duals left to ipm_launch_warm_duals
+void ipm_launch_init_slack(const IpmDev& D, hipStream_t st, int warm = 0);
+// the warm start's lambda and z (d_zL / d_zU NULL: from mu_init) after the slacks and the scaling factors exist; non-finite input -> status 5
+void ipm_launch_warm_duals(const IpmDev& D, const double* d_x0, const double* d_lambda, const double* d_zL, const double* d_zU, hipStream_t st);
+void ipm_launch_bound_multipliers(const IpmDev& D, double* d_zL, double* d_zU, hipStream_t st);   // B x n each, unscaled
 void ipm_launch_pack_x(const IpmDev& D, hipStream_t st);
 void ipm_launch_residual(const IpmDev& D, hipStream_t st);
 void ipm_launch_assemble(const IpmDev& D, int nnz_max, hipStream_t st);          // zero + scatter + right-hand side

@@ -34,6 +34,8 @@ struct rpm_ipm {
   bool attached = false;
   bool lbfgs = false;            // hessian-approximation = limited-memory (rpm_ipm_lbfgs.hip)
   int lb_iterations = 0;         // iterations of the running solve: an upper bound of the pairs any instance holds
+  bool solved = false;           // a solve has finished: D.zL / D.zU hold its bound multipliers (rpm_ipm_get_bound_multipliers)
+  double* d_host_form = nullptr; // the host-pointer entry points' device copies of x, lambda, z_L, z_U (B x (3 n + m)), on first use
   ~rpm_ipm() {
     if (attached && eng && eng->e.ipm_attached > 0) eng->e.ipm_attached -= 1;
     for (void* p : allocs) (void)hipFree(p);
@@ -377,6 +379,12 @@ int rpm_ipm_set_option(rpm_ipm* h, const char* key, double value) {
   else if (k == "mu_init") o.mu_init = value;
   else if (k == "bound_push") o.bound_push = value;
   else if (k == "bound_frac") o.bound_frac = value;
+  else if (k == "warm_start_bound_push") o.ws_bound_push = value;
+  else if (k == "warm_start_bound_frac") o.ws_bound_frac = value;
+  else if (k == "warm_start_slack_bound_push") o.ws_slack_bound_push = value;
+  else if (k == "warm_start_slack_bound_frac") o.ws_slack_bound_frac = value;
+  else if (k == "warm_start_mult_bound_push") o.ws_mult_bound_push = value;
+  else if (k == "warm_start_mult_init_max") o.ws_mult_init_max = value;
   else if (k == "delta_c") o.delta_c = value;
   else if (k == "max_line_search") o.max_ls = int(value);
   else if (k == "restoration") o.resto = value != 0.0;
@@ -724,17 +732,47 @@ int rpm_ipm_get_permutation(rpm_ipm* h, int* pos, int capacity) {
   return RPM_OK;
 }
 
-int rpm_ipm_solve_dev(rpm_ipm* h, double* d_x, double* d_lambda, double* obj, int* status, int* iterations, double* kkt_error,
-                      void* stream) {
-  if (!h || !d_x) return RPM_E_INVALID;
+}  // extern "C"
+
+namespace {
+// The launches that precede the iteration loop: bounds, pushed x, (nlp_scaling) the scaling factors, g at the pushed x, slacks and
+// the duals — z = 1, lambda = 0 of the cold start, or (warm) the caller's d_lambda and d_zL / d_zU (both NULL: z from mu_init).
+int ipm_start(rpm_ipm* h, bool warm, const double* d_x, const double* d_lambda, const double* d_zL, const double* d_zU, hipStream_t st) {
+  Engine& e = h->eng->e;
+  IpmDev& D = h->D;
+  const IpmPlan& p = h->plan;
+  const unsigned B = unsigned(D.B);
+  auto eng_fail = [&](int rc) { h->err = e.err; return rc; };
+  dev_forget_persistent(e);   // the first Jacobian evaluation of this solve writes the constant block of D.jac, the later ones skip it
+  if (h->lbfgs) lb_launch_reset(D, st);
+  IPM_TRY(h, hipMemcpyAsync(D.xt, d_x, size_t(B) * p.n * sizeof(double), hipMemcpyDeviceToDevice, st));
+  ipm_launch_init(D, d_x, st, warm ? 1 : 0);
+  int rc;
+  const bool scal = D.scal_on != 0;
+  if (scal) {   // Ipopt's gradient-based scaling: factors from the gradients at the caller's starting point (before it is pushed inside its bounds)
+    if ((rc = dev_eval_obj(e, D.xt, D.objt, D.grad, st))) return eng_fail(rc);
+    if ((rc = dev_eval_cons(e, D.xt, D.gt, D.jac, 3 | 4 | 16, st))) return eng_fail(rc);
+    ipm_launch_scaling_factors(D, st);
+    // this evaluation has written D.jac's constant block, which the later ones leave alone: it is scaled here, once
+    if (e.nnz_jac > D.nnz_var) ipm_launch_scale(D, nullptr, D.jac, D.nnz_var, e.nnz_jac, nullptr, nullptr, st);
+  }
+  ipm_launch_pack_x(D, st);
+  rc = dev_eval_cons(e, D.xe, D.g, nullptr, 1 | 4, st);
+  if (rc) return eng_fail(rc);
+  if (scal) ipm_launch_scale(D, D.g, nullptr, 0, 0, nullptr, nullptr, st);
+  ipm_launch_init_slack(D, st, warm ? 1 : 0);
+  if (warm) ipm_launch_warm_duals(D, D.xt, d_lambda, d_zL, d_zU, st);   // (D.xt: the caller's x as it came)
+  return launch_check(h, "ipm_init");
+}
+
+int ipm_solve_dev(rpm_ipm* h, bool warm, double* d_x, double* d_lambda, double* d_zL, double* d_zU, double* obj, int* status,
+                  int* iterations, double* kkt_error, void* stream) {
   Engine& e = h->eng->e;
   IpmDev& D = h->D;
   const IpmPlan& p = h->plan;
   hipStream_t st = static_cast<hipStream_t>(dev_stream(e));
   const unsigned B = unsigned(D.B);
   auto eng_fail = [&](int rc) { h->err = e.err; return rc; };
-  dev_forget_persistent(e);   // the first Jacobian evaluation of this solve writes the constant block of D.jac, the later ones skip it
-  if (h->lbfgs) lb_launch_reset(D, st);
   h->lb_iterations = 0;
   h->total_factorizations = h->total_iterations = h->total_trials = h->total_soc = 0;
   h->factor_ms = h->solve_ms = 0.0;
@@ -749,23 +787,9 @@ int rpm_ipm_solve_dev(rpm_ipm* h, double* d_x, double* d_lambda, double* obj, in
   IPM_TRY(h, hipEventRecord(h->ev[0], static_cast<hipStream_t>(stream)));
   IPM_TRY(h, hipStreamWaitEvent(st, h->ev[0], 0));
 
-  IPM_TRY(h, hipMemcpyAsync(D.xt, d_x, size_t(B) * p.n * sizeof(double), hipMemcpyDeviceToDevice, st));
-  ipm_launch_init(D, d_x, st);
-  int rc;
+  int rc = ipm_start(h, warm, d_x, d_lambda, d_zL, d_zU, st);
+  if (rc) return rc;
   const bool scal = D.scal_on != 0;
-  if (scal) {   // Ipopt's gradient-based scaling: factors from the gradients at the caller's starting point (before it is pushed inside its bounds)
-    if ((rc = dev_eval_obj(e, D.xt, D.objt, D.grad, st))) return eng_fail(rc);
-    if ((rc = dev_eval_cons(e, D.xt, D.gt, D.jac, 3 | 4 | 16, st))) return eng_fail(rc);
-    ipm_launch_scaling_factors(D, st);
-    // this evaluation has written D.jac's constant block, which the later ones leave alone: it is scaled here, once
-    if (e.nnz_jac > D.nnz_var) ipm_launch_scale(D, nullptr, D.jac, D.nnz_var, e.nnz_jac, nullptr, nullptr, st);
-  }
-  ipm_launch_pack_x(D, st);
-  rc = dev_eval_cons(e, D.xe, D.g, nullptr, 1 | 4, st);
-  if (rc) return eng_fail(rc);
-  if (scal) ipm_launch_scale(D, D.g, nullptr, 0, 0, nullptr, nullptr, st);
-  ipm_launch_init_slack(D, st);
-  if ((rc = launch_check(h, "ipm_init"))) return rc;
 
   for (;;) {
     ipm_launch_pack_x(D, st);
@@ -852,6 +876,7 @@ int rpm_ipm_solve_dev(rpm_ipm* h, double* d_x, double* d_lambda, double* obj, in
     if (scal) ipm_launch_unscale_lambda(D, d_lambda, st);     // the multipliers of the caller's (unscaled) rows
     else IPM_TRY(h, hipMemcpyAsync(d_lambda, D.lam, size_t(B) * p.m * sizeof(double), hipMemcpyDeviceToDevice, st));
   }
+  if (d_zL && d_zU) ipm_launch_bound_multipliers(D, d_zL, d_zU, st);
   if (scal) {
     sf_host.resize(B);
     IPM_TRY(h, hipMemcpyAsync(sf_host.data(), D.sf, size_t(B) * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -869,23 +894,78 @@ int rpm_ipm_solve_dev(rpm_ipm* h, double* d_x, double* d_lambda, double* obj, in
     if (iterations) iterations[bi] = S.iter;
     if (kkt_error) kkt_error[bi] = S.err0;
   }
+  h->solved = true;
   return RPM_OK;
+}
+
+// the host-pointer entry points' device block, allocated once and kept (rpm_ipm_solve, rpm_ipm_solve_warm,
+// rpm_ipm_get_bound_multipliers, rpm_ipm_debug_start): x (B n), lambda (B m), z_L, z_U (B n each)
+int host_form(rpm_ipm* h, double** d_x, double** d_l, double** d_zL, double** d_zU) {
+  const size_t Bn = size_t(h->D.B) * h->plan.n, Bm = size_t(h->D.B) * std::max(h->plan.m, 1);
+  if (!h->d_host_form) {
+    int rc = ipm_alloc(h, &h->d_host_form, 3 * Bn + Bm);
+    if (rc) return rc;
+  }
+  *d_x = h->d_host_form;
+  *d_l = *d_x + Bn;
+  *d_zL = *d_l + Bm;
+  *d_zU = *d_zL + Bn;
+  return RPM_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int rpm_ipm_solve_dev(rpm_ipm* h, double* d_x, double* d_lambda, double* obj, int* status, int* iterations, double* kkt_error,
+                      void* stream) {
+  if (!h || !d_x) return RPM_E_INVALID;
+  return ipm_solve_dev(h, false, d_x, d_lambda, nullptr, nullptr, obj, status, iterations, kkt_error, stream);
+}
+
+int rpm_ipm_solve_warm_dev(rpm_ipm* h, double* d_x, double* d_lambda, double* d_z_L, double* d_z_U, double* obj, int* status,
+                           int* iterations, double* kkt_error, void* stream) {
+  if (!h) return RPM_E_INVALID;
+  if (!d_x || !d_lambda) { h->err = "rpm_ipm_solve_warm: x and lambda are required"; return RPM_E_INVALID; }
+  if (!d_z_L != !d_z_U) { h->err = "rpm_ipm_solve_warm: z_L and z_U are given together or both NULL"; return RPM_E_INVALID; }
+  return ipm_solve_dev(h, true, d_x, d_lambda, d_z_L, d_z_U, obj, status, iterations, kkt_error, stream);
+}
+
+int rpm_ipm_get_bound_multipliers_dev(rpm_ipm* h, double* d_z_L, double* d_z_U, void* stream) {
+  if (!h) return RPM_E_INVALID;
+  if (!d_z_L || !d_z_U) { h->err = "rpm_ipm_get_bound_multipliers: z_L or z_U is NULL"; return RPM_E_INVALID; }
+  if (!h->solved) { h->err = "rpm_ipm_get_bound_multipliers: no solve has finished"; return RPM_E_INVALID; }
+  ipm_launch_bound_multipliers(h->D, d_z_L, d_z_U, static_cast<hipStream_t>(stream));
+  return launch_check(h, "ipm_bound_mult_kernel");
+}
+
+int rpm_ipm_get_bound_multipliers(rpm_ipm* h, double* z_L, double* z_U) {
+  if (!h) return RPM_E_INVALID;
+  if (!z_L || !z_U) { h->err = "rpm_ipm_get_bound_multipliers: z_L or z_U is NULL"; return RPM_E_INVALID; }
+  if (!h->solved) { h->err = "rpm_ipm_get_bound_multipliers: no solve has finished"; return RPM_E_INVALID; }
+  Engine& e = h->eng->e;
+  hipStream_t st = static_cast<hipStream_t>(dev_stream(e));
+  double *d_x, *d_l, *d_zL, *d_zU;
+  int rc = host_form(h, &d_x, &d_l, &d_zL, &d_zU);
+  if (rc) return rc;
+  const size_t Bn = size_t(h->D.B) * h->plan.n;
+  ipm_launch_bound_multipliers(h->D, d_zL, d_zU, st);
+  if ((rc = launch_check(h, "ipm_bound_mult_kernel"))) return rc;
+  rc = dev_download(e, z_L, d_zL, Bn, STAGE_X);
+  if (!rc) rc = dev_download(e, z_U, d_zU, Bn, STAGE_G);
+  if (rc) h->err = e.err;
+  return rc;
 }
 
 int rpm_ipm_solve(rpm_ipm* h, double* x, double* lambda, double* obj, int* status, int* iterations, double* kkt_error) {
   if (!h || !x) return RPM_E_INVALID;
   IpmDev& D = h->D;
   const IpmPlan& p = h->plan;
-  double *d_x = nullptr, *d_l = nullptr;
-  IPM_TRY(h, hipMalloc(reinterpret_cast<void**>(&d_x), size_t(D.B) * p.n * sizeof(double)));
-  if (hipMalloc(reinterpret_cast<void**>(&d_l), size_t(D.B) * std::max(p.m, 1) * sizeof(double)) != hipSuccess) {
-    (void)hipFree(d_x);
-    h->err = "hipMalloc";
-    return RPM_E_DEVICE;
-  }
+  double *d_x, *d_l, *d_zL, *d_zU;
+  int rc = host_form(h, &d_x, &d_l, &d_zL, &d_zU);
+  if (rc) return rc;
   // x / lambda are the caller's arrays: through the engine's staging slots (or its page-lock registrations)
   Engine& e = h->eng->e;
-  int rc = dev_upload(e, d_x, x, size_t(D.B) * p.n, STAGE_X);
+  rc = dev_upload(e, d_x, x, size_t(D.B) * p.n, STAGE_X);
   if (!rc) rc = dev_sync(e);                                                                   // nothing in flight when the solve starts
   if (rc) h->err = e.err;
   if (!rc) rc = rpm_ipm_solve_dev(h, d_x, d_l, obj, status, iterations, kkt_error, nullptr);
@@ -894,9 +974,71 @@ int rpm_ipm_solve(rpm_ipm* h, double* x, double* lambda, double* obj, int* statu
     if (!rc && lambda) rc = dev_download(e, lambda, d_l, size_t(D.B) * p.m, STAGE_LAMBDA);
     if (rc) h->err = e.err;
   }
-  (void)hipFree(d_x);
-  (void)hipFree(d_l);
   return rc;
+}
+
+int rpm_ipm_solve_warm(rpm_ipm* h, double* x, double* lambda, double* z_L, double* z_U, double* obj, int* status, int* iterations,
+                       double* kkt_error) {
+  if (!h) return RPM_E_INVALID;
+  if (!x || !lambda) { h->err = "rpm_ipm_solve_warm: x and lambda are required"; return RPM_E_INVALID; }
+  if (!z_L != !z_U) { h->err = "rpm_ipm_solve_warm: z_L and z_U are given together or both NULL"; return RPM_E_INVALID; }
+  Engine& e = h->eng->e;
+  const size_t Bn = size_t(h->D.B) * h->plan.n, Bm = size_t(h->D.B) * h->plan.m;
+  double *d_x, *d_l, *d_zL, *d_zU;
+  int rc = host_form(h, &d_x, &d_l, &d_zL, &d_zU);
+  if (rc) return rc;
+  rc = dev_upload(e, d_x, x, Bn, STAGE_X);
+  if (!rc) rc = dev_upload(e, d_l, lambda, Bm, STAGE_LAMBDA);
+  if (!rc && z_L) rc = dev_upload(e, d_zL, z_L, Bn, STAGE_G);
+  if (!rc && z_L) rc = dev_upload(e, d_zU, z_U, Bn, STAGE_GRAD);
+  if (!rc) rc = dev_sync(e);                                                                   // nothing in flight when the solve starts
+  if (rc) { h->err = e.err; return rc; }
+  rc = ipm_solve_dev(h, true, d_x, d_l, z_L ? d_zL : nullptr, z_L ? d_zU : nullptr, obj, status, iterations, kkt_error, nullptr);
+  if (rc) return rc;
+  rc = dev_download(e, x, d_x, Bn, STAGE_X);
+  if (!rc) rc = dev_download(e, lambda, d_l, Bm, STAGE_LAMBDA);
+  if (!rc && z_L) rc = dev_download(e, z_L, d_zL, Bn, STAGE_G);
+  if (!rc && z_L) rc = dev_download(e, z_U, d_zU, Bn, STAGE_GRAD);
+  if (rc) h->err = e.err;
+  return rc;
+}
+
+/* test hook: exactly the launches that precede the iteration loop (warm = 0: the cold start, lambda / z_L / z_U ignored), then the
+ * state: v (B x nv: x, slacks), zL, zU (B x nv), lambda (B x m), mu (B), status (B: 0, or 5 after a non-finite input); outputs may be
+ * NULL.  No step is taken. */
+int rpm_ipm_debug_start(rpm_ipm* h, int warm, const double* x, const double* lambda, const double* z_L, const double* z_U,
+                        double* v_out, double* zL_out, double* zU_out, double* lam_out, double* mu_out, int* status_out) {
+  if (!h) return RPM_E_INVALID;
+  if (!x || (warm && !lambda)) { h->err = "rpm_ipm_debug_start: x (and, warm, lambda) are required"; return RPM_E_INVALID; }
+  if (warm && (!z_L != !z_U)) { h->err = "rpm_ipm_debug_start: z_L and z_U are given together or both NULL"; return RPM_E_INVALID; }
+  Engine& e = h->eng->e;
+  IpmDev& D = h->D;
+  hipStream_t st = static_cast<hipStream_t>(dev_stream(e));
+  const size_t B = size_t(D.B), Bn = B * h->plan.n, Bm = B * h->plan.m, Bv = B * h->plan.nv;
+  double *d_x, *d_l, *d_zL, *d_zU;
+  int rc = host_form(h, &d_x, &d_l, &d_zL, &d_zU);
+  if (rc) return rc;
+  IPM_TRY(h, hipMemcpyAsync(d_x, x, Bn * sizeof(double), hipMemcpyHostToDevice, st));
+  if (warm) IPM_TRY(h, hipMemcpyAsync(d_l, lambda, Bm * sizeof(double), hipMemcpyHostToDevice, st));
+  if (warm && z_L) {
+    IPM_TRY(h, hipMemcpyAsync(d_zL, z_L, Bn * sizeof(double), hipMemcpyHostToDevice, st));
+    IPM_TRY(h, hipMemcpyAsync(d_zU, z_U, Bn * sizeof(double), hipMemcpyHostToDevice, st));
+  }
+  IPM_TRY(h, hipStreamSynchronize(st));
+  h->solved = false;   // D.v, D.zL, D.zU and D.lam are about to hold a start state, not a solve's result
+  if ((rc = ipm_start(h, warm != 0, d_x, d_l, warm && z_L ? d_zL : nullptr, warm && z_L ? d_zU : nullptr, st))) return rc;
+  IPM_TRY(h, hipStreamSynchronize(st));
+  if (v_out) IPM_TRY(h, hipMemcpy(v_out, D.v, Bv * sizeof(double), hipMemcpyDeviceToHost));
+  if (zL_out) IPM_TRY(h, hipMemcpy(zL_out, D.zL, Bv * sizeof(double), hipMemcpyDeviceToHost));
+  if (zU_out) IPM_TRY(h, hipMemcpy(zU_out, D.zU, Bv * sizeof(double), hipMemcpyDeviceToHost));
+  if (lam_out) IPM_TRY(h, hipMemcpy(lam_out, D.lam, Bm * sizeof(double), hipMemcpyDeviceToHost));
+  std::vector<IpmInst> inst(B);
+  IPM_TRY(h, hipMemcpy(inst.data(), D.inst, B * sizeof(IpmInst), hipMemcpyDeviceToHost));
+  for (size_t bi = 0; bi < B; ++bi) {
+    if (mu_out) mu_out[bi] = inst[bi].mu;
+    if (status_out) status_out[bi] = inst[bi].status;
+  }
+  return RPM_OK;
 }
 
 }  // extern "C"

@@ -106,20 +106,24 @@ __device__ inline bool reduce_and_combine(const IpmDev& D, int bi, double* sh, R
 // x pushed into the interior of its bounds (Ipopt 3.12 bound_push / bound_frac, paper section 3.6), z = 1, lambda = 0.  The
 // bounds themselves first move out by bound_relax * max(1, |bound|) (Ipopt's bound_relax_factor): vl0 / vu0 keep the caller's.
 __device__ inline double relax(double bound, const IpmOpts& o) { return o.bound_relax * fmax(1.0, fabs(bound)); }
-__device__ inline double push_inside(double x, double l, double u, bool lo, bool up, const IpmOpts& o) {
+__device__ inline double push_inside(double x, double l, double u, bool lo, bool up, double push, double frac) {
   if (lo) {
-    const double p = up ? fmin(o.bound_push * fmax(1.0, fabs(l)), o.bound_frac * (u - l)) : o.bound_push * fmax(1.0, fabs(l));
+    const double p = up ? fmin(push * fmax(1.0, fabs(l)), frac * (u - l)) : push * fmax(1.0, fabs(l));
     x = fmax(x, l + p);
   }
   if (up) {
-    const double p = lo ? fmin(o.bound_push * fmax(1.0, fabs(u)), o.bound_frac * (u - l)) : o.bound_push * fmax(1.0, fabs(u));
+    const double p = lo ? fmin(push * fmax(1.0, fabs(u)), frac * (u - l)) : push * fmax(1.0, fabs(u));
     x = fmin(x, u - p);
   }
   return x;
 }
-__global__ __launch_bounds__(256) void ipm_init_kernel(IpmDev D, const double* x0) {
+// The cold start (warm = 0: bound_push / bound_frac, z = 1, lambda = 0, least-squares multipliers where the option asks) and the
+// warm start (warm = 1: the warm_start_* pushes; the duals are ipm_warm_duals_kernel's, after the scaling factors exist) share the
+// bounds, the fixed / free pattern, the push rule and the fresh instance record.
+__global__ __launch_bounds__(256) void ipm_init_kernel(IpmDev D, const double* x0, int warm) {
   const int bi = blockIdx.x;
   const size_t o = size_t(bi) * D.nv;
+  const double push = warm ? D.o.ws_bound_push : D.o.bound_push, frac = warm ? D.o.ws_bound_frac : D.o.bound_frac;
   for (int i = threadIdx.x; i < D.n; i += blockDim.x) {
     double x = x0[size_t(bi) * D.n + i];
     double l = D.vl0[o + i], u = D.vu0[o + i];
@@ -128,25 +132,29 @@ __global__ __launch_bounds__(256) void ipm_init_kernel(IpmDev D, const double* x
     else {
       if (lo) l -= relax(l, D.o);
       if (up) u += relax(u, D.o);
-      x = push_inside(x, l, u, lo, up, D.o);
+      x = push_inside(x, l, u, lo, up, push, frac);
     }
     D.v[o + i] = x;
     D.vl[o + i] = l;
     D.vu[o + i] = u;
-    D.zL[o + i] = lo ? 1.0 : 0.0;
-    D.zU[o + i] = up ? 1.0 : 0.0;
+    if (!warm) {
+      D.zL[o + i] = lo ? 1.0 : 0.0;
+      D.zU[o + i] = up ? 1.0 : 0.0;
+    }
   }
-  for (int r = threadIdx.x; r < D.m; r += blockDim.x) D.lam[size_t(bi) * D.m + r] = 0.0;
+  if (!warm)
+    for (int r = threadIdx.x; r < D.m; r += blockDim.x) D.lam[size_t(bi) * D.m + r] = 0.0;
   if (threadIdx.x == 0) {
     IpmInst& S = D.inst[bi];
     S = IpmInst{};
     S.mu = D.o.mu_init;
-    if (D.o.init_ls_mult && D.m > 0) { S.mode = 3; S.skip_update = -2; }   // first pass: least-squares multipliers at the starting point
+    if (!warm && D.o.init_ls_mult && D.m > 0) { S.mode = 3; S.skip_update = -2; }   // first pass: least-squares multipliers at the starting point
   }
 }
 // slacks start at g(x0), pushed inside the (relaxed) [g_l, g_u] the same way
-__global__ __launch_bounds__(256) void ipm_init_slack_kernel(IpmDev D) {
+__global__ __launch_bounds__(256) void ipm_init_slack_kernel(IpmDev D, int warm) {
   const int bi = blockIdx.x;
+  const double push = warm ? D.o.ws_slack_bound_push : D.o.bound_push, frac = warm ? D.o.ws_slack_bound_frac : D.o.bound_frac;
   for (int s = threadIdx.x; s < D.ns; s += blockDim.x) {
     const int r = D.slack_row[s];
     double l = D.gl[r], u = D.gu[r];
@@ -159,12 +167,75 @@ __global__ __launch_bounds__(256) void ipm_init_slack_kernel(IpmDev D) {
     if (lo) l -= relax(l, D.o);
     if (up) u += relax(u, D.o);
     const size_t o = size_t(bi) * D.nv + D.n + s;
-    D.v[o] = push_inside(D.g[size_t(bi) * D.sg + r], l, u, lo, up, D.o);
+    D.v[o] = push_inside(D.g[size_t(bi) * D.sg + r], l, u, lo, up, push, frac);
     D.vl[o] = l;
     D.vu[o] = u;
-    D.zL[o] = lo ? 1.0 : 0.0;
-    D.zU[o] = up ? 1.0 : 0.0;
+    if (!warm) {
+      D.zL[o] = lo ? 1.0 : 0.0;
+      D.zU[o] = up ? 1.0 : 0.0;
+    }
   }
+}
+// The warm start's duals, after ipm_init_slack_kernel and (nlp_scaling) the scaling factors.  lambda: the caller's, clipped to
+// +-warm_start_mult_init_max, then into the scaled problem, (lambda sf) / sc.  z of a variable: the caller's raised to
+// warm_start_mult_bound_push, then times sf — or, z_L / z_U NULL, mu_init over the distance of the pushed x to its relaxed bound —
+// where the bound exists and the variable is free, else 0.  z of the slack of row r from its stationarity -lambda_r - zL + zU = 0:
+// zL = max(-lambda_r, floor), zU = max(lambda_r, floor) where the bound exists.  A NaN or Inf in x0 (n per instance), lambda or z ends
+// the instance with status 5 before its first pass.
+__device__ inline double dual_floor(double z, const IpmOpts& o) { return fmax(z, o.ws_mult_bound_push); }
+__global__ __launch_bounds__(256) void ipm_warm_duals_kernel(IpmDev D, const double* x0, const double* lam_in, const double* zL_in,
+                                                             const double* zU_in) {
+  const int bi = blockIdx.x;
+  const size_t o = size_t(bi) * D.nv;
+  const double sf = D.scal_on ? D.sf[bi] : 1.0;
+  const double* vl = D.vl + o, *vu = D.vu + o;
+  int bad = 0;
+  for (int r = threadIdx.x; r < D.m; r += blockDim.x) {
+    double lam = lam_in[size_t(bi) * D.m + r];
+    bad |= nonfinite(lam);
+    lam = fmax(fmin(lam, D.o.ws_mult_init_max), -D.o.ws_mult_init_max);
+    if (D.scal_on) lam = (lam * sf) / D.sc[size_t(bi) * D.m + r];
+    D.lam[size_t(bi) * D.m + r] = lam;
+    const int s = D.row_slack[r];
+    if (s >= 0) {
+      const double l = vl[D.n + s], u = vu[D.n + s];
+      D.zL[o + D.n + s] = l > -IPM_INF ? dual_floor(-lam, D.o) : 0.0;
+      D.zU[o + D.n + s] = u < IPM_INF ? dual_floor(lam, D.o) : 0.0;
+    }
+  }
+  for (int i = threadIdx.x; i < D.n; i += blockDim.x) {
+    const double l = vl[i], u = vu[i], x = D.v[o + i];
+    const bool lo = has_lo(l, u), up = has_up(l, u);
+    bad |= nonfinite(x0[size_t(bi) * D.n + i]);
+    double zl, zu;
+    if (zL_in) {
+      zl = zL_in[size_t(bi) * D.n + i];
+      zu = zU_in[size_t(bi) * D.n + i];
+      bad |= nonfinite(zl) || nonfinite(zu);
+      zl = dual_floor(zl, D.o);
+      zu = dual_floor(zu, D.o);
+      if (D.scal_on) { zl *= sf; zu *= sf; }
+    } else {
+      zl = D.o.mu_init / (x - l);
+      zu = D.o.mu_init / (u - x);
+    }
+    D.zL[o + i] = lo ? zl : 0.0;
+    D.zU[o + i] = up ? zu : 0.0;
+  }
+  if (__syncthreads_or(bad) && threadIdx.x == 0) D.inst[bi].status = 5;
+}
+// the multipliers of the variables' bounds as the caller's (unscaled) problem has them: z / sf, 0 where there is no bound or the
+// variable is fixed; instance-major B x n
+__global__ void ipm_bound_mult_kernel(IpmDev D, double* zL_out, double* zU_out) {
+  const int bi = blockIdx.y;
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= D.n) return;
+  const size_t o = size_t(bi) * D.nv + i;
+  const double l = D.vl[o], u = D.vu[o];
+  double zl = has_lo(l, u) ? D.zL[o] : 0.0, zu = has_up(l, u) ? D.zU[o] : 0.0;
+  if (D.scal_on) { const double sf = D.sf[bi]; zl /= sf; zu /= sf; }
+  zL_out[size_t(bi) * D.n + i] = zl;
+  zU_out[size_t(bi) * D.n + i] = zu;
 }
 __global__ void ipm_pack_x_kernel(IpmDev D) {
   const int bi = blockIdx.y;
@@ -812,11 +883,17 @@ static unsigned vec_threads(const IpmDev& D) { return D.B <= 32 && D.nv >= 4096 
 static unsigned vec_blocks(const IpmDev& D) {
   return D.B <= 32 && D.nv >= 4096 ? unsigned(std::min(IPM_VEC_BLOCKS, (std::max(D.nv, D.m) + 1023) / 1024)) : 1u;
 }
-void ipm_launch_init(const IpmDev& D, const double* d_x0, hipStream_t st) {
-  hipLaunchKernelGGL(ipm_init_kernel, dim3(unsigned(D.B)), dim3(256), 0, st, D, d_x0);
+void ipm_launch_init(const IpmDev& D, const double* d_x0, hipStream_t st, int warm) {
+  hipLaunchKernelGGL(ipm_init_kernel, dim3(unsigned(D.B)), dim3(256), 0, st, D, d_x0, warm);
 }
-void ipm_launch_init_slack(const IpmDev& D, hipStream_t st) {
-  hipLaunchKernelGGL(ipm_init_slack_kernel, dim3(unsigned(D.B)), dim3(256), 0, st, D);
+void ipm_launch_init_slack(const IpmDev& D, hipStream_t st, int warm) {
+  hipLaunchKernelGGL(ipm_init_slack_kernel, dim3(unsigned(D.B)), dim3(256), 0, st, D, warm);
+}
+void ipm_launch_warm_duals(const IpmDev& D, const double* d_x0, const double* d_lambda, const double* d_zL, const double* d_zU, hipStream_t st) {
+  hipLaunchKernelGGL(ipm_warm_duals_kernel, dim3(unsigned(D.B)), dim3(256), 0, st, D, d_x0, d_lambda, d_zL, d_zU);
+}
+void ipm_launch_bound_multipliers(const IpmDev& D, double* d_zL, double* d_zU, hipStream_t st) {
+  hipLaunchKernelGGL(ipm_bound_mult_kernel, dim3(unsigned((D.n + 255) / 256), unsigned(D.B)), dim3(256), 0, st, D, d_zL, d_zU);
 }
 void ipm_launch_pack_x(const IpmDev& D, hipStream_t st) {
   hipLaunchKernelGGL(ipm_pack_x_kernel, dim3(unsigned((D.n + 255) / 256), unsigned(D.B)), dim3(256), 0, st, D);

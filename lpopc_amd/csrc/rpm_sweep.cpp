@@ -144,6 +144,41 @@ int rpm_sweep_solve(rpm_sweep* s, double* x, double* lambda, double* obj, int* s
       [&](size_t r) { return rpm_ipm_last_error(s->ipm[r]); });
 }
 
+/* rpm_ipm_solve_warm over all shares at once: x B x n, lambda B x m (required), z_L / z_U B x n (both or neither), all in/out */
+int rpm_sweep_solve_warm(rpm_sweep* s, double* x, double* lambda, double* z_L, double* z_U, double* obj, int* status, int* iterations,
+                         double* kkt_error) {
+  if (!s) return RPM_E_INVALID;
+  if (!x || !lambda || (!z_L != !z_U)) {
+    s->err = (!x || !lambda) ? "rpm_sweep_solve_warm: x and lambda are required" : "rpm_sweep_solve_warm: z_L and z_U are given together or both NULL";
+    return RPM_E_INVALID;
+  }
+  return for_each_share(
+      s,
+      [&](size_t r) {
+        const size_t i0 = size_t(s->first[r]);
+        return rpm_ipm_solve_warm(s->ipm[r], x + i0 * s->n, lambda + i0 * s->m, z_L ? z_L + i0 * s->n : nullptr,
+                                  z_U ? z_U + i0 * s->n : nullptr, obj ? obj + i0 : nullptr, status ? status + i0 : nullptr,
+                                  iterations ? iterations + i0 : nullptr, kkt_error ? kkt_error + i0 : nullptr);
+      },
+      [&](size_t r) { return rpm_ipm_last_error(s->ipm[r]); });
+}
+
+/* rpm_ipm_get_bound_multipliers of every share: z_L, z_U B x n */
+int rpm_sweep_get_bound_multipliers(rpm_sweep* s, double* z_L, double* z_U) {
+  if (!s) return RPM_E_INVALID;
+  if (!z_L || !z_U) {
+    s->err = "rpm_sweep_get_bound_multipliers: z_L or z_U is NULL";
+    return RPM_E_INVALID;
+  }
+  return for_each_share(
+      s,
+      [&](size_t r) {
+        const size_t i0 = size_t(s->first[r]);
+        return rpm_ipm_get_bound_multipliers(s->ipm[r], z_L + i0 * s->n, z_U + i0 * s->n);
+      },
+      [&](size_t r) { return rpm_ipm_last_error(s->ipm[r]); });
+}
+
 /* The mesh-error estimate of the whole sweep (rpm_solution_error_batch on every share, side by side).  x: B x n; instance_mask:
  * B or NULL; any result may be NULL: interval_error B x KT, rel_err_max RT, rel_err B x RT, nonfinite B.  rel_err_max is the
  * element-wise maximum of the shares' blocks (a maximum: what one engine holding all B instances returns, bit for bit); a share
@@ -209,6 +244,28 @@ int rpm_sweep_carry_solution(rpm_sweep* from, rpm_sweep* to, const double* x_fro
       [&](size_t r) {
         const size_t i0 = size_t(from->first[r]);
         return rpm_carry_solution_batch(from->eng[r], to->eng[r], x_from + i0 * from->n, x_to + i0 * to->n, nonfinite ? nonfinite + i0 : nullptr);
+      },
+      [&](size_t r) { return rpm_last_error(from->eng[r]); });
+}
+
+/* rpm_carry_multipliers_batch on every share, side by side: x_from B x from.n, lambda_from B x from.m, lambda_to B x to.m */
+int rpm_sweep_carry_multipliers(rpm_sweep* from, rpm_sweep* to, const double* x_from, const double* lambda_from, double* lambda_to,
+                                int* nonfinite) {
+  if (!from) return RPM_E_INVALID;
+  if (!to || !x_from || !lambda_from || !lambda_to) {
+    from->err = !to ? "rpm_sweep_carry_multipliers: the target sweep is NULL" : "rpm_sweep_carry_multipliers: x_from, lambda_from or lambda_to is NULL";
+    return RPM_E_INVALID;
+  }
+  if (from->B != to->B || from->dev != to->dev || from->count != to->count) {
+    from->err = "rpm_sweep_carry_multipliers: the sweeps have different shares (devices or instance counts)";
+    return RPM_E_INVALID;
+  }
+  return for_each_share(
+      from,
+      [&](size_t r) {
+        const size_t i0 = size_t(from->first[r]);
+        return rpm_carry_multipliers_batch(from->eng[r], to->eng[r], x_from + i0 * from->n, lambda_from + i0 * from->m,
+                                           lambda_to + i0 * to->m, nonfinite ? nonfinite + i0 : nullptr);
       },
       [&](size_t r) { return rpm_last_error(from->eng[r]); });
 }

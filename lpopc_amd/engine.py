@@ -31,6 +31,9 @@ ABI_SYMBOLS = [
     "rpm_solution_error", "rpm_ph_refine_mesh", "rpm_ph_refine_from_error",
     "rpm_solution_error_batch_sizes", "rpm_solution_error_batch_dev", "rpm_solution_error_batch", "rpm_sweep_solution_error",
     "rpm_carry_solution_batch_dev", "rpm_carry_solution_batch", "rpm_sweep_carry_solution",
+    "rpm_carry_multipliers_batch_dev", "rpm_carry_multipliers_batch", "rpm_carry_multipliers_layout", "rpm_sweep_carry_multipliers",
+    "rpm_ipm_solve_warm", "rpm_ipm_solve_warm_dev", "rpm_ipm_get_bound_multipliers", "rpm_ipm_get_bound_multipliers_dev",
+    "rpm_ipm_debug_start", "rpm_sweep_solve_warm", "rpm_sweep_get_bound_multipliers",
     "rpm_nlp2op_batch_layout", "rpm_nlp2op_batch_dev", "rpm_nlp2op_batch", "rpm_sweep_nlp2op",
     "rpm_hpliu_create", "rpm_hpliu_destroy", "rpm_hpliu_last_error", "rpm_hpliu_refine",
     "rpm_ipm_create", "rpm_ipm_destroy", "rpm_ipm_last_error", "rpm_ipm_set_option", "rpm_ipm_set_bounds", "rpm_ipm_set_all_bounds", "rpm_ipm_get_info",
@@ -116,6 +119,10 @@ def lib(path=None):
     L.rpm_carry_solution_batch_dev.argtypes = [vp, vp, vp, vp, vp, vp]
     L.rpm_carry_solution_batch.argtypes = [vp, vp, dp, dp, ip]
     L.rpm_sweep_carry_solution.argtypes = [vp, vp, dp, dp, ip]
+    L.rpm_carry_multipliers_batch_dev.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+    L.rpm_carry_multipliers_batch.argtypes = [vp, vp, dp, dp, dp, ip]
+    L.rpm_carry_multipliers_layout.argtypes = [vp, C.c_int, ip]
+    L.rpm_sweep_carry_multipliers.argtypes = [vp, vp, dp, dp, dp, ip]
     L.rpm_nlp2op_batch_layout.argtypes = [vp, C.c_int, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
     L.rpm_nlp2op_batch_dev.argtypes = [vp, vp, vp, vp, vp, vp]
     L.rpm_nlp2op_batch.argtypes = [vp, dp, dp, dp, ip]
@@ -142,6 +149,11 @@ def lib(path=None):
     L.rpm_ipm_get_kernel_times.argtypes = [vp, dp, dp]
     L.rpm_ipm_solve.argtypes = [vp, dp, dp, dp, ip, ip, dp]
     L.rpm_ipm_solve_dev.argtypes = [vp, vp, vp, dp, ip, ip, dp, vp]
+    L.rpm_ipm_solve_warm.argtypes = [vp, dp, dp, dp, dp, dp, ip, ip, dp]
+    L.rpm_ipm_solve_warm_dev.argtypes = [vp, vp, vp, vp, vp, dp, ip, ip, dp, vp]
+    L.rpm_ipm_get_bound_multipliers.argtypes = [vp, dp, dp]
+    L.rpm_ipm_get_bound_multipliers_dev.argtypes = [vp, vp, vp, vp]
+    L.rpm_ipm_debug_start.argtypes = [vp, C.c_int, dp, dp, dp, dp, dp, dp, dp, dp, dp, ip]
     L.rpm_ipm_get_permutation.argtypes = [vp, ip, C.c_int]
     L.rpm_ipm_debug_solve.argtypes = [vp, dp, dp, dp, ip, ip]
     L.rpm_ipm_debug_solve_dense.argtypes = [vp, dp, dp, dp, ip, ip]
@@ -188,6 +200,8 @@ def lib(path=None):
     L.rpm_sweep_set_bounds.argtypes = [vp, C.c_int, dp, dp]
     L.rpm_sweep_solve.argtypes = [vp, dp, dp, dp, ip, ip, dp]
     L.rpm_sweep_get_stats.argtypes = [vp, ip, ip, ip]
+    L.rpm_sweep_solve_warm.argtypes = [vp, dp, dp, dp, dp, dp, ip, ip, dp]
+    L.rpm_sweep_get_bound_multipliers.argtypes = [vp, dp, dp]
     _LIBS[so] = L
     if so == _SO:
         _LIB = L
@@ -588,6 +602,34 @@ class NLPEngine:
         self._check(self._L.rpm_carry_solution_batch_dev(self._h, to._h, self._ptr(d_x), self._ptr(d_x_to), self._ptr(d_nonfinite),
                                                          self._stream(stream)))
 
+    # ---- the sweep's constraint multipliers carried onto another mesh (rpm_carry_multipliers_batch*) ---------------------
+    def carry_multipliers_layout(self):
+        """The row map of the multiplier carry, host only: (n_phases + 1) x 4 — per phase the first defect row, the first path
+        row, the first event row and one past its last row; the last line: the rows after the phases, [first] * 3 + [m]."""
+        rows = np.zeros((self.n_phases + 1, 4), dtype=np.int32)
+        for p in range(self.n_phases + 1):
+            self._check(self._L.rpm_carry_multipliers_layout(self._h, p, _ip(rows[p])))
+        return rows
+
+    def carry_multipliers_batch(self, to, x, lam):
+        """The multipliers lam (n_instances x m) of this engine's solutions x carried as costates / path-multiplier densities
+        onto the mesh of engine `to` -> (lambda_to: n_instances x to.m, a warm solve's starting lambda; nonfinite)."""
+        if self._L is not to._L:
+            raise RpmError(RPM_E_INVALID, "carry_multipliers_batch: the engines must come from one native library")
+        x = self._x(x)
+        lam = np.ascontiguousarray(lam, dtype=np.float64).ravel()
+        if lam.size != self.n_instances * self.m:
+            raise RpmError(RPM_E_INVALID, "lambda has %d entries, expected %d" % (lam.size, self.n_instances * self.m))
+        out = np.zeros((self.n_instances, to.m))
+        flags = np.zeros(self.n_instances, dtype=np.int32)
+        self._check(self._L.rpm_carry_multipliers_batch(self._h, to._h, _dp(x), _dp(lam), _dp(out), _ip(flags)))
+        return out, flags
+
+    def carry_multipliers_batch_dev(self, to, d_x, d_lambda, d_lambda_to, d_nonfinite=None, stream=None):
+        """Device-resident form on torch CUDA tensors (float64; d_nonfinite int32).  Asynchronous on `stream`."""
+        self._check(self._L.rpm_carry_multipliers_batch_dev(self._h, to._h, self._ptr(d_x), self._ptr(d_lambda), self._ptr(d_lambda_to),
+                                                            self._ptr(d_nonfinite), self._stream(stream)))
+
     # ---- the extraction of a whole sweep: all phases, all instances (rpm_nlp2op_batch*) ---------------------------------
     def nlp2op_batch_layout(self):
         """(offsets, EB): per phase the offsets of time, state, control, costate, pathmult, hamiltonian, mayer_cost and
@@ -857,23 +899,71 @@ class BatchedIPM:
         self._chk(self._L.rpm_ipm_debug_lbfgs_solve(self._h, rows.size, _ip(rows), _ip(cols), _dp(v), _dp(r), _dp(sol)))
         return sol
 
-    def solve(self, x0):
-        """x0: (n_instances, n) starting points -> dict(x, lambda, obj, status, iterations, kkt_error)."""
+    def solve(self, x0, lam0=None, z0=None):
+        """x0: (n_instances, n) starting points -> dict(x, lambda, obj, status, iterations, kkt_error).  lam0 (n_instances, m):
+        warm start in the primal and the dual (rpm_ipm_solve_warm); z0 = (z_L, z_U), (n_instances, n) each, or None: the bound
+        multipliers from mu_init.  With z0 the dict also holds z_L and z_U."""
         B, n, m = self._e.n_instances, self._e.n, self._e.m
         x = np.array(x0, dtype=np.float64, order="C").reshape(B, n)
-        lam = np.zeros((B, max(m, 1)))[:, :m].copy()
         obj, err = np.zeros(B), np.zeros(B)
         status, iters = np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.int32)
-        self._chk(self._L.rpm_ipm_solve(self._h, _dp(x), _dp(lam), _dp(obj), _ip(status), _ip(iters), _dp(err)))
-        return {"x": x, "lambda": lam, "obj": obj, "status": status, "iterations": iters, "kkt_error": err}
+        if lam0 is None:
+            if z0 is not None:
+                raise RpmError(RPM_E_INVALID, "solve: z0 needs lam0")
+            lam = np.zeros((B, max(m, 1)))[:, :m].copy()
+            self._chk(self._L.rpm_ipm_solve(self._h, _dp(x), _dp(lam), _dp(obj), _ip(status), _ip(iters), _dp(err)))
+            return {"x": x, "lambda": lam, "obj": obj, "status": status, "iterations": iters, "kkt_error": err}
+        lam = np.array(lam0, dtype=np.float64, order="C").reshape(B, m)
+        out = {"x": x, "lambda": lam, "obj": obj, "status": status, "iterations": iters, "kkt_error": err}
+        zl = zu = None
+        if z0 is not None:
+            zl, zu = (np.array(z, dtype=np.float64, order="C").reshape(B, n) for z in z0)
+            out["z_L"], out["z_U"] = zl, zu
+        self._chk(self._L.rpm_ipm_solve_warm(self._h, _dp(x), _dp(lam), None if zl is None else _dp(zl), None if zu is None else _dp(zu),
+                                             _dp(obj), _ip(status), _ip(iters), _dp(err)))
+        return out
 
-    def solve_dev(self, d_x, d_lambda=None, stream=None):
+    def bound_multipliers(self):
+        """(z_L, z_U), (n_instances, n) each: the multipliers of the variables' bounds after the last solve, unscaled."""
+        B, n = self._e.n_instances, self._e.n
+        zl, zu = np.zeros((B, n)), np.zeros((B, n))
+        self._chk(self._L.rpm_ipm_get_bound_multipliers(self._h, _dp(zl), _dp(zu)))
+        return zl, zu
+
+    def bound_multipliers_dev(self, d_z_L, d_z_U, stream=None):
+        self._chk(self._L.rpm_ipm_get_bound_multipliers_dev(self._h, C.c_void_p(d_z_L.data_ptr()), C.c_void_p(d_z_U.data_ptr()),
+                                                            NLPEngine._stream(stream)))
+
+    def debug_start(self, x0, lam0=None, z0=None, warm=True):
+        """The state the iteration loop starts from (rpm_ipm_debug_start; no step is taken): dict(v (B, nv): x then the slacks,
+        zL, zU (B, nv), lambda (B, m), mu (B), status (B)).  warm=False: the cold start (lam0, z0 ignored)."""
+        B, n, m = self._e.n_instances, self._e.n, self._e.m
+        nv = n + self.info()["n_slacks"]
+        x = np.array(x0, dtype=np.float64, order="C").reshape(B, n)
+        lam = None if lam0 is None else np.array(lam0, dtype=np.float64, order="C").reshape(B, m)
+        zl, zu = (None, None) if z0 is None else (np.array(z, dtype=np.float64, order="C").reshape(B, n) for z in z0)
+        out = {"v": np.zeros((B, nv)), "zL": np.zeros((B, nv)), "zU": np.zeros((B, nv)), "lambda": np.zeros((B, m)), "mu": np.zeros(B),
+               "status": np.zeros(B, dtype=np.int32)}
+        opt = lambda a: None if a is None else _dp(a)
+        self._chk(self._L.rpm_ipm_debug_start(self._h, int(bool(warm)), _dp(x), opt(lam), opt(zl), opt(zu), _dp(out["v"]), _dp(out["zL"]),
+                                              _dp(out["zU"]), _dp(out["lambda"]), _dp(out["mu"]), _ip(out["status"])))
+        return out
+
+    def solve_dev(self, d_x, d_lambda=None, stream=None, d_z_L=None, d_z_U=None, warm=False):
         """d_x: torch CUDA tensor (n_instances, n), overwritten with the solutions; d_lambda: optional (n_instances, m).
-        The solver waits for what is queued on `stream` (default: torch's current stream) before it touches the arrays."""
+        The solver waits for what is queued on `stream` (default: torch's current stream) before it touches the arrays.
+        warm=True: rpm_ipm_solve_warm_dev — d_lambda (required) and d_z_L / d_z_U (n_instances, n; both or neither) are read as
+        the starting duals and overwritten with the solution's."""
         B = self._e.n_instances
         obj, err = np.zeros(B), np.zeros(B)
         status, iters = np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.int32)
-        lp = C.c_void_p(d_lambda.data_ptr()) if d_lambda is not None else None
-        self._chk(self._L.rpm_ipm_solve_dev(self._h, C.c_void_p(d_x.data_ptr()), lp, _dp(obj), _ip(status), _ip(iters), _dp(err),
-                                            NLPEngine._stream(stream)))
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        if warm:
+            self._chk(self._L.rpm_ipm_solve_warm_dev(self._h, ptr(d_x), ptr(d_lambda), ptr(d_z_L), ptr(d_z_U), _dp(obj), _ip(status),
+                                                     _ip(iters), _dp(err), NLPEngine._stream(stream)))
+        else:
+            if d_z_L is not None or d_z_U is not None:
+                raise RpmError(RPM_E_INVALID, "solve_dev: d_z_L / d_z_U need warm=True")
+            self._chk(self._L.rpm_ipm_solve_dev(self._h, ptr(d_x), ptr(d_lambda), _dp(obj), _ip(status), _ip(iters), _dp(err),
+                                                NLPEngine._stream(stream)))
         return {"obj": obj, "status": status, "iterations": iters, "kkt_error": err}

@@ -177,6 +177,28 @@ class SweepGroup:
         self._check(self._L.rpm_sweep_solve(self._h, _dp(x), _dp(lam), _dp(obj), _ip(status), _ip(its), _dp(err)))
         return {"x": x, "lambda": lam[:, :self.m], "obj": obj, "status": status, "iterations": its, "kkt_error": err}
 
+    def solve_warm(self, x0, lam0, z0=None):
+        """rpm_sweep_solve_warm: as BatchedIPM.solve(x0, lam0, z0), over all shares."""
+        B = self.n_instances
+        x = np.ascontiguousarray(x0, dtype=np.float64).reshape(B, self.n).copy()
+        lam = np.ascontiguousarray(lam0, dtype=np.float64).reshape(B, self.m).copy()
+        obj, err = np.zeros(B), np.zeros(B)
+        status, its = np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.int32)
+        out = {"x": x, "lambda": lam, "obj": obj, "status": status, "iterations": its, "kkt_error": err}
+        zl = zu = None
+        if z0 is not None:
+            zl, zu = (np.ascontiguousarray(z, dtype=np.float64).reshape(B, self.n).copy() for z in z0)
+            out["z_L"], out["z_U"] = zl, zu
+        self._check(self._L.rpm_sweep_solve_warm(self._h, _dp(x), _dp(lam), None if zl is None else _dp(zl), None if zu is None else _dp(zu),
+                                                 _dp(obj), _ip(status), _ip(its), _dp(err)))
+        return out
+
+    def bound_multipliers(self):
+        """rpm_sweep_get_bound_multipliers: (z_L, z_U), B x n each, after the last solve."""
+        zl, zu = np.zeros((self.n_instances, self.n)), np.zeros((self.n_instances, self.n))
+        self._check(self._L.rpm_sweep_get_bound_multipliers(self._h, _dp(zl), _dp(zu)))
+        return zl, zu
+
     def stats(self):
         a, b, c = C.c_int(), C.c_int(), C.c_int()
         self._check(self._L.rpm_sweep_get_stats(self._h, C.byref(a), C.byref(b), C.byref(c)))
@@ -208,6 +230,19 @@ class SweepGroup:
         out = np.zeros((self.n_instances, to.n))
         flags = np.zeros(self.n_instances, dtype=np.int32)
         self._check(self._L.rpm_sweep_carry_solution(self._h, to._h, _dp(x), _dp(out), _ip(flags)))
+        return out, flags
+
+    def carry_multipliers(self, to, x, lam):
+        """rpm_sweep_carry_multipliers: the multipliers lam (B x m) of the sweep's solutions x carried onto the mesh of sweep `to`
+        -> (lambda_to: B x to.m, nonfinite: B ints); equal to one engine holding all instances bit for bit."""
+        x = np.ascontiguousarray(x, dtype=np.float64).ravel()
+        lam = np.ascontiguousarray(lam, dtype=np.float64).ravel()
+        if x.size != self.n * self.n_instances or lam.size != self.m * self.n_instances:
+            raise RpmError(RPM_E_INVALID, "x / lambda have %d / %d entries, expected %d / %d" %
+                           (x.size, lam.size, self.n * self.n_instances, self.m * self.n_instances))
+        out = np.zeros((self.n_instances, to.m))
+        flags = np.zeros(self.n_instances, dtype=np.int32)
+        self._check(self._L.rpm_sweep_carry_multipliers(self._h, to._h, _dp(x), _dp(lam), _dp(out), _ip(flags)))
         return out, flags
 
     def nlp2op(self, x, lam):

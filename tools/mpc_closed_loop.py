@@ -1,8 +1,13 @@
 """Receding-horizon demo of row f-2: B quadrotors fly to their own targets; every control period all B optimal-control
 problems (8 x 8 LGR, horizon 2 s) are re-solved on the device from the measured states, warm-started from the previous
 solutions (iterates stay in HBM: solve_dev in/out), and the first part of each plan is applied to a simple simulation
-of the same dynamics.  Prints per-step solve time and iteration counts, cold vs warm.
-python tools/mpc_closed_loop.py [instances] [steps]"""
+of the same dynamics.  Every step is solved three ways from the same measured states: cold from the problem's guess, primal-only
+warm (the previous solution shifted, small mu_init, no push: the leg that drives the simulation) and primal + dual warm
+(rpm_ipm_solve_warm_dev: its own previous solution shifted, with that solve's lambda and bound multipliers).  Prints per-step solve
+time and iteration counts of all three.
+python tools/mpc_closed_loop.py [instances] [steps] [trace]
+"trace": where the slowest primal + dual instance of a step needs more iterations than the slowest primal-only one, its accepted
+steps are printed (f, theta, mu, alpha, alpha_z, delta_w, E_0, backtracks)."""
 import os
 import sys
 import time
@@ -17,6 +22,7 @@ from lpopc_amd.problem import Options
 
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 256
 steps = int(sys.argv[2]) if len(sys.argv) > 2 else 10
+want_trace = len(sys.argv) > 3 and sys.argv[3] == "trace"
 K, NK = 8, 8
 o = Options()
 o.SetStringValue("hessian-approximation", "exact")
@@ -27,6 +33,9 @@ eng = NLPEngine(base, o, n_instances=B, device=0)
 for b in range(B):
     eng.set_instance_constants(b, problems.quadrotor(K, NK, pref=tuple(targets[b])).GetOpimalProblemFuns().consts)
 ipm = BatchedIPM(eng, tol=1e-6)
+cold_ipm, dual_ipm = BatchedIPM(eng, tol=1e-6), BatchedIPM(eng, tol=1e-6)
+if want_trace:
+    dual_ipm.set_option("trace", 64)
 one = NLPEngine(base, o, device=0)
 xl, xu, _, _ = one.get_bounds_info()
 x_guess = one.get_starting_point()
@@ -38,30 +47,65 @@ dt = 0.1
 state = np.zeros((B, 12))
 state[:, :3] = rng.uniform(-0.3, 0.3, size=(B, 3))
 XL, XU = np.tile(xl, (B, 1)), np.tile(xu, (B, 1))
-d_x = torch.from_numpy(np.tile(x_guess, (B, 1))).cuda()
+d_guess = torch.from_numpy(np.tile(x_guess, (B, 1))).cuda()
+d_x, d_x3 = d_guess.clone(), d_guess.clone()
+d_lam3 = torch.zeros((B, eng.m), dtype=torch.float64, device="cuda")
+d_zl3, d_zu3 = (torch.zeros((B, eng.n), dtype=torch.float64, device="cuda") for _ in range(2))
 t_at = (tau + 1.0) * horizon / 2.0
+
+
+def timed(fn):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    r = fn()
+    torch.cuda.synchronize()
+    return r, 1e3 * (time.perf_counter() - t0)
+
+
+def shifted(X):
+    """the plan moved on by dt: the next problem starts where this one is after dt; the rest is kept as the guess"""
+    for j in range(12):
+        traj = X[:, j * N1:(j + 1) * N1]
+        X[:, j * N1:(j + 1) * N1] = np.stack([np.interp(np.minimum(t_at + dt, horizon), t_at, traj[b]) for b in range(B)])
+    return torch.from_numpy(X)
+
+
+def leg(name, r, ms):
+    return "%s %7.1f ms  it %d..%d  ok %d/%d" % (name, ms, r["iterations"].min(), r["iterations"].max(), int((r["status"] <= 1).sum()), B)
+
+
 for step in range(steps):
     XL[:, x0_idx] = XU[:, x0_idx] = state
-    ipm.set_all_bounds(XL, XU)
+    for s_ in (ipm, cold_ipm, dual_ipm):
+        s_.set_all_bounds(XL, XU)
     if step == 1:                                     # warm starts: small barrier, do not push the previous solution away
         ipm.set_option("mu_init", 1e-4)
         ipm.set_option("bound_push", 1e-6)
         ipm.set_option("bound_frac", 1e-6)
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    r = ipm.solve_dev(d_x)
-    torch.cuda.synchronize()
-    ms = 1e3 * (time.perf_counter() - t0)
+        dual_ipm.set_option("mu_init", 1e-4)
+        for k in ("warm_start_bound_push", "warm_start_bound_frac", "warm_start_slack_bound_push", "warm_start_slack_bound_frac"):
+            dual_ipm.set_option(k, 1e-6)
+        dual_ipm.set_option("warm_start_mult_bound_push", 1e-8)
+    d_c = d_guess.clone()
+    rc, ms_c = timed(lambda: cold_ipm.solve_dev(d_c))
+    r, ms = timed(lambda: ipm.solve_dev(d_x))
+    if step == 0:                                     # no duals yet: a cold solve that keeps them
+        r3, ms3 = timed(lambda: dual_ipm.solve_dev(d_x3, d_lam3))
+        dual_ipm.bound_multipliers_dev(d_zl3, d_zu3)
+    else:
+        r3, ms3 = timed(lambda: dual_ipm.solve_dev(d_x3, d_lam3, d_z_L=d_zl3, d_z_U=d_zu3, warm=True))
     X = d_x.cpu().numpy()
     # "plant": follow the planned state trajectory for dt (the plan is dynamically consistent to the mesh accuracy)
     for j in range(12):
         traj = X[:, j * N1:(j + 1) * N1]
         state[:, j] = np.array([np.interp(dt, t_at, traj[b]) for b in range(B)])
     dist = np.linalg.norm(state[:, :3] - targets, axis=1)
-    print("step %2d  %7.1f ms for %d solves  iterations %d..%d  converged %d/%d  mean distance to target %.3f" % (
-        step, ms, B, r["iterations"].min(), r["iterations"].max(), int((r["status"] <= 1).sum()), B, dist.mean()), flush=True)
-    # shift the plan: the next problem starts where this one is after dt; keep the rest as the guess
-    for j in range(12):
-        traj = X[:, j * N1:(j + 1) * N1]
-        X[:, j * N1:(j + 1) * N1] = np.stack([np.interp(np.minimum(t_at + dt, horizon), t_at, traj[b]) for b in range(B)])
-    d_x.copy_(torch.from_numpy(X))
+    print("step %2d  %d solves  %s | %s | %s | mean distance to target %.3f" % (
+        step, B, leg("cold", rc, ms_c), leg("primal-only", r, ms), leg("primal + dual", r3, ms3), dist.mean()), flush=True)
+    if want_trace and r3["iterations"].max() > r["iterations"].max():
+        worst = int(np.argmax(r3["iterations"]))
+        print("  instance %d: primal + dual %d iterations, primal-only %d; its accepted steps:" % (worst, r3["iterations"][worst], r["iterations"][worst]))
+        for row in dual_ipm.trace(worst, 64):
+            print("   f %.9g  theta %.3e  mu %.3e  alpha %.3e  alpha_z %.3e  delta_w %.3e  E_0 %.3e  backtracks %d" % (tuple(row[:7]) + (int(row[7]),)))
+    d_x.copy_(shifted(X))
+    d_x3.copy_(shifted(d_x3.cpu().numpy()))
