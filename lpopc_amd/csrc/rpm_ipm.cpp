@@ -2,31 +2,92 @@
 #include "rpm_ipm.hpp"
 
 #include <algorithm>
+#include <cmath>
 #include <cstdint>
 #include <cstdlib>
 
 namespace rpm {
 
-constexpr int IPM_PLAN_W = 16;   // = IPM_W, the factorisation's block width (rpm_ipm_device.hpp)
-
 static int build_ipm_plan_nd(Engine& e, IpmPlan& p, std::string* why);
+
+// (key, source) pairs grouped by key, keys ascending, the sources of a key in the order they were given: dst[i] is the i-th key,
+// src[ptr[i] .. ptr[i + 1]) its sources — sums over such a list run in a fixed order
+template <class K>
+static void group_by_key(std::vector<std::pair<K, int>>& all, std::vector<int>& ptr, std::vector<int>& src, std::vector<int>& dst) {
+  std::stable_sort(all.begin(), all.end(), [](const auto& a, const auto& c) { return a.first < c.first; });
+  ptr.assign(1, 0);
+  src.clear();
+  dst.clear();
+  for (size_t i = 0; i < all.size(); ++i) {
+    if (i == 0 || all[i].first != all[i - 1].first) {
+      if (i) ptr.push_back(int(src.size()));
+      dst.push_back(int(all[i].first));
+    }
+    src.push_back(all[i].second);
+  }
+  if (!all.empty()) ptr.push_back(int(src.size()));
+}
+
+// rows: equality when g_l == g_u, otherwise one slack each (bounds g_l <= s <= g_u); variables: fixed where x_l == x_u
+static void plan_rows_and_slacks(const Engine& e, IpmPlan& p) {
+  p.row_slack.assign(p.m, -1);
+  for (int r = 0; r < p.m; ++r)
+    if (e.gl[r] != e.gu[r]) {
+      p.row_slack[r] = p.ns++;
+      p.slack_row.push_back(r);
+    }
+  p.nv = p.n + p.ns;
+  p.Nt = p.nv + p.m;
+  p.fixed.assign(p.n, 0);
+  for (int i = 0; i < p.n; ++i) p.fixed[i] = e.xl[i] == e.xu[i] ? 1 : 0;
+}
+
+// f(unknown, unknown) for every off-diagonal entry the KKT matrix keeps: the Jacobian and Hessian entries of free variables in COO
+// order, then every (row, slack) pair
+template <class F>
+static void for_each_offdiagonal(const Engine& e, const IpmPlan& p, F&& f) {
+  for (int k = 0; k < e.nnz_jac; ++k)
+    if (!p.fixed[e.jac_j[k]]) f(p.nv + e.jac_i[k], e.jac_j[k]);
+  for (int k = 0; k < e.nnz_h; ++k)
+    if (!p.fixed[e.hes_i[k]] && !p.fixed[e.hes_j[k]]) f(e.hes_i[k], e.hes_j[k]);
+  for (int s = 0; s < p.ns; ++s) f(p.nv + p.slack_row[s], p.n + s);
+}
+
+// jac_dst, hes_dst, diag_dst, slk_dst from slot(unknown, unknown); the entries of fixed variables are dropped (-1)
+template <class F>
+static void plan_slots(const Engine& e, IpmPlan& p, F&& slot) {
+  p.jac_dst.assign(e.nnz_jac, -1);
+  p.hes_dst.assign(e.nnz_h, -1);
+  for (int k = 0; k < e.nnz_jac; ++k)
+    if (!p.fixed[e.jac_j[k]]) p.jac_dst[k] = slot(p.nv + e.jac_i[k], e.jac_j[k]);
+  for (int k = 0; k < e.nnz_h; ++k)
+    if (!p.fixed[e.hes_i[k]] && !p.fixed[e.hes_j[k]]) p.hes_dst[k] = slot(e.hes_i[k], e.hes_j[k]);
+  p.diag_dst.resize(p.Nt);
+  for (int u = 0; u < p.Nt; ++u) p.diag_dst[u] = slot(u, u);
+  p.slk_dst.resize(p.ns);
+  for (int s = 0; s < p.ns; ++s) p.slk_dst[s] = slot(p.nv + p.slack_row[s], p.n + s);
+}
+
+// Jacobian by column, entries of a column in COO order
+static void plan_jacobian_by_column(const Engine& e, IpmPlan& p) {
+  p.jt_ptr.assign(p.n + 1, 0);
+  for (int k = 0; k < e.nnz_jac; ++k) ++p.jt_ptr[e.jac_j[k] + 1];
+  for (int i = 0; i < p.n; ++i) p.jt_ptr[i + 1] += p.jt_ptr[i];
+  p.jt_ent.resize(e.nnz_jac);
+  p.jt_row.resize(e.nnz_jac);
+  std::vector<int> fill(p.jt_ptr.begin(), p.jt_ptr.end() - 1);
+  for (int k = 0; k < e.nnz_jac; ++k) {
+    const int q = fill[e.jac_j[k]]++;
+    p.jt_ent[q] = k;
+    p.jt_row[q] = e.jac_i[k];
+  }
+}
 
 void ipm_plan_group_hessian(IpmPlan& p) {
   std::vector<std::pair<int, int>> all;   // (slot, COO entry), COO order kept inside a slot
   for (int k = 0; k < int(p.hes_dst.size()); ++k)
     if (p.hes_dst[k] >= 0) all.emplace_back(p.hes_dst[k], k);
-  std::stable_sort(all.begin(), all.end(), [](const auto& a, const auto& c) { return a.first < c.first; });
-  p.hg_ptr.assign(1, 0);
-  p.hg_src.clear();
-  p.hg_dst.clear();
-  for (size_t i = 0; i < all.size(); ++i) {
-    if (i == 0 || all[i].first != all[i - 1].first) {
-      if (i) p.hg_ptr.push_back(int(p.hg_src.size()));
-      p.hg_dst.push_back(all[i].first);
-    }
-    p.hg_src.push_back(all[i].second);
-  }
-  if (!all.empty()) p.hg_ptr.push_back(int(p.hg_src.size()));
+  group_by_key(all, p.hg_ptr, p.hg_src, p.hg_dst);
 }
 
 // Unknowns that must join the border because the Hessian couples them across collocation nodes.  A Lagrangian Hessian of this
@@ -64,17 +125,7 @@ int build_ipm_plan(Engine& e, IpmPlan& p, std::string* why, int nested) {
     if (why) *why = "the Jacobian / Hessian structure is not built yet";
     return RPM_E_INVALID;
   }
-  // rows: equality when g_l == g_u, otherwise one slack each (bounds g_l <= s <= g_u)
-  p.row_slack.assign(p.m, -1);
-  for (int r = 0; r < p.m; ++r)
-    if (e.gl[r] != e.gu[r]) {
-      p.row_slack[r] = p.ns++;
-      p.slack_row.push_back(r);
-    }
-  p.nv = p.n + p.ns;
-  p.Nt = p.nv + p.m;
-  p.fixed.assign(p.n, 0);
-  for (int i = 0; i < p.n; ++i) p.fixed[i] = e.xl[i] == e.xu[i] ? 1 : 0;
+  plan_rows_and_slacks(e, p);
 
   // time key of every unknown: global node index for what lives at a collocation node, -1 for the border
   std::vector<long long> key(p.Nt, -1);
@@ -116,11 +167,7 @@ int build_ipm_plan(Engine& e, IpmPlan& p, std::string* why, int nested) {
     const int a = p.pos[ua], c = p.pos[uc];
     if (a < p.Nb && c < p.Nb) p.b = std::max(p.b, std::abs(a - c));
   };
-  for (int k = 0; k < e.nnz_jac; ++k)
-    if (!p.fixed[e.jac_j[k]]) reach(p.nv + e.jac_i[k], e.jac_j[k]);
-  for (int k = 0; k < e.nnz_h; ++k)
-    if (!p.fixed[e.hes_i[k]] && !p.fixed[e.hes_j[k]]) reach(e.hes_i[k], e.hes_j[k]);
-  for (int s = 0; s < p.ns; ++s) reach(p.nv + p.slack_row[s], p.n + s);
+  for_each_offdiagonal(e, p, reach);
   p.b = std::max(p.b, 16);                       // a 16-column block of the factorisation fits inside the band
   if (p.b > p.Nb - 1) p.b = std::max(p.Nb - 1, 0);
   p.CS = p.b + 1 + p.nb;
@@ -129,40 +176,16 @@ int build_ipm_plan(Engine& e, IpmPlan& p, std::string* why, int nested) {
   auto dst = [&](int ua, int uc) -> int {
     int a = p.pos[ua], c = p.pos[uc];
     if (a < c) std::swap(a, c);
-    const long long o = p.at(a, c);
-    return o > INT32_MAX ? -2 : int(o);
+    return int(p.at(a, c));   // (called once the storage is known to be below 2^31)
   };
-  bool too_big = p.storage() > INT32_MAX;
-  p.jac_dst.assign(e.nnz_jac, -1);
-  p.hes_dst.assign(e.nnz_h, -1);
-  if (!too_big) {
-    for (int k = 0; k < e.nnz_jac; ++k)
-      if (!p.fixed[e.jac_j[k]]) p.jac_dst[k] = dst(p.nv + e.jac_i[k], e.jac_j[k]);
-    for (int k = 0; k < e.nnz_h; ++k)
-      if (!p.fixed[e.hes_i[k]] && !p.fixed[e.hes_j[k]]) p.hes_dst[k] = dst(e.hes_i[k], e.hes_j[k]);
-    p.diag_dst.resize(p.Nt);
-    for (int u = 0; u < p.Nt; ++u) p.diag_dst[u] = dst(u, u);
-    p.slk_dst.resize(p.ns);
-    for (int s = 0; s < p.ns; ++s) p.slk_dst[s] = dst(p.nv + p.slack_row[s], p.n + s);
-  }
-  if (too_big) {
+  if (p.storage() > INT32_MAX) {
     if (why) *why = "KKT storage of one instance exceeds 2^31 doubles";
     return RPM_E_UNSUPPORTED;
   }
-  // Jacobian by column, entries of a column in COO order
-  p.jt_ptr.assign(p.n + 1, 0);
-  for (int k = 0; k < e.nnz_jac; ++k) ++p.jt_ptr[e.jac_j[k] + 1];
-  for (int i = 0; i < p.n; ++i) p.jt_ptr[i + 1] += p.jt_ptr[i];
-  p.jt_ent.resize(e.nnz_jac);
-  p.jt_row.resize(e.nnz_jac);
-  std::vector<int> fill(p.jt_ptr.begin(), p.jt_ptr.end() - 1);
-  for (int k = 0; k < e.nnz_jac; ++k) {
-    const int q = fill[e.jac_j[k]]++;
-    p.jt_ent[q] = k;
-    p.jt_row[q] = e.jac_i[k];
-  }
+  plan_slots(e, p, dst);
+  plan_jacobian_by_column(e, p);
   p.Nt_alloc = p.Nt;
-  p.max_rows = IPM_PLAN_W + p.b + p.nb;
+  p.max_rows = IPM_W + p.b + p.nb;
   ipm_plan_group_hessian(p);
   return RPM_OK;
 }
@@ -174,10 +197,6 @@ struct NdClass {
   std::vector<int> ivl;     // Nt: interval of an interior unknown, -1 otherwise
   std::vector<int> loc;     // Nt: local index inside its interval (interior) or level-2 position (separator / border)
 };
-size_t factor_lds_of(int b, int nb) {   // = kkt_factor_lds_bytes (rpm_kkt_factor.hip)
-  const size_t W = IPM_PLAN_W;
-  return (size_t(b + 24) * W + W * (W + 1) + W * W + W + 2 * size_t(nb) * W + size_t(nb) * (nb + 1) / 2) * sizeof(double);
-}
 long long sub_at(const KktSubHost& g, int i, int j) { return g.koff + (long long)j * g.CS + (i < g.Nb ? i - j : g.b + 1 + i - g.Nb); }
 
 // destinations with long source lists first (order among them and among the rest unchanged); returns how many
@@ -270,16 +289,7 @@ static int build_ipm_plan_nd(Engine& e, IpmPlan& p, std::string* why) {
     return code;
   };
   if (int(e.hes_i.size()) != e.nnz_h || int(e.jac_i.size()) != e.nnz_jac) return fail("the Jacobian / Hessian structure is not built yet", RPM_E_INVALID);
-  p.row_slack.assign(p.m, -1);
-  for (int r = 0; r < p.m; ++r)
-    if (e.gl[r] != e.gu[r]) {
-      p.row_slack[r] = p.ns++;
-      p.slack_row.push_back(r);
-    }
-  p.nv = p.n + p.ns;
-  p.Nt = p.nv + p.m;
-  p.fixed.assign(p.n, 0);
-  for (int i = 0; i < p.n; ++i) p.fixed[i] = e.xl[i] == e.xu[i] ? 1 : 0;
+  plan_rows_and_slacks(e, p);
 
   // ---- intervals, and where every unknown lives: interior of an interval (with its node as sort key), separator, border
   struct Ivl { int phase, k0, nk, nx; std::vector<int> interior; int sep0 = 0; bool last = false; };
@@ -371,11 +381,7 @@ static int build_ipm_plan_nd(Engine& e, IpmPlan& p, std::string* why) {
       const int I = Ia >= 0 ? Ia : Ic, u = Ia >= 0 ? uc : ua;
       if (sep_of[u] < 0) gb[I].push_back(l2pos[u] - Nb2);
     };
-    for (int k = 0; k < e.nnz_jac; ++k)
-      if (!p.fixed[e.jac_j[k]]) touch(p.nv + e.jac_i[k], e.jac_j[k]);
-    for (int k = 0; k < e.nnz_h; ++k)
-      if (!p.fixed[e.hes_i[k]] && !p.fixed[e.hes_j[k]]) touch(e.hes_i[k], e.hes_j[k]);
-    for (int s = 0; s < p.ns; ++s) touch(p.nv + p.slack_row[s], p.n + s);
+    for_each_offdiagonal(e, p, touch);
     for (auto& v : gb) {
       std::sort(v.begin(), v.end());
       v.erase(std::unique(v.begin(), v.end()), v.end());
@@ -388,10 +394,9 @@ static int build_ipm_plan_nd(Engine& e, IpmPlan& p, std::string* why) {
     const auto it = std::lower_bound(gb[I].begin(), gb[I].end(), j);
     return it != gb[I].end() && *it == j ? int(it - gb[I].begin()) : -1;
   };
-  std::vector<int> base(KI), nI(KI), nbL(KI);
+  std::vector<int> nI(KI), nbL(KI);
   int cur = 0;
   for (int I = 0; I < KI; ++I) {
-    base[I] = cur;
     nI[I] = int(iv[I].interior.size());
     nbL[I] = int(sep[I].size()) + (iv[I].last ? 0 : nstate0[I + 1]) + int(gb[I].size());   // own separator, the NEXT interval's first-node states, its part of the border
     for (int q = 0; q < nI[I]; ++q) { const int u = iv[I].interior[q]; C.loc[u] = q; p.pos[u] = cur + q; }
@@ -429,11 +434,7 @@ static int build_ipm_plan_nd(Engine& e, IpmPlan& p, std::string* why) {
       b2 = std::max(b2, std::abs(l2pos[ua] - l2pos[uc]));
     }
   };
-  for (int k = 0; k < e.nnz_jac; ++k)
-    if (!p.fixed[e.jac_j[k]]) reach(p.nv + e.jac_i[k], e.jac_j[k]);
-  for (int k = 0; k < e.nnz_h; ++k)
-    if (!p.fixed[e.hes_i[k]] && !p.fixed[e.hes_j[k]]) reach(e.hes_i[k], e.hes_j[k]);
-  for (int s = 0; s < p.ns; ++s) reach(p.nv + p.slack_row[s], p.n + s);
+  for_each_offdiagonal(e, p, reach);
   if (bad_pair) return fail("nested dissection: an entry couples the interiors of two mesh intervals, or an interior to a separator that is not its own");
   for (int I = 0; I < KI; ++I)   // the Schur complements couple an interval's separator with the next one's states
     if (!iv[I].last) b2 = std::max(b2, int(sep[I].size()) + nstate0[I + 1] - 1);
@@ -465,11 +466,7 @@ static int build_ipm_plan_nd(Engine& e, IpmPlan& p, std::string* why) {
       auto entry = [&](int ua, int uc) {
         if (ivl_of[ua] < 0 && ivl_of[uc] < 0) touch(l2pos[ua], l2pos[uc]);
       };
-      for (int k = 0; k < e.nnz_jac; ++k)
-        if (!p.fixed[e.jac_j[k]]) entry(p.nv + e.jac_i[k], e.jac_j[k]);
-      for (int k = 0; k < e.nnz_h; ++k)
-        if (!p.fixed[e.hes_i[k]] && !p.fixed[e.hes_j[k]]) entry(e.hes_i[k], e.hes_j[k]);
-      for (int s = 0; s < p.ns; ++s) entry(p.nv + p.slack_row[s], p.n + s);
+      for_each_offdiagonal(e, p, entry);
       for (int I = 0; I < KI; ++I) {
         std::vector<int> seps;                       // the separator positions in I's local border
         for (int u : sep[I]) seps.push_back(l2pos[u]);
@@ -497,28 +494,14 @@ static int build_ipm_plan_nd(Engine& e, IpmPlan& p, std::string* why) {
   // ---- sub-problem geometry and storage
   long long koff = 0;
   p.subs.clear();
-  for (int I = 0; I < KI; ++I) {
-    KktSubHost g;
-    g.Nb = nI[I];
-    g.nb = nbL[I];
-    g.Nt = g.Nb + g.nb;
-    g.b = std::max(bI[I], IPM_PLAN_W);
-    if (g.b > g.Nb - 1) g.b = std::max(g.Nb - 1, 0);
-    g.CS = g.b + 1 + g.nb;
-    g.CS += g.CS & 1;
-    g.koff = koff;
-    g.roff = base[I];
-    koff += (long long)g.Nt * g.CS;
-    p.subs.push_back(g);
-  }
   {
-    int roff = l2base;
+    int roff = 0;
     auto push = [&](int Nb_, int nb_, int b_) {
       KktSubHost g;
       g.Nb = Nb_;
       g.nb = nb_;
       g.Nt = Nb_ + nb_;
-      g.b = std::max(b_, IPM_PLAN_W);
+      g.b = std::max(b_, IPM_W);
       if (g.b > g.Nb - 1) g.b = std::max(g.Nb - 1, 0);
       g.CS = g.b + 1 + g.nb;
       g.CS += g.CS & 1;
@@ -528,6 +511,7 @@ static int build_ipm_plan_nd(Engine& e, IpmPlan& p, std::string* why) {
       roff += g.Nt;
       p.subs.push_back(g);
     };
+    for (int I = 0; I < KI; ++I) push(nI[I], nbL[I], bI[I]);   // (right-hand sides in the order of the positions above: the upper levels start at l2base)
     if (p.n_l2) {
       for (int g = 0; g < p.l3_G; ++g) {
         const int n_g = g < p.l3_G - 1 ? p.l3_S - p.l3_w : Nb2 - g * p.l3_S;
@@ -558,8 +542,8 @@ static int build_ipm_plan_nd(Engine& e, IpmPlan& p, std::string* why) {
   p.max_rows = 0;
   p.max_factor_lds = 0;
   for (const KktSubHost& g : p.subs) {
-    p.max_rows = std::max(p.max_rows, IPM_PLAN_W + g.b + g.nb);
-    p.max_factor_lds = std::max(p.max_factor_lds, factor_lds_of(g.b, g.nb));
+    p.max_rows = std::max(p.max_rows, IPM_W + g.b + g.nb);
+    p.max_factor_lds = std::max(p.max_factor_lds, ipm_factor_lds_bytes(g.b, g.nb));
   }
 
   // ---- storage slot of every entry
@@ -586,16 +570,7 @@ static int build_ipm_plan_nd(Engine& e, IpmPlan& p, std::string* why) {
     if (o < 0) missing = true;
     return int(o);
   };
-  p.jac_dst.assign(e.nnz_jac, -1);
-  p.hes_dst.assign(e.nnz_h, -1);
-  for (int k = 0; k < e.nnz_jac; ++k)
-    if (!p.fixed[e.jac_j[k]]) p.jac_dst[k] = dst_i(p.nv + e.jac_i[k], e.jac_j[k]);
-  for (int k = 0; k < e.nnz_h; ++k)
-    if (!p.fixed[e.hes_i[k]] && !p.fixed[e.hes_j[k]]) p.hes_dst[k] = dst_i(e.hes_i[k], e.hes_j[k]);
-  p.diag_dst.resize(p.Nt);
-  for (int u = 0; u < p.Nt; ++u) p.diag_dst[u] = dst_i(u, u);
-  p.slk_dst.resize(p.ns);
-  for (int s = 0; s < p.ns; ++s) p.slk_dst[s] = dst_i(p.nv + p.slack_row[s], p.n + s);
+  plan_slots(e, p, dst_i);
   if (missing) return fail("nested dissection: an entry of the KKT matrix has no slot in the interval / separator layout");
 
   // ---- corner gather (level-1 Schur complements -> level 2), right-hand-side gather and solution scatter, in interval order
@@ -625,29 +600,9 @@ static int build_ipm_plan_nd(Engine& e, IpmPlan& p, std::string* why) {
         p.rs_src.push_back(l2_rhs(l2_of[r]));
       }
     }
-    std::stable_sort(all.begin(), all.end(), [](const auto& a, const auto& c) { return a.first < c.first; });
-    p.cg_ptr.push_back(0);
-    for (size_t i = 0; i < all.size(); ++i) {
-      if (i == 0 || all[i].first != all[i - 1].first) {
-        if (i) p.cg_ptr.push_back(int(p.cg_src.size()));
-        p.cg_dst.push_back(int(all[i].first));
-      }
-      p.cg_src.push_back(all[i].second);
-    }
-    p.cg_ptr.push_back(int(p.cg_src.size()));
-    if (all.empty()) p.cg_ptr.assign(1, 0);
+    group_by_key(all, p.cg_ptr, p.cg_src, p.cg_dst);
     p.n_cg_long = long_lists_first(p.cg_ptr, p.cg_src, p.cg_dst);
-    std::stable_sort(rall.begin(), rall.end(), [](const auto& a, const auto& c) { return a.first < c.first; });
-    p.rg_ptr.push_back(0);
-    for (size_t i = 0; i < rall.size(); ++i) {
-      if (i == 0 || rall[i].first != rall[i - 1].first) {
-        if (i) p.rg_ptr.push_back(int(p.rg_src.size()));
-        p.rg_dst.push_back(rall[i].first);
-      }
-      p.rg_src.push_back(rall[i].second);
-    }
-    p.rg_ptr.push_back(int(p.rg_src.size()));
-    if (rall.empty()) p.rg_ptr.assign(1, 0);
+    group_by_key(rall, p.rg_ptr, p.rg_src, p.rg_dst);
   }
   if (p.n_l2) {   // second stage: the group sub-problems' Schur complements -> the last level, in group order
     const KktSubHost& G3 = p.subs.back();
@@ -670,40 +625,11 @@ static int build_ipm_plan_nd(Engine& e, IpmPlan& p, std::string* why) {
         p.rs2_src.push_back(p.l3_base + l3_of[r]);
       }
     }
-    std::stable_sort(all.begin(), all.end(), [](const auto& a, const auto& c) { return a.first < c.first; });
-    p.cg2_ptr.push_back(0);
-    for (size_t i = 0; i < all.size(); ++i) {
-      if (i == 0 || all[i].first != all[i - 1].first) {
-        if (i) p.cg2_ptr.push_back(int(p.cg2_src.size()));
-        p.cg2_dst.push_back(int(all[i].first));
-      }
-      p.cg2_src.push_back(all[i].second);
-    }
-    p.cg2_ptr.push_back(int(p.cg2_src.size()));
+    group_by_key(all, p.cg2_ptr, p.cg2_src, p.cg2_dst);
     p.n_cg2_long = long_lists_first(p.cg2_ptr, p.cg2_src, p.cg2_dst);
-    std::stable_sort(rall.begin(), rall.end(), [](const auto& a, const auto& c) { return a.first < c.first; });
-    p.rg2_ptr.push_back(0);
-    for (size_t i = 0; i < rall.size(); ++i) {
-      if (i == 0 || rall[i].first != rall[i - 1].first) {
-        if (i) p.rg2_ptr.push_back(int(p.rg2_src.size()));
-        p.rg2_dst.push_back(rall[i].first);
-      }
-      p.rg2_src.push_back(rall[i].second);
-    }
-    p.rg2_ptr.push_back(int(p.rg2_src.size()));
+    group_by_key(rall, p.rg2_ptr, p.rg2_src, p.rg2_dst);
   }
-  // Jacobian by column, entries of a column in COO order
-  p.jt_ptr.assign(p.n + 1, 0);
-  for (int k = 0; k < e.nnz_jac; ++k) ++p.jt_ptr[e.jac_j[k] + 1];
-  for (int i = 0; i < p.n; ++i) p.jt_ptr[i + 1] += p.jt_ptr[i];
-  p.jt_ent.resize(e.nnz_jac);
-  p.jt_row.resize(e.nnz_jac);
-  std::vector<int> fill(p.jt_ptr.begin(), p.jt_ptr.end() - 1);
-  for (int k = 0; k < e.nnz_jac; ++k) {
-    const int q = fill[e.jac_j[k]]++;
-    p.jt_ent[q] = k;
-    p.jt_row[q] = e.jac_i[k];
-  }
+  plan_jacobian_by_column(e, p);
   ipm_plan_group_hessian(p);
   // keep what ipm_plan_offset needs
   p.nd_ivl = ivl_of;

@@ -88,4 +88,87 @@ void ipm_plan_group_hessian(IpmPlan& p);   // hg_* from hes_dst
 // storage offset of the entry between unknowns ua, uc ([0,n) x, [n,nv) slacks, [nv,nv+m) multipliers); -1 if the layout has no slot for it
 long long ipm_plan_offset(const IpmPlan& p, int ua, int uc);
 
+// ---- what the host tables below and the kernels that read them share: one definition for the host compiler and for hipcc
+#if defined(__HIP__) || defined(__HIPCC__)
+#define RPM_IPM_HD __host__ __device__
+#else
+#define RPM_IPM_HD
+#endif
+
+constexpr int IPM_W = 16;               // block width of the factorisation
+constexpr int IPM_LONG_COLUMN = 256;    // a Jacobian column of more entries gets a workgroup of its own in ipm_jt_lambda_kernel
+constexpr int IPM_FILL_CHUNK = 4096;    // doubles of KKT storage one workgroup of ipm_fill_kernel zeroes and fills at a time (2048: 76 us, 4096: 70 us, 8192: 82 us on the metric problem)
+constexpr int IPM_DENSE_SLOTS = 22, IPM_DENSE_TILE_WAVES = 7, IPM_DENSE_LDS_ROW = 18;   // kkt_factor_dense_kernel: tiles per wave, tile waves, doubles per LDS row
+constexpr int IPM_DENSE_TILES = IPM_DENSE_SLOTS * IPM_DENSE_TILE_WAVES;
+// kkt_factor_dense_kernel keeps the trailing IPM_DENSE_ROWS block rows of a block in registers; a block of up to IPM_DENSE_EARLY more
+// eliminates its first ("early") block columns through the storage: their tiles are loaded, used and put back by the wave that owns them
+// (4: three tiles per wave and early column wait in registers beside the resident ones; a fourth spills)
+constexpr int IPM_DENSE_ROWS = 17, IPM_DENSE_EARLY = 4;
+static_assert(IPM_DENSE_ROWS * (IPM_DENSE_ROWS + 1) / 2 <= IPM_DENSE_TILES, "resident tiles");
+RPM_IPM_HD inline int ipm_dense_early(int block_rows) { return block_rows > IPM_DENSE_ROWS ? block_rows - IPM_DENSE_ROWS : 0; }
+// number of tile (I, Kb), Kb <= I, of a block of `block_rows` block rows: the resident ones (Kb >= early columns) column by column
+// from 0 — tile t sits in slot t / 7 of wave t % 7 —, the early ones after them
+RPM_IPM_HD inline int ipm_dense_tile(int block_rows, int I, int Kb) {
+  const int E = ipm_dense_early(block_rows), R = block_rows - E;
+  if (Kb >= E) { const int kr = Kb - E; return kr * R - kr * (kr - 1) / 2 + I - Kb; }
+  return R * (R + 1) / 2 + Kb * block_rows - Kb * (Kb - 1) / 2 + I - Kb;
+}
+RPM_IPM_HD inline int ipm_dense_tiles_of(int block_rows) { return block_rows * (block_rows + 1) / 2; }
+
+// LDS bytes of kkt_factor_kernel for a sub-problem of half bandwidth b and border nb (rpm_kkt_factor.hip)
+inline size_t ipm_factor_lds_bytes(int b, int nb) {
+  const size_t W = IPM_W;
+  return (size_t(b + 24) * W + W * (W + 1) + W * W + W + 2 * size_t(nb) * W + size_t(nb) * (nb + 1) / 2) * sizeof(double);
+}
+
+// band + border storage of one instance (IpmPlan::at): element (i, j), i >= j
+struct KktGeom {
+  int Nt, Nb, nb, b, CS;
+  RPM_IPM_HD size_t at(int i, int j) const { return size_t(j) * CS + (i < Nb ? i - j : b + 1 + i - Nb); }
+  RPM_IPM_HD int block_rows() const { return (Nb + IPM_W - 1) / IPM_W + (nb + IPM_W - 1) / IPM_W; }   // 16-row blocks: band, then border
+};
+// one sub-problem of the factorisation as the kernels take it (KktSubHost): its geometry, where its block starts inside an
+// instance's KKT storage, where its right-hand side starts inside an instance's vector
+struct KktSub {
+  KktGeom g;
+  int roff;
+  long long koff;
+};
+
+// ---- rpm_ipm_tables.cpp (host only): the index tables rpm_ipm_create uploads, pure functions of the plan
+// The factorisation's sub-problems: the whole band + border matrix, or (nested dissection) n_l1 interval blocks, n_l2 groups of
+// separators and the last level.
+struct IpmSubList {
+  std::vector<KktSub> subs;
+  int n_l1 = 0, n_l2 = 0, max_sub_nt = 0;
+};
+IpmSubList ipm_sub_list(const IpmPlan& p);
+std::vector<int> ipm_long_columns(const IpmPlan& p);   // Jacobian columns of more than IPM_LONG_COLUMN entries, ascending
+
+// Every structural slot of the KKT storage in ascending order (IpmDev::as_*): ki = kind << 28 | index — kind 0 Hessian slot hg i,
+// 1 Jacobian entry k, 2 slack s, 3 diagonal of variable i (hg: the Hessian slot that shares it, or -1), 4 diagonal of constraint r.
+// one_pass: ipm_fill_kernel can use the list (sizes below 2^28, no two writers of one slot, offsets inside the storage); ptr[c] is
+// then the first entry at or beyond chunk c (IPM_FILL_CHUNK doubles), ptr.size() - 1 chunks.
+struct IpmFillList {
+  std::vector<int> dst, ki, hg, ptr;
+  bool one_pass = false;
+  int n_chunks() const { return one_pass ? int(ptr.size()) - 1 : 0; }
+};
+IpmFillList ipm_fill_list(const IpmPlan& p);
+
+// Level 1 assembled by kkt_factor_dense_kernel itself (IpmDev::df_*): per interval block the entries of `fill` inside it — the
+// Jacobian entries from ptr[3 s], the Hessian slots from ptr[3 s + 1], slack entries and diagonals from ptr[3 s + 2] — and per lane
+// of register tile t the four 16-bit numbers (1-based into the block's list, 0 = a structural zero) of the entries it holds:
+// map[(s * tiles + t) * 64 + (column & 3) * 16 + row] >> 16 * (column >> 2).  live: the chunks of `fill` that do not lie inside a
+// level-1 block, the only ones ipm_fill_kernel then fills.  built = false (and nothing else filled in): no one-pass list, no level-1
+// blocks, a block of more than IPM_DENSE_ROWS + IPM_DENSE_EARLY block rows, more than 0xffff entries in a block, or more entries
+// than the LDS of its panel holds.
+struct IpmFusedFill {
+  bool built = false;
+  int tiles = IPM_DENSE_TILES;
+  std::vector<int> ptr, ki, hg, live;
+  std::vector<unsigned long long> map;
+};
+IpmFusedFill ipm_fused_fill(const IpmSubList& s, const IpmFillList& fill);
+
 }  // namespace rpm

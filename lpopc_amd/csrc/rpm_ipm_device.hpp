@@ -1,6 +1,6 @@
 // rpm_ipm_device.hpp — what the HIP translation units of row f-2 share: the parameter blocks of the interior-point
 // kernels (rpm_ipm_step_kernels.hip, rpm_kkt_factor.hip, rpm_kkt_solve.hip, rpm_ipm_lbfgs.hip) and their launchers, used by the
-// solver loop and the C ABI (rpm_ipm_solver.hip).
+// solver loop and the C ABI (rpm_ipm_solver.hip, rpm_ipm_debug.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -8,7 +8,6 @@
 
 namespace rpm {
 
-constexpr int IPM_W = 16;        // block width of the factorisation
 constexpr int IPM_FMAX = 1024;   // filter entries kept per instance (the filter empties whenever mu changes; a long Delta-III phase at one mu adds hundreds)
 constexpr int IPM_TRACE = 8;     // doubles per trace record: f, theta, mu, alpha, alpha_z, delta_w, E_0, backtracks
 constexpr double IPM_INF = 1e19; // Ipopt's nlp_lower_bound_inf / nlp_upper_bound_inf
@@ -64,18 +63,7 @@ struct IpmInst {
   long long dbg[8];   // phase clocks of the factorisation (builds with -DIPM_TIMING only)
 };
 
-// band + border storage of one instance (rpm_ipm.hpp): element (i, j), i >= j
-struct KktGeom {
-  int Nt, Nb, nb, b, CS;
-  __device__ size_t at(int i, int j) const { return size_t(j) * CS + (i < Nb ? i - j : b + 1 + i - Nb); }
-};
-// one sub-problem of the factorisation (rpm_ipm.hpp KktSubHost): its geometry, where its block starts inside an instance's
-// KKT storage, where its right-hand side starts inside an instance's vector
-struct KktSub {
-  KktGeom g;
-  int roff;
-  long long koff;
-};
+// (KktGeom, KktSub and the constants the host tables share with the kernels: rpm_ipm.hpp)
 struct IpmDev {
   int B, n, m, ns, nv, Nt, Nb, nb, b, CS, nnz_jac, nnz_h;
   long long sg, sv, kstride;
@@ -151,23 +139,6 @@ struct IpmDev {
   double *lb_Z;               // 2 IPM_LB_H x B x Nt: K0^-1 E, column-major by column
 };
 
-constexpr int IPM_DENSE_SLOTS = 22, IPM_DENSE_TILE_WAVES = 7, IPM_DENSE_LDS_ROW = 18;   // kkt_factor_dense_kernel: tiles per wave, tile waves, doubles per LDS row
-constexpr int IPM_DENSE_TILES = IPM_DENSE_SLOTS * IPM_DENSE_TILE_WAVES;
-// kkt_factor_dense_kernel keeps the trailing IPM_DENSE_ROWS block rows of a block in registers; a block of up to IPM_DENSE_EARLY more
-// eliminates its first ("early") block columns through the storage: their tiles are loaded, used and put back by the wave that owns them
-// (4: three tiles per wave and early column wait in registers beside the resident ones; a fourth spills)
-constexpr int IPM_DENSE_ROWS = 17, IPM_DENSE_EARLY = 4;
-static_assert(IPM_DENSE_ROWS * (IPM_DENSE_ROWS + 1) / 2 <= IPM_DENSE_TILES, "resident tiles");
-__host__ __device__ inline int ipm_dense_early(int block_rows) { return block_rows > IPM_DENSE_ROWS ? block_rows - IPM_DENSE_ROWS : 0; }
-// number of tile (I, Kb), Kb <= I, of a block of `block_rows` block rows: the resident ones (Kb >= early columns) column by column
-// from 0 — tile t sits in slot t / 7 of wave t % 7 —, the early ones after them
-__host__ __device__ inline int ipm_dense_tile(int block_rows, int I, int Kb) {
-  const int E = ipm_dense_early(block_rows), R = block_rows - E;
-  if (Kb >= E) { const int kr = Kb - E; return kr * R - kr * (kr - 1) / 2 + I - Kb; }
-  return R * (R + 1) / 2 + Kb * block_rows - Kb * (Kb - 1) / 2 + I - Kb;
-}
-__host__ __device__ inline int ipm_dense_tiles_of(int block_rows) { return block_rows * (block_rows + 1) / 2; }
-constexpr int IPM_FILL_CHUNK = 4096;   // doubles of KKT storage one workgroup of ipm_fill_kernel zeroes and fills at a time (2048: 76 us, 4096: 70 us, 8192: 82 us on the metric problem)
 constexpr int IPM_VEC_BLOCKS = 64;   // most workgroups per instance of a vector kernel
 constexpr int IPM_VEC_PART = 24;     // doubles of partial results per workgroup
 constexpr int IPM_MT = 8;   // most 16-row tiles per wave of the factorisation: block columns of up to 4 x 8 x 16 = 512 rows

@@ -268,7 +268,6 @@ __device__ inline bool monotone_mu(const IpmOpts& o, double dual, double prim, d
 // grad f + A^T lambda by column (the restoration problem has no grad f).  A thread per unknown for the short columns; the long
 // ones — t0, tf, the final states: every defect row of a phase, 7 168 entries on the metric problem, which one thread walked
 // in 1.4 ms — take a workgroup each (blockIdx.x >= the thread-per-unknown blocks), summed in a fixed order.
-constexpr int IPM_LONG_COLUMN = 256;
 __global__ __launch_bounds__(256) void ipm_jt_lambda_kernel(IpmDev D, int n_thread_blocks) {
   __shared__ double sh[16];
   const int bi = blockIdx.y;

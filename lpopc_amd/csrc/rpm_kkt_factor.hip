@@ -1142,9 +1142,7 @@ hipError_t kkt_factor_dense_prepare(size_t lds_bytes) {
 static bool dense_early(size_t lds_bytes) { return lds_bytes > kkt_factor_dense_lds_bytes(IPM_DENSE_ROWS); }
 
 size_t kkt_factor_lds_bytes(const IpmPlan& p) {
-  if (p.nd) return p.max_factor_lds;
-  return (size_t(p.b + 24) * IPM_W + size_t(IPM_W) * (IPM_W + 1) + size_t(IPM_W) * IPM_W + IPM_W + 2 * size_t(p.nb) * IPM_W +
-          size_t(p.nb) * (p.nb + 1) / 2) * sizeof(double);
+  return p.nd ? p.max_factor_lds : ipm_factor_lds_bytes(p.b, p.nb);
 }
 hipError_t kkt_factor_prepare(int tiles_per_wave, size_t lds_bytes) {
   if (lds_bytes <= 48 * 1024) return hipSuccess;
