@@ -278,6 +278,43 @@ int rpm_carry_multipliers_batch(rpm_engine* from, rpm_engine* to, const double* 
  * out of range: RPM_E_INVALID. */
 int rpm_carry_multipliers_layout(rpm_engine* e, int phase, int rows[4]);
 
+/* The receding-horizon step of a sweep: every instance's plan and duals moved on in time on the engine's own mesh.  dt:
+ * n_instances x n_phases, instance-major, each phase's own advance in the problem's time unit (a single-phase MPC problem
+ * passes n_instances numbers).  x / x_out, z_L, z_U and their outputs: n_instances x n; lambda / lambda_out: n_instances x m;
+ * all packed and instance-major as rpm_ipm_solve_warm_dev takes and returns them.  lambda and lambda_out are given together or
+ * both NULL; z_L, z_U, z_L_out, z_U_out all or none.
+ * Per instance and phase, time[0], time[N] and the knots tau_g are the carry's, from x's t0 and tf.  With tp[q] the phase's own
+ * LGR points a value is taken at s_q = tp[q] + 2 dt / (time[N] - time[0]) (state columns and the z of states also at
+ * 1.0 + 2 dt / (time[N] - time[0])), clamped into [-1, 1]: a dt past the end of the horizon holds the end value, a negative dt
+ * moves back and holds the first value.  A NaN passes through the clamp.
+ *   x:       every state and control column is the carry's natural cubic spline through its N + 1 knots (a control's knot at 1
+ *            by the spline of a control), evaluated at s_q; t0 = time[0] and tf = time[N] as the carry writes them and the
+ *            static parameters are copied: the window keeps its place, the caller's time is relative to the step.
+ *   lambda:  defect rows as costates and path rows divided by the weights, with rpm_carry_multipliers_batch's transforms before
+ *            and after, evaluated at s_q: lambda'[defect] = -w_q c(s_q), lambda'[path] = w_q p(s_q); event rows and the rows
+ *            after the last phase are copied.
+ *   z_L, z_U: x's layout column by column, the same knots and point search, but piecewise linear, A y[kl-1] + B y[kr-1] held
+ *            between the two knot values against the last ulp of rounding (a control column's knot at 1 holds its last node's
+ *            value): non-negative multipliers stay non-negative and inside their column's range, where a spline would not
+ *            keep them so.  The entries at t0, tf and the parameters are copied.
+ * With dt == 0 the shift of x and of lambda is rpm_carry_solution_batch(e, e, ...) and rpm_carry_multipliers_batch(e, e, ...)
+ * bit for bit: one kernel, one copy of the knots, the recurrences, the search and the transforms.
+ * nonfinite: n_instances ints or NULL, 1 when any array produced for the instance holds a NaN or Inf; an instance with NaN or
+ * Inf anywhere, with tf == t0 or with a NaN dt spoils itself only.
+ * Argument errors are decided on the host before anything is queued, the message is rpm_last_error(e): NULL dt, x or x_out,
+ * half a pair, an output overlapping any input or another output (the caller ping-pongs two sets of buffers): RPM_E_INVALID;
+ * an interval-sharded engine, a column that does not fit one workgroup's LDS: RPM_E_UNSUPPORTED; no device: RPM_E_DEVICE.
+ * The _dev form queues one launch per array given, plus one for the verdicts, on `stream`.  After the first call on an engine it
+ * allocates nothing, copies nothing and never synchronises: it can follow rpm_ipm_solve_warm_dev and
+ * rpm_ipm_get_bound_multipliers_dev on the caller's stream and be captured into a graph.  The host-pointer form stages its
+ * arrays and blocks.  The calling thread's current device is restored.  Option "carry_tile" applies; every value gives the
+ * same bits. */
+int rpm_shift_plan_batch_dev(rpm_engine* e, const double* d_dt, const double* d_x, double* d_x_out, const double* d_lambda,
+                             double* d_lambda_out, const double* d_z_L, const double* d_z_U, double* d_z_L_out, double* d_z_U_out,
+                             int* d_nonfinite, void* stream);
+int rpm_shift_plan_batch(rpm_engine* e, const double* dt, const double* x, double* x_out, const double* lambda, double* lambda_out,
+                         const double* z_L, const double* z_U, double* z_L_out, double* z_U_out, int* nonfinite);
+
 /* Solution extraction for a whole sweep: Nlp2OpConverter::Nlp2OpControl, Core/Nlp2OPConverter.cpp:13-196, for all phases and all
  * n_instances instances of the engine at once, every instance with its own constants (rpm_set_instance_constants) and static
  * parameters.  x: n_instances x n, lambda: n_instances x m, both packed and instance-major as rpm_ipm_solve[_dev] returns them.
@@ -382,6 +419,16 @@ const char* rpm_ipm_last_error(const rpm_ipm* s);
 int rpm_ipm_set_option(rpm_ipm* s, const char* key, double value);
 int rpm_ipm_set_bounds(rpm_ipm* s, int instance, const double* x_l, const double* x_u);
 int rpm_ipm_set_all_bounds(rpm_ipm* s, const double* x_l, const double* x_u);   /* n_instances x n each */
+/* The measured initial states of a receding-horizon sweep: state0 is n_instances x nx of `phase`; both calls write
+ * lower = upper = state0[b][j] at variable x_state0 + j (N + 1) of every instance and leave every other bound alone, so the
+ * next solve is bit for bit the solve after rpm_ipm_set_all_bounds with the same numbers.  Every one of the phase's nx initial
+ * states must be fixed in the solver's plan (the KKT layout is shared by all instances), else RPM_E_INVALID naming the first
+ * free one; a phase out of range or a NULL array: RPM_E_INVALID; all decided on the host.  The _dev form takes a device array
+ * and is one small launch on `stream`: no copy, no synchronisation, capturable into a graph; rpm_ipm_solve[_warm]_dev on the
+ * same stream reads what it wrote.  A NaN or Inf measured state ends that instance's next solve with status 5 and disturbs no
+ * other instance. */
+int rpm_ipm_set_initial_states_dev(rpm_ipm* s, int phase, const double* d_state0, void* stream);
+int rpm_ipm_set_initial_states(rpm_ipm* s, int phase, const double* state0);
 int rpm_ipm_get_info(rpm_ipm* s, int* kkt_order, int* band_order, int* half_bandwidth, int* border,
                      long long* storage_doubles, int* n_slacks);
 int rpm_ipm_get_stats(rpm_ipm* s, int* iterations, int* factorizations, int* trial_points);
@@ -682,6 +729,11 @@ int rpm_sweep_carry_multipliers(rpm_sweep* from, rpm_sweep* to, const double* x_
 int rpm_sweep_solve_warm(rpm_sweep* s, double* x, double* lambda, double* z_L, double* z_U, double* obj, int* status, int* iterations,
                          double* kkt_error);
 int rpm_sweep_get_bound_multipliers(rpm_sweep* s, double* z_L, double* z_U);
+/* rpm_shift_plan_batch / rpm_ipm_set_initial_states on every share side by side (host arrays, all B instances: dt B x n_phases,
+ * state0 B x nx): what one engine holding all B instances computes, bit for bit */
+int rpm_sweep_shift_plan(rpm_sweep* s, const double* dt, const double* x, double* x_out, const double* lambda, double* lambda_out,
+                         const double* z_L, const double* z_U, double* z_L_out, double* z_U_out, int* nonfinite);
+int rpm_sweep_set_initial_states(rpm_sweep* s, int phase, const double* state0);
 /* rpm_nlp2op_batch on every share side by side (x: B x n, lambda: B x m, out: B x EB, nonfinite: B or NULL): what one engine
  * holding all B instances returns, bit for bit. */
 int rpm_sweep_nlp2op(rpm_sweep* s, const double* x, const double* lambda, double* out, int* nonfinite);

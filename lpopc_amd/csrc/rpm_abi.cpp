@@ -429,6 +429,27 @@ int rpm_carry_multipliers_batch(rpm_engine* from, rpm_engine* to, const double* 
   RPM_GUARD_END(e)
 }
 
+// ---- the receding-horizon shift of a sweep's plan and duals (rpm_carry_kernels.hip) ---------------------------------------
+int rpm_shift_plan_batch_dev(rpm_engine* h, const double* d_dt, const double* d_x, double* d_x_out, const double* d_lambda,
+                             double* d_lambda_out, const double* d_z_L, const double* d_z_U, double* d_z_L_out, double* d_z_U_out,
+                             int* d_nonfinite, void* stream) {
+  if (!h) return RPM_E_INVALID;
+  Engine& e = h->e;
+  RPM_GUARD_BEGIN
+  return rpm::dev_shift_plan_batch(e, rpm::ShiftArrays{d_dt, d_x, d_x_out, d_lambda, d_lambda_out, d_z_L, d_z_U, d_z_L_out, d_z_U_out},
+                                   d_nonfinite, stream);
+  RPM_GUARD_END(e)
+}
+
+int rpm_shift_plan_batch(rpm_engine* h, const double* dt, const double* x, double* x_out, const double* lambda, double* lambda_out,
+                         const double* z_L, const double* z_U, double* z_L_out, double* z_U_out, int* nonfinite) {
+  if (!h) return RPM_E_INVALID;
+  Engine& e = h->e;
+  RPM_GUARD_BEGIN
+  return rpm::host_shift_plan_batch(e, rpm::ShiftArrays{dt, x, x_out, lambda, lambda_out, z_L, z_U, z_L_out, z_U_out}, nonfinite);
+  RPM_GUARD_END(e)
+}
+
 int rpm_carry_multipliers_layout(rpm_engine* h, int phase, int rows[4]) {
   if (!h || !rows) return RPM_E_INVALID;
   if (rpm::carry_multipliers_layout(h->e, phase, rows)) return fail(h->e, RPM_E_INVALID, "carry_multipliers_layout: the phase index is out of range");

@@ -10,6 +10,8 @@
 //   5. t0 = time[0], tf = time[N]; static parameters copied.
 // Everything but the cubes of step 4 repeats the one-instance path (rpm_nlp2op_control, a new rpm_create carrying the guess,
 // rpm_get_starting_point) operation by operation; the cubes are A * A * A here and glibc's pow(A, 3) there.
+// The receding-horizon shift of a plan (rpm_shift_plan_batch*) is the same kernel with from == to and every evaluation point
+// moved by the instance's own 2 dt / (time[N] - time[0]), clamped into [-1, 1]; bound multipliers ride it piecewise linearly.
 #include "rpm_post_device.hpp"
 
 namespace rpm {
@@ -53,18 +55,54 @@ struct CarryMult {
   int m_from, m_to, P;
 };
 
-// spline_eval's tail (rpm_setup.cpp): binary search for the knot interval, then A, B, Cc, Dd as written there.  The search
+// What the shift of a plan needs beyond the carry: dt NULL = a carry, which reads nothing else of this.
+struct CarryShift {
+  const double* dt;       // n_instances x P: every phase's own advance in the problem's time unit
+  const double* z_from;   // not NULL: a bound-multiplier array in x's layout supplies the columns (x_from still the knots), which
+                          // are interpolated piecewise linearly; its entries at t0, tf and the parameters are copied
+  int P;
+};
+
+// spline_eval's tail (rpm_setup.cpp): binary search for the knot interval, then A, B as written there.  The search
 // halves kr - kl whatever the comparisons say, and its trip count is bounded besides: NaN knots cannot spin it.
-__device__ __forceinline__ double carry_eval(double x, const double* xd, const double* yd, const double* c, int n) {
+struct CarryAt {
+  int kl, kr;
+  double h, A, B;
+};
+__device__ __forceinline__ CarryAt carry_locate(double x, const double* xd, int n) {
   int kl = 1, kr = n;
   for (int it = 0; it < 32 && kr - kl > 1; ++it) {
     const int k = (kr + kl) / 2;
     if (xd[k - 1] > x) kr = k; else kl = k;
   }
   const double h = xd[kr - 1] - xd[kl - 1];
-  const double A = (xd[kr - 1] - x) / h, B = (x - xd[kl - 1]) / h;
+  return CarryAt{kl, kr, h, (xd[kr - 1] - x) / h, (x - xd[kl - 1]) / h};
+}
+// the natural cubic spline there: Cc, Dd as spline_eval writes them
+__device__ __forceinline__ double carry_eval(double x, const double* xd, const double* yd, const double* c, int n) {
+  const CarryAt p = carry_locate(x, xd, n);
+  const double h = p.h, A = p.A, B = p.B;
   const double Cc = (A * A * A - A) * (h * h) / 6.0, Dd = (B * B * B - B) * (h * h) / 6.0;
-  return A * yd[kl - 1] + B * yd[kr - 1] + Cc * c[kl - 1] + Dd * c[kr - 1];
+  return A * yd[p.kl - 1] + B * yd[p.kr - 1] + Cc * c[p.kl - 1] + Dd * c[p.kr - 1];
+}
+// the same knots and search, the cubic terms dropped: a convex combination, non-negative columns stay non-negative.  A and B
+// are rounded separately, so the sum can come out an ulp outside the two knot values (x next to a knot): it is held between
+// them, with comparisons a NaN passes through.
+__device__ __forceinline__ double carry_eval_linear(double x, const double* xd, const double* yd, int n) {
+  const CarryAt p = carry_locate(x, xd, n);
+  const double yl = yd[p.kl - 1], yr = yd[p.kr - 1];
+  const double lo = yl < yr ? yl : yr, hi = yl < yr ? yr : yl;
+  double v = p.A * yl + p.B * yr;
+  v = v > hi ? hi : v;
+  return v < lo ? lo : v;
+}
+// A shifted evaluation point: tau moved on by dt in the instance's own time, then clamped into [-1, 1] so that a dt past
+// either end holds the end value; the comparisons are written so that a NaN passes through.
+__device__ __forceinline__ double carry_shifted(double tau, double dt, double t0, double tf, double tau_0) {
+  const double time_0 = post_time(t0, tf, tau_0), time_N = post_time(t0, tf, 1.0);
+  double s = tau + 2 * dt / (time_N - time_0);
+  s = s > 1.0 ? 1.0 : s;
+  return s < -1.0 ? -1.0 : s;
 }
 
 // Workgroup (group of columns of a phase, tile of TB instances), 256 threads.  x is instance-major with every column
@@ -73,7 +111,7 @@ __device__ __forceinline__ double carry_eval(double x, const double* xd, const d
 __global__ void __launch_bounds__(256)
 rpm_carry_kernel(const PhaseDev* __restrict__ fph, const double* __restrict__ fpts, int n_from, const PhaseDev* __restrict__ tph,
                  const double* __restrict__ tpts, int n_to, const CarryGroup* __restrict__ groups, int B, int TB,
-                 const double* __restrict__ x_from, double* __restrict__ x_to, CarryMult mu_) {
+                 const double* __restrict__ x_from, double* __restrict__ x_to, CarryMult mu_, CarryShift sh) {
   extern __shared__ __align__(16) double carry_sm[];
   const CarryGroup v = groups[blockIdx.x];
   const PhaseDev pf = fph[v.phase], pt = tph[v.phase];
@@ -83,6 +121,8 @@ rpm_carry_kernel(const PhaseDev* __restrict__ fph, const double* __restrict__ fp
   const double *__restrict__ lam_from = mu_.lam_from, *__restrict__ tw = mu_.tw;
   double* __restrict__ lam_to = mu_.lam_to;
   const int m_from = mu_.m_from, m_to = mu_.m_to, P = mu_.P;
+  const double *__restrict__ dts = sh.dt, *__restrict__ z_from = sh.z_from;
+  const bool lin = z_from != nullptr;
   const CarryRows rf(pf.g0, N, nx, pf.nc, pf.ne), rt(pt.g0, Nt, nx, pt.nc, pt.ne);
   const CarryLds L(M, TB, ncols);
   const int Mp = L.Mp;
@@ -115,14 +155,20 @@ rpm_carry_kernel(const PhaseDev* __restrict__ fph, const double* __restrict__ fp
       const double* lb = lam_from + size_t(b0 + bi) * m_from;
       if (col < nx) val = k < N ? -((1 / K.weights[pf.node0 + k]) * lb[rf.defect0 + col * N + k]) : post_end_costate(K, pf, lb + pf.g0, col);
       else if (k < N) val = (1 / K.weights[pf.node0 + k]) * lb[rf.path0 + (col - nx) * N + k];
-    } else if (col < nx) val = xb[pf.x_state0 + col * M + k];
-    else if (k < N) val = xb[pf.x_control0 + (col - nx) * N + k];
+    } else {
+      const double* vb = lin ? z_from + size_t(b0 + bi) * n_from : xb;
+      if (col < nx) val = vb[pf.x_state0 + col * M + k];
+      else if (k < N) val = vb[pf.x_control0 + (col - nx) * N + k];
+    }
     ys[(bi * ncols + cl) * Mp + k] = val;
   }
   __syncthreads();
 
   // ---- wave 0: mu, once per instance.  The other waves: the controls' values at tau = 1 -------------------------------
-  if (tid < 64) {
+  if (lin) {   // piecewise linear: no recurrences; a control's knot at 1 holds its last node's value
+    for (int r = tid; r < nb * ncols; r += nt)
+      if (v.col0 + r % ncols >= nx) ys[r * Mp + N] = ys[r * Mp + N - 1];
+  } else if (tid < 64) {
     for (int bi = tid; bi < nb; bi += 64) {
       const double* xd = tau + bi * Mp;
       double* m = mu + bi * Mp;
@@ -144,7 +190,7 @@ rpm_carry_kernel(const PhaseDev* __restrict__ fph, const double* __restrict__ fp
   __syncthreads();
 
   // ---- one lane per (instance, column): forward recurrence, back substitution, interior c doubled ------------------
-  for (int r = tid; r < nb * ncols; r += nt) {
+  for (int r = tid; r < (lin ? 0 : nb * ncols); r += nt) {
     const double* xd = tau + (r / ncols) * Mp;
     const double* m = mu + (r / ncols) * Mp;
     const double* y = ys + r * Mp;
@@ -171,17 +217,27 @@ rpm_carry_kernel(const PhaseDev* __restrict__ fph, const double* __restrict__ fp
   const double* tp = tpts + pt.node0;
   const int ns = nx - v.col0 < 0 ? 0 : (nx - v.col0 < ncols ? nx - v.col0 : ncols);   // state columns of this group
   const int nc = ncols - ns, Q = mult ? Nt : Nt + 1;
+  // the point a value is taken at: the target's own, or (shift) that point moved on by the instance's dt of this phase
+  auto at = [&](int bi, double tau_q) -> double {
+    if (!dts) return tau_q;
+    const double* xb = x_from + size_t(b0 + bi) * n_from;
+    return carry_shifted(tau_q, dts[size_t(b0 + bi) * sh.P + v.phase], xb[pf.x_t0], xb[pf.x_t0 + 1], fp[0]);
+  };
+  auto eval = [&](int bi, int r, double tau_q) -> double {
+    const double x = at(bi, tau_q);
+    return lin ? carry_eval_linear(x, tau + bi * Mp, ys + r * Mp, M) : carry_eval(x, tau + bi * Mp, ys + r * Mp, cs + r * Mp, M);
+  };
   for (int idx = tid; idx < nb * ns * Q; idx += nt) {
     const int q = idx % Q, cl = (idx / Q) % ns, bi = idx / (Q * ns);
     const int r = bi * ncols + cl;
-    const double val = carry_eval(q < Nt ? tp[q] : 1.0, tau + bi * Mp, ys + r * Mp, cs + r * Mp, M);
+    const double val = eval(bi, r, q < Nt ? tp[q] : 1.0);
     if (mult) lam_to[size_t(b0 + bi) * m_to + rt.defect0 + (v.col0 + cl) * Nt + q] = -(tw[pt.node0 + q] * val);
     else x_to[size_t(b0 + bi) * n_to + pt.x_state0 + (v.col0 + cl) * Q + q] = val;
   }
   for (int idx = tid; idx < nb * nc * Nt; idx += nt) {
     const int q = idx % Nt, cl = ns + (idx / Nt) % nc, bi = idx / (Nt * nc);
     const int r = bi * ncols + cl;
-    const double val = carry_eval(tp[q], tau + bi * Mp, ys + r * Mp, cs + r * Mp, M);
+    const double val = eval(bi, r, tp[q]);
     if (mult) lam_to[size_t(b0 + bi) * m_to + rt.path0 + (v.col0 + cl - nx) * Nt + q] = tw[pt.node0 + q] * val;
     else x_to[size_t(b0 + bi) * n_to + pt.x_control0 + (v.col0 + cl - nx) * Nt + q] = val;
   }
@@ -197,7 +253,8 @@ rpm_carry_kernel(const PhaseDev* __restrict__ fph, const double* __restrict__ fp
       const double* xb = x_from + size_t(b0 + bi) * n_from;
       const double t0 = xb[pf.x_t0], tf = xb[pf.x_t0 + 1];
       double val;
-      if (j == 0) val = post_time(t0, tf, fp[0]);          // time[0]
+      if (lin) val = z_from[size_t(b0 + bi) * n_from + pf.x_t0 + j];
+      else if (j == 0) val = post_time(t0, tf, fp[0]);     // time[0]
       else if (j == 1) val = post_time(t0, tf, 1.0);       // time[N]
       else val = xb[pf.x_t0 + j];
       x_to[size_t(b0 + bi) * n_to + pt.x_t0 + j] = val;
@@ -221,7 +278,8 @@ struct CarryPlan {
 };
 struct CarryState {
   std::vector<CarryPlan> plans;
-  HostForm host;   // host-pointer form: the carried block
+  HostForm host;    // host-pointer form: the carried block
+  HostForm shift;   // host-pointer form of the shift: dt, the four inputs and the four outputs in one block
 };
 
 size_t carry_budget(const Engine& from) {
@@ -280,9 +338,11 @@ CarryState& carry_state(Device& d) {
   return *static_cast<CarryState*>(d.carry);
 }
 
-// d_lam_from NULL: the solutions, x_from -> x_to; else the multipliers, lam_from -> lam_to with x_from's t0 / tf for the knots
+// d_lam_from NULL: the solutions, x_from -> x_to; else the multipliers, lam_from -> lam_to with x_from's t0 / tf for the knots.
+// sh.dt not NULL: the shift of a plan (from == to); sh.z_from not NULL: a bound-multiplier array z_from -> x_to.
 int carry_launch(Engine& from, Engine& to, const double* d_x_from, double* d_x_to, const double* d_lam_from, double* d_lam_to,
-                 int* d_nonfinite, hipStream_t st) {
+                 int* d_nonfinite, hipStream_t st, CarryShift sh = CarryShift{}) {
+  const std::string who = sh.dt ? "shift_plan_batch" : (d_lam_from ? "carry_multipliers_batch" : "carry_solution_batch");
   Device& d = *from.dev;
   HIP_TRY(from, hipSetDevice(d.device_id));
   CarryState& cs = carry_state(d);
@@ -294,7 +354,7 @@ int carry_launch(Engine& from, Engine& to, const double* d_x_from, double* d_x_t
     CarryPlan p;
     std::vector<CarryGroup> groups;
     if (!carry_plan(from, mult, &p.TB, &groups, &p.lds)) {
-      from.err = std::string(mult ? "carry_multipliers_batch" : "carry_solution_batch") + ": a column does not fit one workgroup's LDS";
+      from.err = who + ": a column does not fit one workgroup's LDS";
       return RPM_E_UNSUPPORTED;
     }
     p.mult = mult;
@@ -312,11 +372,11 @@ int carry_launch(Engine& from, Engine& to, const double* d_x_from, double* d_x_t
   if (mult) cm = CarryMult{d_lam_from, d_lam_to, d.kp, to.dev->d_weights, from.m, to.m, from.P};
   hipLaunchKernelGGL(rpm_carry_kernel, dim3(unsigned(plan->n_groups), unsigned((B + plan->TB - 1) / plan->TB)), dim3(256), plan->lds, st,
                      d.d_phases, d.d_points, from.n, to.dev->d_phases, to.dev->d_points, to.n, plan->d_groups, B, plan->TB, d_x_from,
-                     d_x_to, cm);
+                     d_x_to, cm, sh);
   if (d_nonfinite) flag_launch(mult ? to.m : to.n, mult ? d_lam_to : d_x_to, d_nonfinite, B, st);
   const hipError_t s = hipGetLastError();
   if (s != hipSuccess) {
-    from.err = std::string(mult ? "carry_multipliers_batch" : "carry_solution_batch") + " launch: " + hipGetErrorString(s);
+    from.err = who + " launch: " + hipGetErrorString(s);
     return RPM_E_DEVICE;
   }
   return RPM_OK;
@@ -335,6 +395,7 @@ void carry_destroy(Device* d) {
   for (CarryPlan& p : cs->plans)
     if (p.d_groups) (void)hipFree(p.d_groups);
   cs->host.release();
+  cs->shift.release();
   delete cs;
   d->carry = nullptr;
 }
@@ -447,6 +508,122 @@ int host_carry_mult_batch(Engine& from, Engine& to, const double* x_from, const 
   if (rc == RPM_OK) rc = dev_download(from, lam_to, cs.host.out, count, STAGE_G);
   if (rc) return rc;
   return cs.host.finish(from, nonfinite, B);
+}
+
+// ---- the receding-horizon shift of a plan: the carry onto the engine's own mesh, every point moved by the instance's dt ----
+
+// nonfinite[b] = 1 when any of up to four blocks of instance b holds a NaN or Inf: rpm_flag_kernel over several arrays
+struct ShiftFlagged {
+  const double* v[4];
+  long long len[4];
+};
+__global__ void __launch_bounds__(256) rpm_shift_flag_kernel(ShiftFlagged f, int* __restrict__ verdicts) {
+  bool bad = false;
+  for (int a = 0; a < 4; ++a) {
+    if (!f.v[a]) continue;
+    const double* vb = f.v[a] + size_t(blockIdx.x) * f.len[a];
+    for (long long i = threadIdx.x; i < f.len[a]; i += blockDim.x) bad |= nonfinite(vb[i]);
+  }
+  const int any = __syncthreads_or(bad ? 1 : 0);
+  if (threadIdx.x == 0) verdicts[blockIdx.x] = any ? 1 : 0;
+}
+
+// every argument error of the shift, decided on the host before a device is touched (all host or all device pointers)
+int shift_check(Engine& e, const ShiftArrays& a) {
+  const std::string who = "shift_plan_batch: ";
+  if (!a.dt) return carry_fail(e, RPM_E_INVALID, who + "dt is NULL");
+  if (!a.x) return carry_fail(e, RPM_E_INVALID, who + "x is NULL");
+  if (!a.x_out) return carry_fail(e, RPM_E_INVALID, who + "x_out is NULL");
+  if (!a.lambda != !a.lambda_out) return carry_fail(e, RPM_E_INVALID, who + "lambda and lambda_out are given together or both NULL");
+  if (!a.z_L != !a.z_U || !a.z_L != !a.z_L_out || !a.z_L != !a.z_U_out)
+    return carry_fail(e, RPM_E_INVALID, who + "z_L, z_U, z_L_out and z_U_out are given together or all NULL");
+  const size_t B = size_t(e.n_instances), Bn = B * e.n * sizeof(double), Bm = B * e.m * sizeof(double);
+  struct Range { const char* name; const void* p; size_t bytes; };
+  const Range in[5] = {{"dt", a.dt, B * e.P * sizeof(double)}, {"x", a.x, Bn}, {"lambda", a.lambda, Bm}, {"z_L", a.z_L, Bn}, {"z_U", a.z_U, Bn}};
+  const Range out[4] = {{"x_out", a.x_out, Bn}, {"lambda_out", a.lambda_out, Bm}, {"z_L_out", a.z_L_out, Bn}, {"z_U_out", a.z_U_out, Bn}};
+  auto overlap = [](const Range& u, const Range& v) {
+    const char *p = static_cast<const char*>(u.p), *q = static_cast<const char*>(v.p);
+    return p && q && u.bytes && v.bytes && p < q + v.bytes && q < p + u.bytes;
+  };
+  for (int o = 0; o < 4; ++o) {
+    for (const Range& r : in)
+      if (overlap(out[o], r)) return carry_fail(e, RPM_E_INVALID, who + out[o].name + " and " + r.name + " overlap");
+    for (int o2 = o + 1; o2 < 4; ++o2)
+      if (overlap(out[o], out[o2])) return carry_fail(e, RPM_E_INVALID, who + out[o].name + " and " + out[o2].name + " overlap");
+  }
+  if (sharded(e)) return carry_fail(e, RPM_E_UNSUPPORTED, who + "not with interval sharding");
+  for (int mult = 0; mult < (a.lambda ? 2 : 1); ++mult) {
+    int TB = 0;
+    size_t lds = 0;
+    if (!carry_plan(e, mult, &TB, nullptr, &lds)) {
+      int most = 0;
+      for (const PhaseHost& p : e.ph) most = std::max(most, p.N + 1);
+      return carry_fail(e, RPM_E_UNSUPPORTED, who + "a column of " + std::to_string(most) + " knots does not fit one workgroup's LDS");
+    }
+  }
+  return RPM_OK;
+}
+
+namespace {
+// one launch per kind of array, then the verdicts over everything produced
+int shift_launch(Engine& e, const ShiftArrays& a, int* d_nonfinite, hipStream_t st) {
+  const CarryShift sh{a.dt, nullptr, e.P};
+  int rc = carry_launch(e, e, a.x, a.x_out, nullptr, nullptr, nullptr, st, sh);
+  if (rc == RPM_OK && a.lambda) rc = carry_launch(e, e, a.x, nullptr, a.lambda, a.lambda_out, nullptr, st, sh);
+  if (rc == RPM_OK && a.z_L) rc = carry_launch(e, e, a.x, a.z_L_out, nullptr, nullptr, nullptr, st, CarryShift{a.dt, a.z_L, e.P});
+  if (rc == RPM_OK && a.z_U) rc = carry_launch(e, e, a.x, a.z_U_out, nullptr, nullptr, nullptr, st, CarryShift{a.dt, a.z_U, e.P});
+  if (rc || !d_nonfinite) return rc;
+  const ShiftFlagged f{{a.x_out, a.lambda_out, a.z_L_out, a.z_U_out}, {e.n, e.m, e.n, e.n}};
+  hipLaunchKernelGGL(rpm_shift_flag_kernel, dim3(unsigned(e.n_instances)), dim3(256), 0, st, f, d_nonfinite);
+  const hipError_t s = hipGetLastError();
+  if (s != hipSuccess) return carry_fail(e, RPM_E_DEVICE, std::string("shift_plan_batch launch: ") + hipGetErrorString(s));
+  return RPM_OK;
+}
+}  // namespace
+
+// device-resident: at most four launches and the verdicts' on `stream`; after the first call on an engine nothing else
+int dev_shift_plan_batch(Engine& e, const ShiftArrays& a, int* d_nonfinite, void* stream) {
+  int rc = shift_check(e, a);
+  if (rc) return rc;
+  DeviceRestore restore;
+  rc = carry_devices(e, e);
+  if (rc) return rc;
+  return shift_launch(e, a, d_nonfinite, static_cast<hipStream_t>(stream));
+}
+
+// the same through host arrays: everything up through the staging slots into one device block, the results back; blocking
+int host_shift_plan_batch(Engine& e, const ShiftArrays& a, int* nonfinite) {
+  int rc = shift_check(e, a);
+  if (rc) return rc;
+  DeviceRestore restore;
+  rc = carry_devices(e, e);
+  if (rc) return rc;
+  Device& d = *e.dev;
+  HIP_TRY(e, hipSetDevice(d.device_id));
+  CarryState& cs = carry_state(d);
+  const size_t B = size_t(e.n_instances), Bp = B * e.P, Bn = B * e.n, Bm = B * e.m;
+  rc = cs.shift.ensure(e, Bp + 6 * Bn + 2 * Bm, B);
+  if (rc) return rc;
+  double* base = cs.shift.out;
+  ShiftArrays dv{};
+  double *d_dt = base, *d_x = d_dt + Bp, *d_lam = d_x + Bn, *d_zl = d_lam + Bm, *d_zu = d_zl + Bn;
+  dv.dt = d_dt; dv.x = d_x; dv.x_out = d_zu + Bn;
+  if (a.lambda) { dv.lambda = d_lam; dv.lambda_out = dv.x_out + Bn; }
+  if (a.z_L) { dv.z_L = d_zl; dv.z_U = d_zu; dv.z_L_out = dv.x_out + Bn + Bm; dv.z_U_out = dv.z_L_out + Bn; }
+  rc = dev_upload(e, d_dt, a.dt, Bp, STAGE_V);
+  if (rc == RPM_OK) rc = dev_upload(e, d_x, a.x, Bn, STAGE_X);
+  if (rc == RPM_OK && a.lambda) rc = dev_upload(e, d_lam, a.lambda, Bm, STAGE_LAMBDA);
+  if (rc == RPM_OK && a.z_L) rc = dev_upload(e, d_zl, a.z_L, Bn, STAGE_G);
+  if (rc == RPM_OK && a.z_L) rc = dev_upload(e, d_zu, a.z_U, Bn, STAGE_GRAD);
+  if (rc) return rc;
+  rc = shift_launch(e, dv, nonfinite ? cs.shift.flags : nullptr, d.stream);
+  if (rc == RPM_OK) rc = cs.shift.fetch(e, nonfinite, B);
+  if (rc == RPM_OK) rc = dev_download(e, a.x_out, dv.x_out, Bn, STAGE_X);
+  if (rc == RPM_OK && a.lambda) rc = dev_download(e, a.lambda_out, dv.lambda_out, Bm, STAGE_LAMBDA);
+  if (rc == RPM_OK && a.z_L) rc = dev_download(e, a.z_L_out, dv.z_L_out, Bn, STAGE_G);
+  if (rc == RPM_OK && a.z_L) rc = dev_download(e, a.z_U_out, dv.z_U_out, Bn, STAGE_GRAD);
+  if (rc) return rc;
+  return cs.shift.finish(e, nonfinite, B);
 }
 
 // the row map of the multiplier carry on the host: phase < P: {first defect row, first path row, first event row, one past the

@@ -272,6 +272,20 @@ int dev_carry_mult_batch(Engine& from, Engine& to, const double* d_x_from, const
                          void* stream);
 int host_carry_mult_batch(Engine& from, Engine& to, const double* x_from, const double* lam_from, double* lam_to, int* nonfinite);
 int carry_multipliers_layout(const Engine& e, int phase, int rows[4]);   // host only
+// the receding-horizon shift of a plan through the same kernel (from == to, every point moved by the instance's dt): x and lambda
+// as the two carries take them, z_L / z_U in x's layout piecewise linearly.  All host or all device pointers; lambda / lambda_out
+// both or neither, the four z arrays all or none.  shift_check decides every argument error on the host.
+struct ShiftArrays {
+  const double *dt, *x;
+  double* x_out;
+  const double* lambda;
+  double* lambda_out;
+  const double *z_L, *z_U;
+  double *z_L_out, *z_U_out;
+};
+int shift_check(Engine& e, const ShiftArrays& a);
+int dev_shift_plan_batch(Engine& e, const ShiftArrays& a, int* d_nonfinite, void* stream);
+int host_shift_plan_batch(Engine& e, const ShiftArrays& a, int* nonfinite);
 
 // rpm_extract_kernels.hip: Nlp2OpControl for all phases and all instances of the engine.  nlp2op_batch_layout is host only;
 // extract_check decides every error of the engine's state on the host, the two drivers call it before they touch a device.

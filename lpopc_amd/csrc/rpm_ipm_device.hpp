@@ -144,6 +144,7 @@ constexpr int IPM_VEC_PART = 24;     // doubles of partial results per workgroup
 constexpr int IPM_MT = 8;   // most 16-row tiles per wave of the factorisation: block columns of up to 4 x 8 x 16 = 512 rows
 
 // launchers (rpm_ipm_step_kernels.hip; assemble: rpm_kkt_factor.hip, inertia: rpm_kkt_solve.hip); all asynchronous on `st`
+void ipm_launch_set_state0(const IpmDev& D, int x_state0, int M, int nx, const double* d_state0, hipStream_t st);   // vl0 = vu0 = the measured states
 void ipm_launch_init(const IpmDev& D, const double* d_x0, hipStream_t st, int warm = 0);    // warm: the warm_start_* pushes, duals left to ipm_launch_warm_duals
 void ipm_launch_init_slack(const IpmDev& D, hipStream_t st, int warm = 0);
 // the warm start's lambda and z (d_zL / d_zU NULL: from mu_init) after the slacks and the scaling factors exist; non-finite input -> status 5

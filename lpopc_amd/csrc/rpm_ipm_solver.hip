@@ -418,6 +418,58 @@ int rpm_ipm_set_all_bounds(rpm_ipm* h, const double* x_l, const double* x_u) {
 
 }  // extern "C"
 
+namespace {
+// the measured initial states of a phase: every argument error, decided on the host.  All nx initial states must be fixed in the
+// plan, because the KKT layout is shared by all instances.
+int initial_states_check(rpm_ipm* h, const char* who, int phase, const void* state0) {
+  const Engine& e = h->eng->e;
+  if (phase < 0 || phase >= e.P) { h->err = std::string(who) + ": phase " + std::to_string(phase) + " is out of range"; return RPM_E_INVALID; }
+  if (!state0) { h->err = std::string(who) + ": state0 is NULL"; return RPM_E_INVALID; }
+  const PhaseHost& p = e.ph[size_t(phase)];
+  for (int j = 0; j < p.nx; ++j) {
+    const int i = p.var0 + j * (p.N + 1);
+    if (!h->plan.fixed[size_t(i)]) {
+      h->err = std::string(who) + ": variable " + std::to_string(i) + " (initial state " + std::to_string(j) +
+               ") is free in the solver's plan (the KKT layout is shared by all instances)";
+      return RPM_E_INVALID;
+    }
+  }
+  return RPM_OK;
+}
+}  // namespace
+
+extern "C" {
+
+/* vl0 = vu0 = state0[b][j] at variable x_state0 + j (N + 1) of every instance: one small launch on `stream`, no copy, no
+ * synchronisation */
+int rpm_ipm_set_initial_states_dev(rpm_ipm* h, int phase, const double* d_state0, void* stream) {
+  if (!h) return RPM_E_INVALID;
+  int rc = initial_states_check(h, "rpm_ipm_set_initial_states_dev", phase, d_state0);
+  if (rc) return rc;
+  const PhaseHost& p = h->eng->e.ph[size_t(phase)];
+  ipm_launch_set_state0(h->D, p.var0, p.N + 1, p.nx, d_state0, static_cast<hipStream_t>(stream));
+  return launch_check(h, "ipm_set_state0_kernel");
+}
+
+/* the same from a host array (n_instances x nx) through the engine's staging slot; blocking */
+int rpm_ipm_set_initial_states(rpm_ipm* h, int phase, const double* state0) {
+  if (!h) return RPM_E_INVALID;
+  int rc = initial_states_check(h, "rpm_ipm_set_initial_states", phase, state0);
+  if (rc) return rc;
+  Engine& e = h->eng->e;
+  const PhaseHost& p = e.ph[size_t(phase)];
+  double *d_x, *d_l, *d_zL, *d_zU;
+  if ((rc = host_form(h, &d_x, &d_l, &d_zL, &d_zU))) return rc;
+  rc = dev_upload(e, d_x, state0, size_t(h->D.B) * p.nx, STAGE_X);
+  if (rc) { h->err = e.err; return rc; }
+  ipm_launch_set_state0(h->D, p.var0, p.N + 1, p.nx, d_x, static_cast<hipStream_t>(dev_stream(e)));
+  if ((rc = launch_check(h, "ipm_set_state0_kernel"))) return rc;
+  if ((rc = dev_sync(e))) h->err = e.err;
+  return rc;
+}
+
+}  // extern "C"
+
 namespace rpm {
 int ipm_check_start_args(rpm_ipm* h, const char* who, const char* need, bool warm, const void* x, const void* lambda, const void* z_L,
                          const void* z_U) {

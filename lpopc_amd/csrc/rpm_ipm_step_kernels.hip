@@ -119,14 +119,18 @@ __device__ inline double push_inside(double x, double l, double u, bool lo, bool
 }
 // The cold start (warm = 0: bound_push / bound_frac, z = 1, lambda = 0, least-squares multipliers where the option asks) and the
 // warm start (warm = 1: the warm_start_* pushes; the duals are ipm_warm_duals_kernel's, after the scaling factors exist) share the
-// bounds, the fixed / free pattern, the push rule and the fresh instance record.
+// bounds, the fixed / free pattern, the push rule and the fresh instance record.  A NaN bound (a measured state that is one,
+// rpm_ipm_set_initial_states) compares unequal to itself: the variable would count as free of bounds while the KKT layout has it
+// fixed, so it ends the instance with status 5 before its first pass.
 __global__ __launch_bounds__(256) void ipm_init_kernel(IpmDev D, const double* x0, int warm) {
   const int bi = blockIdx.x;
   const size_t o = size_t(bi) * D.nv;
   const double push = warm ? D.o.ws_bound_push : D.o.bound_push, frac = warm ? D.o.ws_bound_frac : D.o.bound_frac;
+  int bad = 0;
   for (int i = threadIdx.x; i < D.n; i += blockDim.x) {
     double x = x0[size_t(bi) * D.n + i];
     double l = D.vl0[o + i], u = D.vu0[o + i];
+    bad |= (l != l) || (u != u);
     const bool lo = has_lo(l, u), up = has_up(l, u);
     if (l == u) x = l;
     else {
@@ -144,12 +148,25 @@ __global__ __launch_bounds__(256) void ipm_init_kernel(IpmDev D, const double* x
   }
   if (!warm)
     for (int r = threadIdx.x; r < D.m; r += blockDim.x) D.lam[size_t(bi) * D.m + r] = 0.0;
+  const int any_bad = __syncthreads_or(bad);
   if (threadIdx.x == 0) {
     IpmInst& S = D.inst[bi];
     S = IpmInst{};
     S.mu = D.o.mu_init;
     if (!warm && D.o.init_ls_mult && D.m > 0) { S.mode = 3; S.skip_update = -2; }   // first pass: least-squares multipliers at the starting point
+    if (any_bad) S.status = 5;
   }
+}
+// The measured initial states of a receding-horizon sweep written into the caller's bounds: vl0 = vu0 = state0[b][j] at variable
+// x_state0 + j M of every instance, nothing else touched.  One thread per (instance, state).
+__global__ __launch_bounds__(256) void ipm_set_state0_kernel(IpmDev D, int x_state0, int M, int nx, const double* __restrict__ state0) {
+  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= D.B * nx) return;
+  const int j = idx % nx, bi = idx / nx;
+  const size_t o = size_t(bi) * D.nv + x_state0 + size_t(j) * M;
+  const double s = state0[idx];
+  D.vl0[o] = s;
+  D.vu0[o] = s;
 }
 // slacks start at g(x0), pushed inside the (relaxed) [g_l, g_u] the same way
 __global__ __launch_bounds__(256) void ipm_init_slack_kernel(IpmDev D, int warm) {
@@ -881,6 +898,10 @@ static unsigned vec_threads(const IpmDev& D) { return D.B <= 32 && D.nv >= 4096 
 // workgroups per instance of the vector kernels that can split an instance (ipm_accept_kernel)
 static unsigned vec_blocks(const IpmDev& D) {
   return D.B <= 32 && D.nv >= 4096 ? unsigned(std::min(IPM_VEC_BLOCKS, (std::max(D.nv, D.m) + 1023) / 1024)) : 1u;
+}
+void ipm_launch_set_state0(const IpmDev& D, int x_state0, int M, int nx, const double* d_state0, hipStream_t st) {
+  if (D.B * nx == 0) return;
+  hipLaunchKernelGGL(ipm_set_state0_kernel, dim3(unsigned((D.B * nx + 255) / 256)), dim3(256), 0, st, D, x_state0, M, nx, d_state0);
 }
 void ipm_launch_init(const IpmDev& D, const double* d_x0, hipStream_t st, int warm) {
   hipLaunchKernelGGL(ipm_init_kernel, dim3(unsigned(D.B)), dim3(256), 0, st, D, d_x0, warm);

@@ -270,6 +270,40 @@ int rpm_sweep_carry_multipliers(rpm_sweep* from, rpm_sweep* to, const double* x_
       [&](size_t r) { return rpm_last_error(from->eng[r]); });
 }
 
+/* rpm_shift_plan_batch on every share, side by side: dt B x n_phases, x / z B x n, lambda B x m, nonfinite B or NULL */
+int rpm_sweep_shift_plan(rpm_sweep* s, const double* dt, const double* x, double* x_out, const double* lambda, double* lambda_out,
+                         const double* z_L, const double* z_U, double* z_L_out, double* z_U_out, int* nonfinite) {
+  if (!s) return RPM_E_INVALID;
+  if (!dt || !x || !x_out) {
+    s->err = "rpm_sweep_shift_plan: dt, x or x_out is NULL";
+    return RPM_E_INVALID;
+  }
+  const size_t P = size_t(s->eng[0]->e.P);
+  return for_each_share(
+      s,
+      [&](size_t r) {
+        const size_t i0 = size_t(s->first[r]);
+        auto at = [&](auto* p, size_t stride) { return p ? p + i0 * stride : nullptr; };
+        return rpm_shift_plan_batch(s->eng[r], dt + i0 * P, x + i0 * s->n, x_out + i0 * s->n, at(lambda, size_t(s->m)),
+                                    at(lambda_out, size_t(s->m)), at(z_L, size_t(s->n)), at(z_U, size_t(s->n)), at(z_L_out, size_t(s->n)),
+                                    at(z_U_out, size_t(s->n)), nonfinite ? nonfinite + i0 : nullptr);
+      },
+      [&](size_t r) { return rpm_last_error(s->eng[r]); });
+}
+
+/* rpm_ipm_set_initial_states of every share: state0 B x nx of the phase */
+int rpm_sweep_set_initial_states(rpm_sweep* s, int phase, const double* state0) {
+  if (!s) return RPM_E_INVALID;
+  if (!state0 || phase < 0 || phase >= s->eng[0]->e.P) {
+    s->err = !state0 ? "rpm_sweep_set_initial_states: state0 is NULL" : "rpm_sweep_set_initial_states: the phase index is out of range";
+    return RPM_E_INVALID;
+  }
+  const size_t nx = size_t(s->eng[0]->e.ph[size_t(phase)].nx);
+  return for_each_share(
+      s, [&](size_t r) { return rpm_ipm_set_initial_states(s->ipm[r], phase, state0 + size_t(s->first[r]) * nx); },
+      [&](size_t r) { return rpm_ipm_last_error(s->ipm[r]); });
+}
+
 /* rpm_nlp2op_batch on every share, side by side: x B x n, lambda B x m, out B x EB, nonfinite B or NULL */
 int rpm_sweep_nlp2op(rpm_sweep* s, const double* x, const double* lambda, double* out, int* nonfinite) {
   if (!s) return RPM_E_INVALID;

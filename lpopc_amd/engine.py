@@ -34,6 +34,8 @@ ABI_SYMBOLS = [
     "rpm_carry_multipliers_batch_dev", "rpm_carry_multipliers_batch", "rpm_carry_multipliers_layout", "rpm_sweep_carry_multipliers",
     "rpm_ipm_solve_warm", "rpm_ipm_solve_warm_dev", "rpm_ipm_get_bound_multipliers", "rpm_ipm_get_bound_multipliers_dev",
     "rpm_ipm_debug_start", "rpm_sweep_solve_warm", "rpm_sweep_get_bound_multipliers",
+    "rpm_shift_plan_batch_dev", "rpm_shift_plan_batch", "rpm_sweep_shift_plan",
+    "rpm_ipm_set_initial_states_dev", "rpm_ipm_set_initial_states", "rpm_sweep_set_initial_states",
     "rpm_nlp2op_batch_layout", "rpm_nlp2op_batch_dev", "rpm_nlp2op_batch", "rpm_sweep_nlp2op",
     "rpm_hpliu_create", "rpm_hpliu_destroy", "rpm_hpliu_last_error", "rpm_hpliu_refine",
     "rpm_ipm_create", "rpm_ipm_destroy", "rpm_ipm_last_error", "rpm_ipm_set_option", "rpm_ipm_set_bounds", "rpm_ipm_set_all_bounds", "rpm_ipm_get_info",
@@ -123,6 +125,12 @@ def lib(path=None):
     L.rpm_carry_multipliers_batch.argtypes = [vp, vp, dp, dp, dp, ip]
     L.rpm_carry_multipliers_layout.argtypes = [vp, C.c_int, ip]
     L.rpm_sweep_carry_multipliers.argtypes = [vp, vp, dp, dp, dp, ip]
+    L.rpm_shift_plan_batch_dev.argtypes = [vp] * 12
+    L.rpm_shift_plan_batch.argtypes = [vp] + [dp] * 9 + [ip]
+    L.rpm_sweep_shift_plan.argtypes = [vp] + [dp] * 9 + [ip]
+    L.rpm_ipm_set_initial_states_dev.argtypes = [vp, C.c_int, vp, vp]
+    L.rpm_ipm_set_initial_states.argtypes = [vp, C.c_int, dp]
+    L.rpm_sweep_set_initial_states.argtypes = [vp, C.c_int, dp]
     L.rpm_nlp2op_batch_layout.argtypes = [vp, C.c_int, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
     L.rpm_nlp2op_batch_dev.argtypes = [vp, vp, vp, vp, vp, vp]
     L.rpm_nlp2op_batch.argtypes = [vp, dp, dp, dp, ip]
@@ -630,6 +638,21 @@ class NLPEngine:
         self._check(self._L.rpm_carry_multipliers_batch_dev(self._h, to._h, self._ptr(d_x), self._ptr(d_lambda), self._ptr(d_lambda_to),
                                                             self._ptr(d_nonfinite), self._stream(stream)))
 
+    # ---- the receding-horizon shift of the sweep's plan and duals (rpm_shift_plan_batch*) -------------------------------
+    def shift_plan_batch(self, dt, x, lam=None, z=None):
+        """Every instance's plan moved on by its own dt (n_instances x n_phases) on this engine's mesh: x (n_instances x n),
+        lam (n_instances x m) or None, z = (z_L, z_U) (n_instances x n each) or None -> dict(x, nonfinite, and lambda / z_L, z_U
+        where they were given)."""
+        return _shift_plan(self._L.rpm_shift_plan_batch, self._check, self._h, self.n_instances, self.n_phases, self.n, self.m,
+                           dt, x, lam, z)
+
+    def shift_plan_batch_dev(self, d_dt, d_x, d_x_out, d_lambda=None, d_lambda_out=None, d_z_L=None, d_z_U=None, d_z_L_out=None,
+                             d_z_U_out=None, d_nonfinite=None, stream=None):
+        """Device-resident form on torch CUDA tensors (float64; d_nonfinite int32).  Asynchronous on `stream`."""
+        self._check(self._L.rpm_shift_plan_batch_dev(self._h, self._ptr(d_dt), self._ptr(d_x), self._ptr(d_x_out), self._ptr(d_lambda),
+                                                     self._ptr(d_lambda_out), self._ptr(d_z_L), self._ptr(d_z_U), self._ptr(d_z_L_out),
+                                                     self._ptr(d_z_U_out), self._ptr(d_nonfinite), self._stream(stream)))
+
     # ---- the extraction of a whole sweep: all phases, all instances (rpm_nlp2op_batch*) ---------------------------------
     def nlp2op_batch_layout(self):
         """(offsets, EB): per phase the offsets of time, state, control, costate, pathmult, hamiltonian, mayer_cost and
@@ -692,6 +715,26 @@ class NLPEngine:
     def shard_unpack_all_dev(self, d_gathered, d_g, d_values, skip_own=True, stream=None):
         self._check(self._L.rpm_shard_unpack_all_dev(self._h, self._ptr(d_gathered), self._ptr(d_g), self._ptr(d_values),
                                                      1 if skip_own else 0, self._stream(stream)))
+
+
+def _shift_plan(fn, check, handle, B, P, n, m, dt, x, lam, z):
+    """The host form of the shift for an engine or a sweep: arrays checked for size, results as a dict."""
+    def arr(a, cols, name):
+        a = np.ascontiguousarray(a, dtype=np.float64).ravel()
+        if a.size != B * cols:
+            raise RpmError(RPM_E_INVALID, "%s has %d entries, expected %d" % (name, a.size, B * cols))
+        return a
+    dt, x = arr(dt, P, "dt"), arr(x, n, "x")
+    out = {"x": np.zeros((B, n)), "nonfinite": np.zeros(B, dtype=np.int32)}
+    args = [None] * 6
+    if lam is not None:
+        out["lambda"] = np.zeros((B, m))
+        args[0], args[1] = _dp(arr(lam, m, "lambda")), _dp(out["lambda"])
+    if z is not None:
+        out["z_L"], out["z_U"] = np.zeros((B, n)), np.zeros((B, n))
+        args[2:] = [_dp(arr(z[0], n, "z_L")), _dp(arr(z[1], n, "z_U")), _dp(out["z_L"]), _dp(out["z_U"])]
+    check(fn(handle, _dp(dt), _dp(x), _dp(out["x"]), *args, _ip(out["nonfinite"])))
+    return out
 
 
 class HpLiuRefiner:
@@ -789,6 +832,20 @@ class BatchedIPM:
         x_l, x_u = np.ascontiguousarray(x_l, dtype=np.float64), np.ascontiguousarray(x_u, dtype=np.float64)
         assert x_l.shape == x_u.shape == (self._e.n_instances, self._e.n)
         self._chk(self._L.rpm_ipm_set_all_bounds(self._h, _dp(x_l), _dp(x_u)))
+
+    def set_initial_states(self, phase, state0):
+        """The measured initial states of `phase`, (n_instances, nx): lower = upper = state0 at every instance's initial
+        states, every other bound left alone."""
+        s0 = np.ascontiguousarray(state0, dtype=np.float64)
+        nx = self._e._desc.phases[int(phase)].nx if 0 <= int(phase) < self._e.n_phases else 0
+        if nx and s0.size != self._e.n_instances * nx:
+            raise RpmError(RPM_E_INVALID, "state0 has %d entries, expected %d" % (s0.size, self._e.n_instances * nx))
+        self._chk(self._L.rpm_ipm_set_initial_states(self._h, int(phase), _dp(s0)))
+
+    def set_initial_states_dev(self, phase, d_state0, stream=None):
+        """Device-resident form on a torch CUDA tensor (float64, n_instances x nx): one small launch on `stream`."""
+        self._chk(self._L.rpm_ipm_set_initial_states_dev(self._h, int(phase), C.c_void_p(d_state0.data_ptr()),
+                                                         NLPEngine._stream(stream)))
 
     def info(self):
         a = [C.c_int() for _ in range(4)]

@@ -7,7 +7,7 @@ import ctypes as C
 import numpy as np
 
 from . import _abi
-from .engine import RPM_E_INVALID, RPM_OK, RpmError, _batch_estimate, _batch_extract, _dp, _extract_layout, _ip, _phase_shapes, lib
+from .engine import RPM_E_INVALID, RPM_OK, RpmError, _batch_estimate, _batch_extract, _dp, _extract_layout, _ip, _phase_shapes, _shift_plan, lib
 
 
 class _EngineView:
@@ -244,6 +244,20 @@ class SweepGroup:
         flags = np.zeros(self.n_instances, dtype=np.int32)
         self._check(self._L.rpm_sweep_carry_multipliers(self._h, to._h, _dp(x), _dp(lam), _dp(out), _ip(flags)))
         return out, flags
+
+    def shift_plan(self, dt, x, lam=None, z=None):
+        """rpm_sweep_shift_plan: as NLPEngine.shift_plan_batch (dt: B x n_phases), over all shares; equal to one engine holding
+        all instances bit for bit."""
+        return _shift_plan(self._L.rpm_sweep_shift_plan, self._check, self._h, self.n_instances, self.n_phases, self.n, self.m,
+                           dt, x, lam, z)
+
+    def set_initial_states(self, phase, state0):
+        """rpm_sweep_set_initial_states: the measured initial states of `phase`, B x nx, to every share's solver."""
+        s0 = np.ascontiguousarray(state0, dtype=np.float64)
+        nx = self._desc.phases[int(phase)].nx if 0 <= int(phase) < self.n_phases else 0
+        if nx and s0.size != self.n_instances * nx:
+            raise RpmError(RPM_E_INVALID, "state0 has %d entries, expected %d" % (s0.size, self.n_instances * nx))
+        self._check(self._L.rpm_sweep_set_initial_states(self._h, int(phase), _dp(s0)))
 
     def nlp2op(self, x, lam):
         """rpm_sweep_nlp2op: as NLPEngine.nlp2op_batch, over all shares; equal to one engine holding all instances bit for bit."""

@@ -5,6 +5,13 @@ of the same dynamics.  Every step is solved three ways from the same measured st
 warm (the previous solution shifted, small mu_init, no push: the leg that drives the simulation) and primal + dual warm
 (rpm_ipm_solve_warm_dev: its own previous solution shifted, with that solve's lambda and bound multipliers).  Prints per-step solve
 time and iteration counts of all three.
+A fourth leg keeps the whole step on the device: the measured states (B x 12 doubles, the only upload) go into the solver's bounds
+with set_initial_states_dev, the warm solve, bound_multipliers_dev, then shift_plan_batch_dev moves x, lambda, z_L and z_U on by dt
+into a second set of buffers, and the plan's next initial state is read from the shifted plan on the device.  Its whole step, from
+bounds in to shifted plan out, is printed beside the primal + dual leg's, which is timed the same way with its set_all_bounds, its
+download, its np.interp shift and its upload; that leg shifts the states only and leaves lambda and z where they were.  A fifth leg
+is the fourth with everything around the solve replayed from two captured graphs (the bounds before it; multipliers, shift and
+the copy back into fixed buffers after it): the solve itself reads three counters per iteration on the host and cannot be captured.
 python tools/mpc_closed_loop.py [instances] [steps] [trace]
 "trace": where the slowest primal + dual instance of a step needs more iterations than the slowest primal-only one, its accepted
 steps are printed (f, theta, mu, alpha, alpha_z, delta_w, E_0, backtracks)."""
@@ -34,6 +41,7 @@ for b in range(B):
     eng.set_instance_constants(b, problems.quadrotor(K, NK, pref=tuple(targets[b])).GetOpimalProblemFuns().consts)
 ipm = BatchedIPM(eng, tol=1e-6)
 cold_ipm, dual_ipm = BatchedIPM(eng, tol=1e-6), BatchedIPM(eng, tol=1e-6)
+dev_ipm, graph_ipm = BatchedIPM(eng, tol=1e-6), BatchedIPM(eng, tol=1e-6)
 if want_trace:
     dual_ipm.set_option("trace", 64)
 one = NLPEngine(base, o, device=0)
@@ -54,6 +62,18 @@ d_zl3, d_zu3 = (torch.zeros((B, eng.n), dtype=torch.float64, device="cuda") for 
 t_at = (tau + 1.0) * horizon / 2.0
 
 
+def plan_buffers():
+    return [d_guess.clone(), torch.zeros((B, eng.m), dtype=torch.float64, device="cuda"),
+            torch.zeros((B, eng.n), dtype=torch.float64, device="cuda"), torch.zeros((B, eng.n), dtype=torch.float64, device="cuda")]
+
+
+cur4, nxt4, cur5, nxt5 = plan_buffers(), plan_buffers(), plan_buffers(), plan_buffers()
+d_dt = torch.full((B, 1), dt, dtype=torch.float64, device="cuda")
+d_state4, d_state5 = (torch.zeros((B, 12), dtype=torch.float64, device="cuda") for _ in range(2))
+d_x0_idx = torch.from_numpy(x0_idx).cuda()
+graphs = {}
+
+
 def timed(fn):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -70,30 +90,94 @@ def shifted(X):
     return torch.from_numpy(X)
 
 
+def warm_options(solver):
+    solver.set_option("mu_init", 1e-4)
+    for k in ("warm_start_bound_push", "warm_start_bound_frac", "warm_start_slack_bound_push", "warm_start_slack_bound_frac"):
+        solver.set_option(k, 1e-6)
+    solver.set_option("warm_start_mult_bound_push", 1e-8)
+
+
+def solve_plan(solver, plan, warm):
+    t0 = time.perf_counter()
+    if warm:
+        r = solver.solve_dev(plan[0], plan[1], d_z_L=plan[2], d_z_U=plan[3], warm=True)
+    else:                                             # no duals yet: a cold solve that keeps them
+        r = solver.solve_dev(plan[0], plan[1])
+    r["solve_ms"] = 1e3 * (time.perf_counter() - t0)
+    return r
+
+
+def device_step(warm):
+    """the fourth leg: measured states in, shifted plan out, the next initial state read from it"""
+    d_state4.copy_(torch.from_numpy(state))
+    dev_ipm.set_initial_states_dev(0, d_state4)
+    r = solve_plan(dev_ipm, cur4, warm)
+    dev_ipm.bound_multipliers_dev(cur4[2], cur4[3])
+    eng.shift_plan_batch_dev(d_dt, cur4[0], nxt4[0], cur4[1], nxt4[1], cur4[2], cur4[3], nxt4[2], nxt4[3])
+    r["next_state"] = nxt4[0].index_select(1, d_x0_idx)
+    return r
+
+
+def after_solve5():
+    graph_ipm.bound_multipliers_dev(cur5[2], cur5[3])
+    eng.shift_plan_batch_dev(d_dt, cur5[0], nxt5[0], cur5[1], nxt5[1], cur5[2], cur5[3], nxt5[2], nxt5[3])
+    for a, b_ in zip(cur5, nxt5):                     # fixed buffers: a graph replays the addresses it was captured with
+        a.copy_(b_)
+
+
+def graph_step(warm):
+    """the fifth leg: the fourth's step with the launches around the solve replayed from captured graphs"""
+    d_state5.copy_(torch.from_numpy(state))
+    if graphs:
+        graphs["before"].replay()
+    else:
+        graph_ipm.set_initial_states_dev(0, d_state5)
+    r = solve_plan(graph_ipm, cur5, warm)
+    if graphs:
+        graphs["after"].replay()
+        return r
+    after_solve5()                                    # the first step runs directly (the launch plans go up), then is captured
+    torch.cuda.synchronize()
+    side = torch.cuda.Stream()
+    graphs["before"], graphs["after"] = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graphs["before"], stream=side):
+        graph_ipm.set_initial_states_dev(0, d_state5)
+    with torch.cuda.graph(graphs["after"], stream=side):
+        after_solve5()
+    return r
+
+
+def host_step(warm):
+    """the primal + dual leg timed like the fourth: bounds up, solve, plan down, np.interp shift of the states, plan up"""
+    dual_ipm.set_all_bounds(XL, XU)
+    r = solve_plan(dual_ipm, [d_x3, d_lam3, d_zl3, d_zu3], warm)
+    if not warm:
+        dual_ipm.bound_multipliers_dev(d_zl3, d_zu3)
+    d_x3.copy_(shifted(d_x3.cpu().numpy()))
+    return r
+
+
 def leg(name, r, ms):
     return "%s %7.1f ms  it %d..%d  ok %d/%d" % (name, ms, r["iterations"].min(), r["iterations"].max(), int((r["status"] <= 1).sum()), B)
 
 
 for step in range(steps):
     XL[:, x0_idx] = XU[:, x0_idx] = state
-    for s_ in (ipm, cold_ipm, dual_ipm):
+    for s_ in (ipm, cold_ipm):
         s_.set_all_bounds(XL, XU)
     if step == 1:                                     # warm starts: small barrier, do not push the previous solution away
         ipm.set_option("mu_init", 1e-4)
         ipm.set_option("bound_push", 1e-6)
         ipm.set_option("bound_frac", 1e-6)
-        dual_ipm.set_option("mu_init", 1e-4)
-        for k in ("warm_start_bound_push", "warm_start_bound_frac", "warm_start_slack_bound_push", "warm_start_slack_bound_frac"):
-            dual_ipm.set_option(k, 1e-6)
-        dual_ipm.set_option("warm_start_mult_bound_push", 1e-8)
+        for s_ in (dual_ipm, dev_ipm, graph_ipm):
+            warm_options(s_)
     d_c = d_guess.clone()
     rc, ms_c = timed(lambda: cold_ipm.solve_dev(d_c))
     r, ms = timed(lambda: ipm.solve_dev(d_x))
-    if step == 0:                                     # no duals yet: a cold solve that keeps them
-        r3, ms3 = timed(lambda: dual_ipm.solve_dev(d_x3, d_lam3))
-        dual_ipm.bound_multipliers_dev(d_zl3, d_zu3)
-    else:
-        r3, ms3 = timed(lambda: dual_ipm.solve_dev(d_x3, d_lam3, d_z_L=d_zl3, d_z_U=d_zu3, warm=True))
+    r3, step3 = timed(lambda: host_step(step > 0))
+    ms3 = r3["solve_ms"]
+    r4, step4 = timed(lambda: device_step(step > 0))
+    r5, step5 = timed(lambda: graph_step(step > 0))
     X = d_x.cpu().numpy()
     # "plant": follow the planned state trajectory for dt (the plan is dynamically consistent to the mesh accuracy)
     for j in range(12):
@@ -107,5 +191,9 @@ for step in range(steps):
         print("  instance %d: primal + dual %d iterations, primal-only %d; its accepted steps:" % (worst, r3["iterations"][worst], r["iterations"][worst]))
         for row in dual_ipm.trace(worst, 64):
             print("   f %.9g  theta %.3e  mu %.3e  alpha %.3e  alpha_z %.3e  delta_w %.3e  E_0 %.3e  backtracks %d" % (tuple(row[:7]) + (int(row[7]),)))
+    print("         whole step, bounds in to shifted plan out: primal + dual (host shift, set_all_bounds) %7.1f ms | on the device %7.1f ms"
+          " (solve %.1f ms, it %d..%d, ok %d/%d) | with graphs %7.1f ms (it %d..%d) | next state, device plan against the plant: mean |diff| %.2e" % (
+              step3, step4, r4["solve_ms"], r4["iterations"].min(), r4["iterations"].max(), int((r4["status"] <= 1).sum()), B,
+              step5, r5["iterations"].min(), r5["iterations"].max(), np.abs(r4["next_state"].cpu().numpy() - state).mean()), flush=True)
     d_x.copy_(shifted(X))
-    d_x3.copy_(shifted(d_x3.cpu().numpy()))
+    cur4, nxt4 = nxt4, cur4
