@@ -409,7 +409,8 @@ int rpm_hpliu_refine(rpm_hpliu* h, rpm_engine* e, const double* x, const double*
  *   rpm_ipm_solve[_dev]: x (n_instances x n, in: starting points, out: solutions; host resp. device pointer),
  *                       lambda (n_instances x m, may be NULL); per instance on the host, any may be NULL: objective,
  *                       status (0 converged, 1 converged to Ipopt's acceptable level, 2 iteration limit, 3 line search failed where Ipopt would enter
- *                       restoration, 4 inertia correction failed, 5 NaN/Inf), iteration count, scaled KKT error
+ *                       restoration, 4 inertia correction failed, 5 NaN/Inf), iteration count, scaled KKT error; a NaN or Inf in an
+ *                       instance's starting point ends that instance with status 5 before its first pass and touches no other
  *   rpm_ipm_get_info:   order of the KKT system, of its banded part, half bandwidth, border size, doubles of storage per
  *                       instance, number of slack variables (one per inequality row) */
 typedef struct rpm_ipm rpm_ipm;

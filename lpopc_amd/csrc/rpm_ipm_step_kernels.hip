@@ -121,7 +121,8 @@ __device__ inline double push_inside(double x, double l, double u, bool lo, bool
 // warm start (warm = 1: the warm_start_* pushes; the duals are ipm_warm_duals_kernel's, after the scaling factors exist) share the
 // bounds, the fixed / free pattern, the push rule and the fresh instance record.  A NaN bound (a measured state that is one,
 // rpm_ipm_set_initial_states) compares unequal to itself: the variable would count as free of bounds while the KKT layout has it
-// fixed, so it ends the instance with status 5 before its first pass.
+// fixed, so it ends the instance with status 5 before its first pass.  So does a NaN or Inf in x0: fmax / fmin of the push rule
+// return their other argument for a NaN, which would start the instance from its bound as if nothing were wrong.
 __global__ __launch_bounds__(256) void ipm_init_kernel(IpmDev D, const double* x0, int warm) {
   const int bi = blockIdx.x;
   const size_t o = size_t(bi) * D.nv;
@@ -130,7 +131,7 @@ __global__ __launch_bounds__(256) void ipm_init_kernel(IpmDev D, const double* x
   for (int i = threadIdx.x; i < D.n; i += blockDim.x) {
     double x = x0[size_t(bi) * D.n + i];
     double l = D.vl0[o + i], u = D.vu0[o + i];
-    bad |= (l != l) || (u != u);
+    bad |= (l != l) || (u != u) || nonfinite(x);
     const bool lo = has_lo(l, u), up = has_up(l, u);
     if (l == u) x = l;
     else {
