@@ -489,6 +489,33 @@ int rpm_ipm_get_bound_multipliers_dev(rpm_ipm* s, double* d_z_L, double* d_z_U, 
  * (rpm_ipm_get_bound_multipliers: RPM_E_INVALID until the next solve). */
 int rpm_ipm_debug_start(rpm_ipm* s, int warm, const double* x, const double* lambda, const double* z_L, const double* z_U,
                         double* v_out, double* zL_out, double* zU_out, double* lam_out, double* mu_out, int* status_out);
+/* test hook (host pointers, synchronous): the iteration loop's own next steps on the state rpm_ipm_debug_start has just made, and
+ * what they wrote.  Valid only directly after rpm_ipm_debug_start on the same solver (no solve and no other debug call in between),
+ * else RPM_E_INVALID with a message; a second pass needs a second start.  It launches nothing of its own: the members of the solve
+ * loop (IpmLoop) and the production launchers.
+ *   stage 1  evaluation of f, grad f, g, the Jacobian ((nlp_scaling) scaled), grad_x L, the residual pass: c, the scalars of the
+ *            optimality error, the termination verdict, the barrier update, tau, phi; (limited-memory) the memory's first pass
+ *   stage 2  stage 1, then the exact Hessian (exact mode) and the assembly of the KKT matrix and its right-hand side.  Assembly of
+ *            the level-1 blocks by the factorisation kernel ("fused_fill") is off for this call, so the fill kernel writes the whole
+ *            storage.  Nothing is factored.
+ *   stage 3  stage 1, the Hessian, then assembly + factorisation with the inertia correction and the options as they are set,
+ *            the substitution and the direction kernel: dz, the step lengths, the slope.  No trial point is evaluated.
+ * As in the loop, the steps after stage 1 are skipped when no instance is left running.  Outputs, n_instances rows each, any may be
+ * NULL, an array of a later stage than the one asked for is left untouched; all in the solver's (scaled) problem:
+ *   after stage 1   obj (1), grad (n), g (m), jac (nnz_jac), c (m), glag (nv: grad_x L, -lambda_r at the slack of row r)
+ *   after stage 2   hess (nnz_h), k_storage (storage_doubles of rpm_ipm_get_info), rhs (Nt, unknown order: variables, slacks,
+ *                   multipliers); after stage 3 rhs holds the solution of the system and k_storage its factors
+ *   after stage 3   dv, dzL, dzU (nv), dlam (m)
+ *   always          record (RPM_IPM_RECORD_DOUBLES): the instance record, integers as doubles, in this order —
+ *                   mu tau f theta lnsum dinf cinf comp_max comp_min sum_lam sum_z err0 | delta_w delta_w_last alpha_max alpha_z
+ *                   alpha alpha_min dphi phi theta_max theta_min | status (the device's: 0 running, 1 converged, 6 acceptable level,
+ *                   2 .. 5 as rpm_ipm_solve) iter nfilt accepted refactor npos nneg nbad ls armijo nzb pad | mode resto_it
+ *                   enter_resto n_resto n_acc skip_update | th0 zeta mu_r th_r thr_max thr_min phi_r | nrfilt soc_on soc_req soc_p
+ *                   use_soc n_soc | alpha_soc az_soc th_old_soc | mu_max refs[0..3] | fixed_mode nrefs n_recalc
+ * The last solve's bound multipliers stay gone, as after rpm_ipm_debug_start. */
+#define RPM_IPM_RECORD_DOUBLES 64
+int rpm_ipm_debug_pass(rpm_ipm* s, int stage, double* obj, double* grad, double* g, double* jac, double* c, double* glag, double* hess,
+                       double* k_storage, double* rhs, double* dv, double* dlam, double* dzL, double* dzU, double* record);
 /* test hooks: KKT position of every unknown ([0,n) variables, slacks, then the m multipliers); factor + solve the
  * caller's matrices given in the band + border storage (host pointers, n_instances of each) */
 int rpm_ipm_get_permutation(rpm_ipm* s, int* pos, int capacity);

@@ -69,6 +69,25 @@ class rpm_segment(C.Structure):
     _fields_ = [("off", C.c_int), ("len", C.c_int), ("pos", C.c_int)]
 
 
+# rpm_ipm_debug_pass: the instance record as RPM_IPM_RECORD_DOUBLES doubles per instance, in this order (include/rpm_hip.h)
+IPM_RECORD_FIELDS = (
+    "mu", "tau", "f", "theta", "lnsum", "dinf", "cinf", "comp_max", "comp_min", "sum_lam", "sum_z", "err0",
+    "delta_w", "delta_w_last", "alpha_max", "alpha_z", "alpha", "alpha_min", "dphi", "phi", "theta_max", "theta_min",
+    "status", "iter", "nfilt", "accepted", "refactor", "npos", "nneg", "nbad", "ls", "armijo", "nzb", "pad",
+    "mode", "resto_it", "enter_resto", "n_resto", "n_acc", "skip_update",
+    "th0", "zeta", "mu_r", "th_r", "thr_max", "thr_min", "phi_r",
+    "nrfilt", "soc_on", "soc_req", "soc_p", "use_soc", "n_soc",
+    "alpha_soc", "az_soc", "th_old_soc", "mu_max", "refs0", "refs1", "refs2", "refs3",
+    "fixed_mode", "nrefs", "n_recalc")
+RPM_IPM_RECORD_DOUBLES = len(IPM_RECORD_FIELDS)     # 64
+# its outputs after the handle and the stage, in argument order
+IPM_PASS_OUTPUTS = ("obj", "grad", "g", "jac", "c", "glag", "hess", "K", "rhs", "dv", "dlam", "dzL", "dzU", "record")
+
+
+def bind_ipm_debug_pass(L):
+    L.rpm_ipm_debug_pass.argtypes = [C.c_void_p, C.c_int] + [c_double_p] * len(IPM_PASS_OUTPUTS)
+
+
 def _darr(values, keep):
     a = np.ascontiguousarray(np.asarray(values, dtype=np.float64).ravel())
     keep.append(a)

@@ -17,6 +17,7 @@ int debug_factor_solve(rpm_ipm* h, const double* store, double* rhs, size_t rhs_
   IpmDev& D = h->D;
   hipStream_t st = static_cast<hipStream_t>(dev_stream(h->eng->e));
   const size_t B = size_t(D.B);
+  h->debug_started = false;
   inst.assign(B, IpmInst{});
   for (IpmInst& s : inst) s.refactor = 1;
   IPM_TRY(h, hipMemcpyAsync(D.inst, inst.data(), B * sizeof(IpmInst), hipMemcpyHostToDevice, st));
@@ -60,6 +61,21 @@ void pivot_signs(const std::vector<IpmInst>& inst, int* n_pos, int* n_neg) {
     if (n_pos) n_pos[bi] = inst[bi].npos;
     if (n_neg) n_neg[bi] = inst[bi].nneg;
   }
+}
+// the instance record as rpm_ipm_debug_pass hands it out: every field up to n_recalc in declaration order, dbg left out (the order
+// is documented in rpm_hip.h and named in lpopc_amd/_abi.py: IPM_RECORD_FIELDS)
+void flat_record(const IpmInst& S, double* r) {
+  const double v[] = {S.mu, S.tau, S.f, S.theta, S.lnsum, S.dinf, S.cinf, S.comp_max, S.comp_min, S.sum_lam, S.sum_z, S.err0,
+                      S.delta_w, S.delta_w_last, S.alpha_max, S.alpha_z, S.alpha, S.alpha_min, S.dphi, S.phi, S.theta_max, S.theta_min,
+                      double(S.status), double(S.iter), double(S.nfilt), double(S.accepted), double(S.refactor), double(S.npos),
+                      double(S.nneg), double(S.nbad), double(S.ls), double(S.armijo), double(S.nzb), double(S.pad),
+                      double(S.mode), double(S.resto_it), double(S.enter_resto), double(S.n_resto), double(S.n_acc), double(S.skip_update),
+                      S.th0, S.zeta, S.mu_r, S.th_r, S.thr_max, S.thr_min, S.phi_r,
+                      double(S.nrfilt), double(S.soc_on), double(S.soc_req), double(S.soc_p), double(S.use_soc), double(S.n_soc),
+                      S.alpha_soc, S.az_soc, S.th_old_soc, S.mu_max, S.refs[0], S.refs[1], S.refs[2], S.refs[3],
+                      double(S.fixed_mode), double(S.nrefs), double(S.n_recalc)};
+  static_assert(sizeof(v) / sizeof(v[0]) == RPM_IPM_RECORD_DOUBLES, "RPM_IPM_RECORD_DOUBLES");
+  std::memcpy(r, v, sizeof(v));
 }
 int no_slot(rpm_ipm* h, const char* who, long long a, long long c) {
   h->err = std::string(who) + ": entry (" + std::to_string(a) + ", " + std::to_string(c) + ") has no slot in the layout";
@@ -149,6 +165,7 @@ int rpm_ipm_debug_lbfgs_step(rpm_ipm* h, int reset, const double* x, const doubl
   IpmDev& D = h->D;
   hipStream_t st = static_cast<hipStream_t>(dev_stream(h->eng->e));
   const size_t B = size_t(D.B), row = size_t(p.n) * sizeof(double), pitch = size_t(p.nv) * sizeof(double);
+  h->debug_started = false;
   IPM_TRY(h, hipMemcpyAsync(D.xt, x, B * row, hipMemcpyHostToDevice, st));
   if (reset) {
     ipm_launch_init(D, D.xt, st);
@@ -249,6 +266,77 @@ int rpm_ipm_debug_start(rpm_ipm* h, int warm, const double* x, const double* lam
   for (size_t bi = 0; bi < B; ++bi) {
     if (mu_out) mu_out[bi] = inst[bi].mu;
     if (status_out) status_out[bi] = inst[bi].status;
+  }
+  h->debug_started = true;
+  return RPM_OK;
+}
+
+/* test hook: the loop's own next steps (IpmLoop, rpm_ipm_solver.hpp) on the state rpm_ipm_debug_start has just made, and what they
+ * wrote.  stage 1: evaluate_and_residual.  stage 2: then exact_hessian (exact mode) and ipm_launch_assemble with level 1 left to the
+ * fill kernel (df_on off for this call), no factorisation.  stage 3: evaluate_and_residual, exact_hessian,
+ * factor_with_inertia_correction, substitute, direction — no trial point.  A pass after which no instance runs stops there, as the
+ * loop does. */
+int rpm_ipm_debug_pass(rpm_ipm* h, int stage, double* obj, double* grad, double* g, double* jac, double* c, double* glag, double* hess,
+                       double* k_storage, double* rhs, double* dv, double* dlam, double* dzL, double* dzU, double* record) {
+  if (!h) return RPM_E_INVALID;
+  if (stage < 1 || stage > 3) { h->err = "rpm_ipm_debug_pass: stage 1, 2 or 3"; return RPM_E_INVALID; }
+  if (!h->debug_started) { h->err = "rpm_ipm_debug_pass: valid only directly after rpm_ipm_debug_start on this solver"; return RPM_E_INVALID; }
+  h->debug_started = false;
+  Engine& e = h->eng->e;
+  IpmDev& D = h->D;
+  const IpmPlan& p = h->plan;
+  hipStream_t st = static_cast<hipStream_t>(dev_stream(e));
+  h->lb_iterations = 0;
+  h->total_factorizations = h->total_iterations = h->total_trials = h->total_soc = 0;
+  h->factor_ms = h->solve_ms = 0.0;
+  h->solve_pending = false;
+  const IpmLoop L{h, e, D, st, D.scal_on != 0};
+  int rc = L.evaluate_and_residual();
+  if (!rc && stage >= 2 && h->h_cnt[0] > 0) {
+    if (!h->lbfgs) rc = L.exact_hessian();
+    if (!rc && stage == 2) {
+      const int df_keep = D.df_on;
+      D.df_on = 0;
+      ipm_launch_assemble(D, std::max(e.nnz_jac, e.nnz_h), st);
+      D.df_on = df_keep;
+      rc = launch_check(h, "ipm_launch_assemble");
+    }
+    if (!rc && stage == 3) rc = L.factor_with_inertia_correction();
+    if (!rc && stage == 3) rc = L.substitute();
+    if (!rc && stage == 3) rc = L.direction();
+  }
+  h->solve_pending = false;
+  if (rc) return rc;
+  IPM_TRY(h, hipStreamSynchronize(st));
+  const size_t B = size_t(D.B), d8 = sizeof(double);
+  auto rows = [&](double* dst, const double* src, size_t width, size_t pitch) -> hipError_t {   // B rows of `width` doubles, `pitch` apart
+    if (!dst || !width) return hipSuccess;
+    return hipMemcpy2D(dst, width * d8, src, pitch * d8, width * d8, B, hipMemcpyDeviceToHost);
+  };
+  IPM_TRY(h, rows(obj, D.obj, 1, 1));
+  IPM_TRY(h, rows(grad, D.grad, size_t(p.n), size_t(p.n)));
+  IPM_TRY(h, rows(g, D.g, size_t(p.m), size_t(D.sg)));
+  IPM_TRY(h, rows(jac, D.jac, size_t(e.nnz_jac), size_t(D.sv)));
+  IPM_TRY(h, rows(c, D.c, size_t(p.m), size_t(p.m)));
+  IPM_TRY(h, rows(glag, D.glag, size_t(p.nv), size_t(p.nv)));
+  // what the stage did not write is left alone in the caller's arrays, not filled from stale device memory
+  if (stage >= 2 && !h->lbfgs) IPM_TRY(h, rows(hess, D.hess, size_t(e.nnz_h), size_t(e.nnz_h)));   // (limited-memory: there is none)
+  if (stage >= 2) IPM_TRY(h, rows(k_storage, D.K, size_t(p.storage()), size_t(p.storage())));
+  if (stage >= 3) {
+    IPM_TRY(h, rows(dv, D.dv, size_t(p.nv), size_t(p.nv)));
+    IPM_TRY(h, rows(dlam, D.dlam, size_t(p.m), size_t(p.m)));
+    IPM_TRY(h, rows(dzL, D.dzL, size_t(p.nv), size_t(p.nv)));
+    IPM_TRY(h, rows(dzU, D.dzU, size_t(p.nv), size_t(p.nv)));
+  }
+  if (rhs && stage >= 2) {
+    std::vector<double> r(B * size_t(p.Nt_alloc));
+    IPM_TRY(h, hipMemcpy(r.data(), D.rhs, r.size() * d8, hipMemcpyDeviceToHost));
+    from_kkt_order(p, B, r, rhs);
+  }
+  if (record) {
+    std::vector<IpmInst> inst(B);
+    IPM_TRY(h, hipMemcpy(inst.data(), D.inst, B * sizeof(IpmInst), hipMemcpyDeviceToHost));
+    for (size_t bi = 0; bi < B; ++bi) flat_record(inst[bi], record + bi * RPM_IPM_RECORD_DOUBLES);
   }
   return RPM_OK;
 }

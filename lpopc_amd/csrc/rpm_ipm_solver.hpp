@@ -1,6 +1,9 @@
 // rpm_ipm_solver.hpp — private to rpm_ipm_solver.hip (create, options, the loop, the solve entry points) and rpm_ipm_debug.hip
-// (the test hooks): the solver object behind the rpm_ipm handle and the few helpers both units use.
+// (the test hooks): the solver object behind the rpm_ipm handle, the few helpers both units use and the steps of the solve loop
+// (IpmLoop), which rpm_ipm_debug_pass runs one pass of.
 #pragma once
+#include <algorithm>
+#include <cstdio>
 #include <string>
 #include <vector>
 
@@ -27,6 +30,7 @@ struct rpm_ipm {
   bool lbfgs = false;            // hessian-approximation = limited-memory (rpm_ipm_lbfgs.hip)
   int lb_iterations = 0;         // iterations of the running solve: an upper bound of the pairs any instance holds
   bool solved = false;           // a solve has finished: D.zL / D.zU hold its bound multipliers (rpm_ipm_get_bound_multipliers)
+  bool debug_started = false;    // rpm_ipm_debug_start was the last call to touch the state: rpm_ipm_debug_pass may run on it
   double* d_host_form = nullptr; // the host-pointer entry points' device copies of x, lambda, z_L, z_U (B x (3 n + m)), on first use
   ~rpm_ipm() {
     if (attached && eng && eng->e.ipm_attached > 0) eng->e.ipm_attached -= 1;
@@ -82,5 +86,153 @@ int ipm_start(rpm_ipm* h, bool warm, const double* d_x, const double* d_lambda, 
 // the host-pointer entry points' device block, allocated once and kept (rpm_ipm_solve, rpm_ipm_solve_warm,
 // rpm_ipm_get_bound_multipliers, rpm_ipm_debug_start): x (B n), lambda (B m), z_L, z_U (B n each)
 int host_form(rpm_ipm* h, double** d_x, double** d_l, double** d_zL, double** d_zU);
+
+inline int ipm_abi_status(int device_status) {   // IpmInst::status -> rpm_hip.h: 0 converged, 1 converged to the acceptable level
+  return device_status == 1 ? 0 : (device_status == 6 ? 1 : device_status);
+}
+
+// ---- one solve: the steps of an iteration, in the order ipm_solve_dev takes them (rpm_ipm_debug_pass runs the first of them on an
+// injected state: the same members, no launch sequence of its own)
+struct IpmLoop {
+  rpm_ipm* h;
+  Engine& e;
+  IpmDev& D;
+  hipStream_t st;
+  bool scal;     // nlp_scaling is on
+  int eng_fail(int rc) const { h->err = e.err; return rc; }
+
+  int fetch_counts() const {
+    IPM_TRY(h, hipMemcpyAsync(h->h_cnt, D.cnt, 4 * sizeof(int), hipMemcpyDeviceToHost, st));
+    IPM_TRY(h, hipStreamSynchronize(st));
+    return RPM_OK;
+  }
+  // f, grad f, g, the Jacobian and the optimality residual at the current iterate; h_cnt[0]: instances still running
+  int evaluate_and_residual() const {
+    int rc;
+    ipm_launch_pack_x(D, st);
+    if ((rc = dev_eval_obj(e, D.xe, D.obj, D.grad, st))) return eng_fail(rc);
+    // D.jac is this solver's own array, written by the tile kernel only: its constant Doffdiag block (55 % of the metric
+    // problem's Jacobian) is written by the first evaluation of a solve and left alone afterwards (flag 16)
+    if ((rc = dev_eval_cons(e, D.xe, D.g, D.jac, 3 | 4 | 16, st))) return eng_fail(rc);
+    // (without the scaling's own evaluation the first pass of a solve writes the constant block too: then all of D.jac is scaled)
+    if (scal) ipm_launch_scale(D, D.g, D.jac, 0, D.nnz_var, D.obj, D.grad, st);
+    IPM_TRY(h, hipMemsetAsync(D.cnt, 0, 4 * sizeof(int), st));
+    ipm_launch_residual(D, st);
+    if (h->lbfgs) lb_launch_update(D, st);     // the pair of the step just taken (grad_x L at the new point is in D.glag)
+    return fetch_counts();
+  }
+  int exact_hessian() const {
+    if (scal) ipm_launch_scale_lambda(D, st);            // sf (H_f + sum (lambda_i sc_i / sf) H_ci)
+    if (int rc = dev_eval_h(e, D.xe, 1.0, scal ? D.lam_h : D.lam, D.hess, st)) return eng_fail(rc);
+    if (scal) ipm_launch_scale_hessian(D, st);
+    return RPM_OK;
+  }
+  // assemble and factor until no instance asks for another delta_w (Algorithm IC)
+  int factor_with_inertia_correction() const {
+    int rc;
+    for (int tries = 0; tries < 80; ++tries) {
+      IPM_TRY(h, hipMemsetAsync(D.cnt + 1, 0, sizeof(int), st));
+      ipm_launch_assemble(D, std::max(e.nnz_jac, e.nnz_h), st);
+      IPM_TRY(h, hipEventRecord(h->ev[0], st));
+      if ((rc = factor_and_solve_launch(h, st, true, false, 1))) return rc;
+      IPM_TRY(h, hipEventRecord(h->ev[1], st));
+      ipm_launch_inertia(D, st);
+      h->total_factorizations += 1;
+      if ((rc = fetch_counts())) return rc;
+      float ms = 0.f;
+      if (hipEventElapsedTime(&ms, h->ev[0], h->ev[1]) == hipSuccess) h->factor_ms += ms;
+      if (h->h_cnt[1] == 0) break;
+    }
+    return RPM_OK;
+  }
+  int substitute() const {
+    IPM_TRY(h, hipEventRecord(h->ev[2], st));
+    if (h->lbfgs && h->lb_iterations > 0) {
+      // Z = K0^-1 E with the factors in place (all columns of all instances in one pass), then C = M - E'Z
+      lb_launch_columns_and_solve(D, st);
+      lb_launch_small(D, st);
+    }
+    if (int rc = factor_and_solve_launch(h, st, false, true, 1, 1)) return rc;   // (the right-hand side the factorisation was given)
+    if (h->lbfgs) lb_launch_correct(D, 1, st);
+    IPM_TRY(h, hipEventRecord(h->ev[3], st));
+    h->solve_pending = true;   // its time is read once the line search's first fetch_counts has waited for it
+    return RPM_OK;
+  }
+  // the step, then rounds: every pending instance evaluates one trial point per round — its next backtracking step, or the next
+  // second-order correction (right-hand side, substitution with the factors in place, step lengths) where one was asked for
+  int direction() const {
+    IPM_TRY(h, hipMemsetAsync(D.cnt + 2, 0, 2 * sizeof(int), st));
+    ipm_launch_direction(D, st);
+    h->h_cnt[3] = 0;
+    return RPM_OK;
+  }
+  int line_search() const {
+    int rc;
+    if ((rc = direction())) return rc;
+    for (int ls = 0; ls <= D.o.max_ls + D.o.max_soc + 2; ++ls) {
+      if (h->h_cnt[3] > 0) {
+        ipm_launch_soc_rhs(D, st);
+        if ((rc = factor_and_solve_launch(h, st, false, true, 2))) return rc;
+        if (h->lbfgs) lb_launch_correct(D, 2, st);
+        ipm_launch_soc_direction(D, st);
+        h->total_soc += 1;
+      }
+      ipm_launch_trial(D, st);
+      if ((rc = dev_eval_obj(e, D.xt, D.objt, nullptr, st))) return eng_fail(rc);
+      if ((rc = dev_eval_cons(e, D.xt, D.gt, nullptr, 1 | 4, st))) return eng_fail(rc);
+      if (scal) ipm_launch_scale(D, D.gt, nullptr, 0, 0, D.objt, nullptr, st);
+      IPM_TRY(h, hipMemsetAsync(D.cnt + 2, 0, 2 * sizeof(int), st));
+      ipm_launch_accept(D, st);
+      h->total_trials += 1;
+      if ((rc = fetch_counts())) return rc;
+      if (h->solve_pending) {
+        float ms = 0.f;
+        if (hipEventElapsedTime(&ms, h->ev[2], h->ev[3]) == hipSuccess) h->solve_ms += ms;
+        h->solve_pending = false;
+      }
+      if (h->h_cnt[2] == 0 && h->h_cnt[3] == 0) break;
+    }
+    return RPM_OK;
+  }
+  int update() const {
+    ipm_launch_update(D, st);
+    if (h->lbfgs) {
+      ipm_launch_jt_lambda_into(D, D.lb_gold, st);   // grad_x L(x_old, lambda_new): D.grad / D.jac still belong to the old iterate
+      h->lb_iterations += 1;
+    }
+    return launch_check(h, "ipm iteration");
+  }
+  // x back into the caller's array, multipliers, per-instance verdicts
+  int collect(double* d_x, double* d_lambda, double* d_zL, double* d_zU, double* obj, int* status, int* iterations, double* kkt_error) const {
+    const size_t B = size_t(D.B);
+    ipm_launch_pack_x(D, st);
+    IPM_TRY(h, hipMemcpyAsync(d_x, D.xe, B * D.n * sizeof(double), hipMemcpyDeviceToDevice, st));
+    std::vector<double> sf_host;
+    if (d_lambda) {
+      if (scal) ipm_launch_unscale_lambda(D, d_lambda, st);     // the multipliers of the caller's (unscaled) rows
+      else IPM_TRY(h, hipMemcpyAsync(d_lambda, D.lam, B * D.m * sizeof(double), hipMemcpyDeviceToDevice, st));
+    }
+    if (d_zL && d_zU) ipm_launch_bound_multipliers(D, d_zL, d_zU, st);
+    if (scal) {
+      sf_host.resize(B);
+      IPM_TRY(h, hipMemcpyAsync(sf_host.data(), D.sf, B * sizeof(double), hipMemcpyDeviceToHost, st));
+    }
+    IPM_TRY(h, hipMemcpyAsync(h->h_inst.data(), D.inst, B * sizeof(IpmInst), hipMemcpyDeviceToHost, st));
+    IPM_TRY(h, hipStreamSynchronize(st));
+#ifdef IPM_TIMING
+    fprintf(stderr, "last factorisation of instance 0, phase clocks [100 MHz ticks]: T %lld  k-loop %lld  diag %lld  panel %lld  corner %lld  tail %lld | dense level 1, diagonal wave: waiting %lld  factoring %lld\n",
+            h->h_inst[0].dbg[0], h->h_inst[0].dbg[1], h->h_inst[0].dbg[2], h->h_inst[0].dbg[3], h->h_inst[0].dbg[4], h->h_inst[0].dbg[5], h->h_inst[0].dbg[6], h->h_inst[0].dbg[7]);
+#endif
+    for (size_t bi = 0; bi < B; ++bi) {
+      const IpmInst& S = h->h_inst[bi];
+      if (obj) obj[bi] = scal ? S.f / sf_host[bi] : S.f;
+      if (status) status[bi] = ipm_abi_status(S.status);
+      if (iterations) iterations[bi] = S.iter;
+      if (kkt_error) kkt_error[bi] = S.err0;
+    }
+    h->solved = true;
+    return RPM_OK;
+  }
+};
 
 }  // namespace rpm

@@ -45,7 +45,7 @@ ABI_SYMBOLS = [
     "rpm_sweep_create", "rpm_sweep_destroy", "rpm_sweep_last_error", "rpm_sweep_size", "rpm_sweep_engine", "rpm_sweep_solver", "rpm_sweep_share",
     "rpm_sweep_set_option", "rpm_sweep_set_bounds", "rpm_sweep_solve", "rpm_sweep_get_stats",
     "rpm_ipm_get_stats", "rpm_ipm_get_subproblems", "rpm_ipm_get_trace", "rpm_ipm_get_restorations", "rpm_ipm_get_kernel_times", "rpm_ipm_solve", "rpm_ipm_solve_dev", "rpm_ipm_get_permutation", "rpm_ipm_debug_solve", "rpm_ipm_debug_solve_dense", "rpm_ipm_debug_slot",
-    "rpm_ipm_debug_lbfgs_step", "rpm_ipm_debug_lbfgs_state", "rpm_ipm_debug_lbfgs_solve",
+    "rpm_ipm_debug_lbfgs_step", "rpm_ipm_debug_lbfgs_state", "rpm_ipm_debug_lbfgs_solve", "rpm_ipm_debug_pass",
 ]
 
 
@@ -162,6 +162,7 @@ def lib(path=None):
     L.rpm_ipm_get_bound_multipliers.argtypes = [vp, dp, dp]
     L.rpm_ipm_get_bound_multipliers_dev.argtypes = [vp, vp, vp, vp]
     L.rpm_ipm_debug_start.argtypes = [vp, C.c_int, dp, dp, dp, dp, dp, dp, dp, dp, dp, ip]
+    _abi.bind_ipm_debug_pass(L)
     L.rpm_ipm_get_permutation.argtypes = [vp, ip, C.c_int]
     L.rpm_ipm_debug_solve.argtypes = [vp, dp, dp, dp, ip, ip]
     L.rpm_ipm_debug_solve_dense.argtypes = [vp, dp, dp, dp, ip, ip]
@@ -1004,6 +1005,24 @@ class BatchedIPM:
         opt = lambda a: None if a is None else _dp(a)
         self._chk(self._L.rpm_ipm_debug_start(self._h, int(bool(warm)), _dp(x), opt(lam), opt(zl), opt(zu), _dp(out["v"]), _dp(out["zL"]),
                                               _dp(out["zU"]), _dp(out["lambda"]), _dp(out["mu"]), _ip(out["status"])))
+        return out
+
+    def debug_pass(self, stage):
+        """The loop's own next steps on the state debug_start has just made (rpm_ipm_debug_pass; valid only directly after
+        debug_start).  stage 1: evaluation + residual pass; 2: + Hessian and KKT assembly; 3: + factorisation, substitution and the
+        direction kernel.  -> dict of everything the hook returns, n_instances rows each: obj, grad, g, jac, c, glag, hess, K
+        (the KKT storage), rhs (unknown order; after stage 3 the solution), dv, dlam, dzL, dzU, record (_abi.IPM_RECORD_FIELDS), and
+        inst: the record as a dict of (n_instances,) arrays by field name."""
+        B, n, m = self._e.n_instances, self._e.n, self._e.m
+        info = self.info()
+        nv = n + info["n_slacks"]
+        width = {"obj": 1, "grad": n, "g": m, "jac": self._e.nnz_jac, "c": m, "glag": nv, "hess": self._e.nnz_h if self._e._desc.hessian_approximation == 1 else 0,   # (limited-memory: none)
+                 "K": info["storage_doubles"], "rhs": info["kkt_order"], "dv": nv,
+                 "dlam": m, "dzL": nv, "dzU": nv, "record": _abi.RPM_IPM_RECORD_DOUBLES}
+        out = {k: np.full((B, width[k]), np.nan) for k in _abi.IPM_PASS_OUTPUTS}
+        self._chk(self._L.rpm_ipm_debug_pass(self._h, int(stage), *[_dp(out[k]) for k in _abi.IPM_PASS_OUTPUTS]))
+        out["obj"] = out["obj"][:, 0]
+        out["inst"] = {name: out["record"][:, k] for k, name in enumerate(_abi.IPM_RECORD_FIELDS)}
         return out
 
     def solve_dev(self, d_x, d_lambda=None, stream=None, d_z_L=None, d_z_U=None, warm=False):

@@ -95,14 +95,16 @@ def _relaxed(l, u, lo, up, f):
 
 
 def _reference_start(one, XL, XU, x0, lam, z, o, warm):
-    """-> dict(v, zL, zU, lambda, mu), B rows each; `one`: a one-instance engine of the problem for g, grad f and the Jacobian"""
+    """-> dict(v, zL, zU, lambda, mu), B rows each; `one`: a one-instance engine of the problem for g, grad f and the Jacobian.
+    For the tests of the pass that follows (test_ipm_pass.py) also the relaxed bounds vl, vu (x, then the slacks) and the scaling
+    factors sc, sf."""
     _, _, gl, gu = one.get_bounds_info()
     B, n, m = len(x0), one.n, one.m
     srow = np.nonzero(gl != gu)[0]
     rows, cols = one.eval_jac_g_structure()
     if rows.max() == m or cols.max() == n:          # 1-based triplets
         rows, cols = rows - 1, cols - 1
-    out = {k: [] for k in ("v", "zL", "zU", "lambda")}
+    out = {k: [] for k in ("v", "zL", "zU", "lambda", "vl", "vu", "sc", "sf")}
     floor, big = o["warm_start_mult_bound_push"], o["warm_start_mult_init_max"]
     for b in range(B):
         l, u = XL[b], XU[b]
@@ -153,6 +155,10 @@ def _reference_start(one, XL, XU, x0, lam, z, o, warm):
         out["zL"].append(np.concatenate([zl, szl]))
         out["zU"].append(np.concatenate([zu, szu]))
         out["lambda"].append(lt)
+        out["vl"].append(np.concatenate([np.where(fixed, l, lr), slr]))
+        out["vu"].append(np.concatenate([np.where(fixed, u, ur), sur]))
+        out["sc"].append(sc)
+        out["sf"].append(sf)
     res = {k: np.stack(v) for k, v in out.items()}
     res["mu"] = np.full(B, o["mu_init"])
     return res
@@ -172,13 +178,20 @@ def _quadrotor_bounds(eng, B, seed=8, scale=0.2, base=None):
 OPEN = {}           # per problem: (variable of instance 0 without a lower bound, variable of instance 0 without an upper bound)
 
 
-def _start_case(name, open_bounds=True):
+def _start_case(name, open_bounds=True, B=None, options=None, nested=None):
+    """B, options (default: the exact Hessian), nested (engine option ipm_nested) and the launch problems: for test_ipm_pass.py"""
     if name == "quadrotor":
-        prob, B = problems.quadrotor(2, 4), 3
+        prob, B0 = problems.quadrotor(2, 4), 3
+    elif name == "bryson_denham":
+        prob, B0 = problems.bryson_denham(2, 8), 2
     else:
-        prob, B = problems.bryson_denham(2, 8), 2
-    eng = NLPEngine(prob, _exact(), n_instances=B, device=0)
-    one = NLPEngine(prob, _exact(), device=0)
+        prob, B0 = {"launch_2x5": problems.launch(2, 5), "launch_16x8": problems.launch(16, 8)}[name], 2
+    B = B or B0
+    options = options or _exact()
+    eng = NLPEngine(prob, options, n_instances=B, device=0)
+    if nested is not None:
+        eng.set_option("ipm_nested", nested)
+    one = NLPEngine(prob, options, device=0)
     xl, xu, gl, gu = eng.get_bounds_info()
     if name == "quadrotor":
         XL, XU, _ = _quadrotor_bounds(eng, B)
