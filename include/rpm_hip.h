@@ -315,6 +315,64 @@ int rpm_shift_plan_batch_dev(rpm_engine* e, const double* d_dt, const double* d_
 int rpm_shift_plan_batch(rpm_engine* e, const double* dt, const double* x, double* x_out, const double* lambda, double* lambda_out,
                          const double* z_L, const double* z_U, double* z_L_out, double* z_U_out, int* nonfinite);
 
+/* "The plan at time t" of a sweep: one phase's state and control columns of every instance evaluated at caller-given times.
+ * x: n_instances x n as the solver returns it; times: n_instances x n_times, instance-major, in the problem's time unit;
+ * out: n_instances x (nx + nu) x n_times, per instance column-major with n_times rows, the nx states first, then the nu
+ * controls (the shape of rpm_nlp2op_control's arrays).
+ * Per instance time[0], time[N] and the knots are the carry's, from x's t0 and tf.  The coordinate of a time t is
+ *   s = 2 (t - time[0]) / (time[N] - time[0]) - 1,   time[0] = post_time(t0, tf, tau_0), time[N] = post_time(t0, tf, 1),
+ * the very expression that forms the knots, so t = time[k] gives knot k to the bit; s is clamped into [-1, 1] with comparisons
+ * a NaN passes through: outside the horizon the end values are held.  A state column is the carry's natural cubic spline through
+ * its N + 1 knots, a control column that spline with its knot at 1 by the spline of a control; both are evaluated at s by the
+ * code the carry and the shift evaluate with.  At t = time[k], k < N, the node values of x come back to the bit; at time[N] a
+ * state's end value and the control-at-tau=1 row of rpm_nlp2op_batch.
+ * nonfinite: n_instances ints or NULL, 1 when any sample of the instance is NaN or Inf; an instance with NaN or Inf in its columns,
+ * its t0 / tf or its times, or with tf == t0, spoils itself only.
+ * Argument errors are decided on the host before anything is queued, the message is rpm_last_error(e): NULL x, times or out,
+ * n_times < 1, a phase out of range, out overlapping x or times: RPM_E_INVALID; an interval-sharded engine, a column that does
+ * not fit one workgroup's LDS: RPM_E_UNSUPPORTED; no device: RPM_E_DEVICE.
+ * The _dev form queues one launch (two with d_nonfinite) on `stream`.  After the first call on an engine it allocates nothing,
+ * copies nothing and never synchronises, whatever n_times is, and can be captured into a graph.  The host-pointer form stages its
+ * arrays and blocks.  The calling thread's current device is restored.  Options "carry_tile" and "carry_lds_bytes" apply (the
+ * columns are dealt over workgroups by the carry's planner); every value gives the same bits. */
+int rpm_sample_plan_batch_dev(rpm_engine* e, int phase, const double* d_x, int n_times, const double* d_times,
+                              double* d_out, int* d_nonfinite, void* stream);
+int rpm_sample_plan_batch(rpm_engine* e, int phase, const double* x, int n_times, const double* times, double* out, int* nonfinite);
+
+/* The plant of a sweep's closed loop: instance b integrates its own dynamics under its plan's control,
+ *   y' = f(t, y, u(t), p_b; consts_b),
+ * f the functor's dae() (path outputs ignored), p_b the plan's own static parameters, consts_b the instance's constants
+ * (rpm_set_instance_constants), over dt[b] from t_start[b] in n_steps classical Runge-Kutta steps of h = dt[b] / n_steps.
+ * x: n_instances x n, the plans; t_start: n_instances, or NULL = the phase's time[0]; dt: n_instances (0 returns the start state,
+ * a negative dt integrates backwards); state0: n_instances x nx, or NULL = the plan's own first state values; state_out:
+ * n_instances x nx, and it may be the very pointer state0 (a state updated in place); traj: NULL, or n_instances x (n_steps + 1)
+ * x nx, instance-major, row i the state after i steps (row 0 the start state).
+ * Per step, with t_i = t_start + i h:
+ *   k1 = f(t_i, y, u(t_i)), k2 = f(t_i + h / 2, y + (h / 2) k1, u(t_i + h / 2)), k3 = f(t_i + h / 2, y + (h / 2) k2, u(t_i + h / 2)),
+ *   k4 = f(t_i + h, y + h k3, u(t_i + h));  acc = k1; acc = acc + 2 k2; acc = acc + 2 k3; acc = acc + k4;  y = y + (h / 6) acc.
+ * hold == 0: u(t) is the sampling rule of rpm_sample_plan_batch for the control columns at each stage time, so the control the
+ * plant sees is the control the shift and the extraction see; hold == 1: u is that rule at t_start for the whole call, the
+ * zero-order hold a digital controller applies.  Past either end of the horizon the end value is held.  Controls are NOT clipped
+ * to their bounds: the spline of a plan at its bounds can overshoot them between nodes, and the plant receives what the plan says.
+ * One phase per call; events and phase boundaries are the caller's.
+ * nonfinite: n_instances ints or NULL, 1 when the start state or the state after any step is NaN or Inf; an instance with a NaN
+ * dt, t_start, state or control node, or with tf == t0, spoils itself only.
+ * Argument errors are decided on the host before anything is queued, the message is rpm_last_error(e): NULL x, dt or state_out,
+ * n_steps outside 1 ... 65536, hold not 0 or 1, a phase out of range, an output overlapping an input or the other output
+ * (state_out == state0 excepted): RPM_E_INVALID; an interval-sharded engine, the nu control columns of the phase not fitting one
+ * workgroup's LDS even at one instance per workgroup (the integrating lane needs all of them): RPM_E_UNSUPPORTED; no device:
+ * RPM_E_DEVICE.
+ * The _dev form queues one launch on `stream`; it allocates nothing, copies nothing and never synchronises, so it can follow
+ * rpm_ipm_solve_warm_dev and feed rpm_ipm_set_initial_states_dev on the caller's stream and be captured into a graph.  The
+ * host-pointer form stages its arrays and blocks.  The calling thread's current device is restored.  Option "rollout_tile"
+ * (0 = automatic, 1, 2, 4, 8): instances per workgroup; every value gives the same bits.  "carry_lds_bytes" lowers the LDS a
+ * workgroup may use here too.  User-problem libraries carry the kernel for their functor. */
+int rpm_rollout_batch_dev(rpm_engine* e, int phase, const double* d_x, const double* d_t_start, const double* d_dt,
+                          int n_steps, int hold, const double* d_state0, double* d_state_out, double* d_traj,
+                          int* d_nonfinite, void* stream);
+int rpm_rollout_batch(rpm_engine* e, int phase, const double* x, const double* t_start, const double* dt, int n_steps, int hold,
+                      const double* state0, double* state_out, double* traj, int* nonfinite);
+
 /* Solution extraction for a whole sweep: Nlp2OpConverter::Nlp2OpControl, Core/Nlp2OPConverter.cpp:13-196, for all phases and all
  * n_instances instances of the engine at once, every instance with its own constants (rpm_set_instance_constants) and static
  * parameters.  x: n_instances x n, lambda: n_instances x m, both packed and instance-major as rpm_ipm_solve[_dev] returns them.
@@ -762,6 +820,13 @@ int rpm_sweep_get_bound_multipliers(rpm_sweep* s, double* z_L, double* z_U);
 int rpm_sweep_shift_plan(rpm_sweep* s, const double* dt, const double* x, double* x_out, const double* lambda, double* lambda_out,
                          const double* z_L, const double* z_U, double* z_L_out, double* z_U_out, int* nonfinite);
 int rpm_sweep_set_initial_states(rpm_sweep* s, int phase, const double* state0);
+/* rpm_sample_plan_batch / rpm_rollout_batch on every share side by side (host arrays, all B instances, dealt as
+ * rpm_sweep_shift_plan deals them: times B x n_times, out B x (nx + nu) x n_times; t_start, dt B, state0 / state_out B x nx, traj
+ * B x (n_steps + 1) x nx): what one engine holding all B instances computes, bit for bit.  NULL x, times, out, dt or state_out, a
+ * phase, n_times or n_steps out of range: RPM_E_INVALID with the message in rpm_sweep_last_error(s). */
+int rpm_sweep_sample_plan(rpm_sweep* s, int phase, const double* x, int n_times, const double* times, double* out, int* nonfinite);
+int rpm_sweep_rollout(rpm_sweep* s, int phase, const double* x, const double* t_start, const double* dt, int n_steps, int hold,
+                      const double* state0, double* state_out, double* traj, int* nonfinite);
 /* rpm_nlp2op_batch on every share side by side (x: B x n, lambda: B x m, out: B x EB, nonfinite: B or NULL): what one engine
  * holding all B instances returns, bit for bit. */
 int rpm_sweep_nlp2op(rpm_sweep* s, const double* x, const double* lambda, double* out, int* nonfinite);

@@ -88,6 +88,18 @@ def bind_ipm_debug_pass(L):
     L.rpm_ipm_debug_pass.argtypes = [C.c_void_p, C.c_int] + [c_double_p] * len(IPM_PASS_OUTPUTS)
 
 
+def bind_rollout(L):
+    """rpm_sample_plan_batch* / rpm_rollout_batch* and their sweep forms: (handle, phase, x, n_times, times, out, nonfinite[, stream])
+    and (handle, phase, x, t_start, dt, n_steps, hold, state0, state_out, traj, nonfinite[, stream])"""
+    vp, i = C.c_void_p, C.c_int
+    L.rpm_sample_plan_batch_dev.argtypes = [vp, i, vp, i, vp, vp, vp, vp]
+    L.rpm_rollout_batch_dev.argtypes = [vp, i, vp, vp, vp, i, i, vp, vp, vp, vp, vp]
+    for fn in (L.rpm_sample_plan_batch, L.rpm_sweep_sample_plan):
+        fn.argtypes = [vp, i, c_double_p, i, c_double_p, c_double_p, c_int_p]
+    for fn in (L.rpm_rollout_batch, L.rpm_sweep_rollout):
+        fn.argtypes = [vp, i, c_double_p, c_double_p, c_double_p, i, i, c_double_p, c_double_p, c_double_p, c_int_p]
+
+
 def _darr(values, keep):
     a = np.ascontiguousarray(np.asarray(values, dtype=np.float64).ravel())
     keep.append(a)

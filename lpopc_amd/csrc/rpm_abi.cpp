@@ -450,6 +450,44 @@ int rpm_shift_plan_batch(rpm_engine* h, const double* dt, const double* x, doubl
   RPM_GUARD_END(e)
 }
 
+// ---- a sweep's plans sampled at caller-given times (rpm_carry_kernels.hip) and rolled out through the problem's own dynamics
+// (rpm_rollout_kernels.hip) ---------------------------------------------------------------------------------------------------
+int rpm_sample_plan_batch_dev(rpm_engine* h, int phase, const double* d_x, int n_times, const double* d_times, double* d_out,
+                              int* d_nonfinite, void* stream) {
+  if (!h) return RPM_E_INVALID;
+  Engine& e = h->e;
+  RPM_GUARD_BEGIN
+  return rpm::dev_sample_plan_batch(e, phase, d_x, n_times, d_times, d_out, d_nonfinite, stream);
+  RPM_GUARD_END(e)
+}
+
+int rpm_sample_plan_batch(rpm_engine* h, int phase, const double* x, int n_times, const double* times, double* out, int* nonfinite) {
+  if (!h) return RPM_E_INVALID;
+  Engine& e = h->e;
+  RPM_GUARD_BEGIN
+  return rpm::host_sample_plan_batch(e, phase, x, n_times, times, out, nonfinite);
+  RPM_GUARD_END(e)
+}
+
+int rpm_rollout_batch_dev(rpm_engine* h, int phase, const double* d_x, const double* d_t_start, const double* d_dt, int n_steps,
+                          int hold, const double* d_state0, double* d_state_out, double* d_traj, int* d_nonfinite, void* stream) {
+  if (!h) return RPM_E_INVALID;
+  Engine& e = h->e;
+  RPM_GUARD_BEGIN
+  return rpm::dev_rollout_batch(e, phase, rpm::RolloutArrays{d_x, d_t_start, d_dt, d_state0, d_state_out, d_traj}, n_steps, hold,
+                                d_nonfinite, stream);
+  RPM_GUARD_END(e)
+}
+
+int rpm_rollout_batch(rpm_engine* h, int phase, const double* x, const double* t_start, const double* dt, int n_steps, int hold,
+                      const double* state0, double* state_out, double* traj, int* nonfinite) {
+  if (!h) return RPM_E_INVALID;
+  Engine& e = h->e;
+  RPM_GUARD_BEGIN
+  return rpm::host_rollout_batch(e, phase, rpm::RolloutArrays{x, t_start, dt, state0, state_out, traj}, n_steps, hold, nonfinite);
+  RPM_GUARD_END(e)
+}
+
 int rpm_carry_multipliers_layout(rpm_engine* h, int phase, int rows[4]) {
   if (!h || !rows) return RPM_E_INVALID;
   if (rpm::carry_multipliers_layout(h->e, phase, rows)) return fail(h->e, RPM_E_INVALID, "carry_multipliers_layout: the phase index is out of range");
@@ -739,6 +777,10 @@ int rpm_set_option(rpm_engine* h, const char* key, int value) {
     if (value < 0) return fail(e, RPM_E_INVALID, "carry_lds_bytes must be 0 (what the device offers) or a byte count");
     e.opt_carry_lds = value;
     return RPM_OK;
+  } else if (k == "rollout_tile") {
+    if (value != 0 && value != 1 && value != 2 && value != 4 && value != 8) return fail(e, RPM_E_INVALID, "rollout_tile must be 0 (auto), 1, 2, 4 or 8");
+    e.opt_rollout_tile = value;
+    return RPM_OK;
   } else if (k == "extract_tile") {
     if (value != 0 && value != 1 && value != 2 && value != 4 && value != 8) return fail(e, RPM_E_INVALID, "extract_tile must be 0 (auto), 1, 2, 4 or 8");
     e.opt_extract_tile = value;
@@ -785,6 +827,7 @@ int rpm_get_option(rpm_engine* h, const char* key, int* value) {
   else if (k == "carry_tile") *value = e.opt_carry_tile;
   else if (k == "carry_lds_bytes") *value = e.opt_carry_lds;
   else if (k == "carry_groups") *value = rpm::carry_group_count(e);   // workgroups per tile of instances under the current options (0: a column does not fit)
+  else if (k == "rollout_tile") *value = e.opt_rollout_tile;
   else if (k == "extract_tile") *value = e.opt_extract_tile;
   else if (k == "extract_lds_bytes") *value = e.opt_extract_lds;
   else if (k == "extract_groups") *value = rpm::extract_group_count(e);   // workgroups per tile of instances of the spline launch (0: one fused launch, -1: a column does not fit)

@@ -12,7 +12,9 @@
 // rpm_get_starting_point) operation by operation; the cubes are A * A * A here and glibc's pow(A, 3) there.
 // The receding-horizon shift of a plan (rpm_shift_plan_batch*) is the same kernel with from == to and every evaluation point
 // moved by the instance's own 2 dt / (time[N] - time[0]), clamped into [-1, 1]; bound multipliers ride it piecewise linearly.
-#include "rpm_post_device.hpp"
+// The plans at caller-given times (rpm_sample_plan_batch*) are steps 1 - 3 and the spline of step 4 evaluated at the coordinate
+// of every time (rpm_sample_kernel).  The spline's rules are in rpm_carry_device.hpp, shared with the roll-out.
+#include "rpm_carry_device.hpp"
 
 namespace rpm {
 
@@ -21,22 +23,6 @@ struct CarryGroup {
   int phase, col0, ncols;
   int first;   // the phase's first group also writes t0, tf and the static parameters
 };
-
-// Dynamic LDS of rpm_carry_kernel, offsets in doubles.  Rows are Mp = (N + 1) | 1 doubles apart: the lanes that walk different
-// rows in step then sit on different banks (an odd number of doubles is 2 * odd dwords; 32 lanes x 2 dwords cover the 64 banks).
-struct CarryLds {
-  int Mp;
-  int pts;     // [Mp]               the source phase's LGR points
-  int tau;     // [TB][Mp]           knots tau_g of every instance
-  int mu;      // [TB][Mp]           mu of the forward recurrence: depends on the knots only
-  int y;       // [TB * ncols][Mp]   the columns, row = instance * ncols + column
-  int c;       // [TB * ncols][Mp]   z of the forward recurrence, overwritten by the second derivatives c
-  int total;
-  __host__ __device__ constexpr CarryLds(int M, int TB, int ncols)
-      : Mp(M | 1), pts(0), tau(Mp), mu(tau + TB * Mp), y(mu + TB * Mp), c(y + TB * ncols * Mp), total(c + TB * ncols * Mp) {}
-};
-static_assert(CarryLds(65, 8, 16).Mp == 65 && CarryLds(64, 1, 1).Mp == 65 && CarryLds(65, 8, 16).total == 65 * (1 + 16 + 2 * 128),
-              "CarryLds: an array overlaps its neighbour or the total changed");
 
 // A phase's rows of g / lambda: defects (nx x N, state-major), path rows (nc x N), events (ne); after the last phase's: the tail.
 struct CarryRows {
@@ -63,47 +49,8 @@ struct CarryShift {
   int P;
 };
 
-// spline_eval's tail (rpm_setup.cpp): binary search for the knot interval, then A, B as written there.  The search
-// halves kr - kl whatever the comparisons say, and its trip count is bounded besides: NaN knots cannot spin it.
-struct CarryAt {
-  int kl, kr;
-  double h, A, B;
-};
-__device__ __forceinline__ CarryAt carry_locate(double x, const double* xd, int n) {
-  int kl = 1, kr = n;
-  for (int it = 0; it < 32 && kr - kl > 1; ++it) {
-    const int k = (kr + kl) / 2;
-    if (xd[k - 1] > x) kr = k; else kl = k;
-  }
-  const double h = xd[kr - 1] - xd[kl - 1];
-  return CarryAt{kl, kr, h, (xd[kr - 1] - x) / h, (x - xd[kl - 1]) / h};
-}
-// the natural cubic spline there: Cc, Dd as spline_eval writes them
-__device__ __forceinline__ double carry_eval(double x, const double* xd, const double* yd, const double* c, int n) {
-  const CarryAt p = carry_locate(x, xd, n);
-  const double h = p.h, A = p.A, B = p.B;
-  const double Cc = (A * A * A - A) * (h * h) / 6.0, Dd = (B * B * B - B) * (h * h) / 6.0;
-  return A * yd[p.kl - 1] + B * yd[p.kr - 1] + Cc * c[p.kl - 1] + Dd * c[p.kr - 1];
-}
-// the same knots and search, the cubic terms dropped: a convex combination, non-negative columns stay non-negative.  A and B
-// are rounded separately, so the sum can come out an ulp outside the two knot values (x next to a knot): it is held between
-// them, with comparisons a NaN passes through.
-__device__ __forceinline__ double carry_eval_linear(double x, const double* xd, const double* yd, int n) {
-  const CarryAt p = carry_locate(x, xd, n);
-  const double yl = yd[p.kl - 1], yr = yd[p.kr - 1];
-  const double lo = yl < yr ? yl : yr, hi = yl < yr ? yr : yl;
-  double v = p.A * yl + p.B * yr;
-  v = v > hi ? hi : v;
-  return v < lo ? lo : v;
-}
-// A shifted evaluation point: tau moved on by dt in the instance's own time, then clamped into [-1, 1] so that a dt past
-// either end holds the end value; the comparisons are written so that a NaN passes through.
-__device__ __forceinline__ double carry_shifted(double tau, double dt, double t0, double tf, double tau_0) {
-  const double time_0 = post_time(t0, tf, tau_0), time_N = post_time(t0, tf, 1.0);
-  double s = tau + 2 * dt / (time_N - time_0);
-  s = s > 1.0 ? 1.0 : s;
-  return s < -1.0 ? -1.0 : s;
-}
+// CarryLds, the spline's helpers (carry_locate, carry_eval, carry_eval_linear, carry_shifted, carry_coord) and the three
+// per-workgroup stages between staging and evaluation: rpm_carry_device.hpp, shared with the roll-out.
 
 // Workgroup (group of columns of a phase, tile of TB instances), 256 threads.  x is instance-major with every column
 // contiguous in k, so the columns are staged with k-fastest loads; one lane per (instance, column) runs the recurrences out
@@ -138,14 +85,11 @@ rpm_carry_kernel(const PhaseDev* __restrict__ fph, const double* __restrict__ fp
 
   // ---- stage: points, every instance's knots, the columns ------------------------------------------------------
   for (int k = tid; k < N; k += nt) pts[k] = fp[k];
-  for (int idx = tid; idx < nb * M; idx += nt) {
-    const int k = idx % M, bi = idx / M;
+  carry_stage_knots(tau, Mp, fp, N, nb, [&](int bi, double* t0, double* tf) {
     const double* xb = x_from + size_t(b0 + bi) * n_from;
-    const double t0 = xb[pf.x_t0], tf = xb[pf.x_t0 + 1];
-    const double time_k = post_time(t0, tf, k < N ? fp[k] : 1.0);
-    const double time_0 = post_time(t0, tf, fp[0]), time_N = post_time(t0, tf, 1.0);
-    tau[bi * Mp + k] = 2 * (time_k - time_0) / (time_N - time_0) - 1;
-  }
+    *t0 = xb[pf.x_t0];
+    *tf = xb[pf.x_t0 + 1];
+  });
   for (int idx = tid; idx < nb * ncols * M; idx += nt) {
     const int k = idx % M, cl = (idx / M) % ncols, bi = idx / (M * ncols);
     const double* xb = x_from + size_t(b0 + bi) * n_from;
@@ -168,49 +112,12 @@ rpm_carry_kernel(const PhaseDev* __restrict__ fph, const double* __restrict__ fp
   if (lin) {   // piecewise linear: no recurrences; a control's knot at 1 holds its last node's value
     for (int r = tid; r < nb * ncols; r += nt)
       if (v.col0 + r % ncols >= nx) ys[r * Mp + N] = ys[r * Mp + N - 1];
-  } else if (tid < 64) {
-    for (int bi = tid; bi < nb; bi += 64) {
-      const double* xd = tau + bi * Mp;
-      double* m = mu + bi * Mp;
-      m[0] = 0.0;
-      for (int i = 1; i < M - 1; ++i) {
-        const double him1 = xd[i] - xd[i - 1], hi = xd[i + 1] - xd[i];
-        const double li = 2 * (xd[i + 1] - xd[i - 1]) - him1 * m[i - 1];
-        m[i] = hi / li;
-      }
-      m[M - 1] = 0.0;
-    }
-  } else {
-    for (int r = tid - 64; r < nb * ncols; r += nt - 64) {
-      if (v.col0 + r % ncols < nx) continue;
-      double* y = ys + r * Mp;
-      y[N] = post_spline_end(N, pts, [&](int k) -> double { return y[k]; });
-    }
-  }
+  } else
+    carry_stage_mu_and_ends(tau, mu, ys, pts, Mp, N, nb, ncols, [&](int r) { return v.col0 + r % ncols >= nx; });
   __syncthreads();
 
   // ---- one lane per (instance, column): forward recurrence, back substitution, interior c doubled ------------------
-  for (int r = tid; r < (lin ? 0 : nb * ncols); r += nt) {
-    const double* xd = tau + (r / ncols) * Mp;
-    const double* m = mu + (r / ncols) * Mp;
-    const double* y = ys + r * Mp;
-    double* c = cs + r * Mp;
-    double z = 0.0;
-    c[0] = 0.0;
-    for (int i = 1; i < M - 1; ++i) {
-      const double him1 = xd[i] - xd[i - 1], hi = xd[i + 1] - xd[i];
-      const double alpha = 3.0 / hi * (y[i + 1] - y[i]) - 3.0 / him1 * (y[i] - y[i - 1]);
-      const double li = 2 * (xd[i + 1] - xd[i - 1]) - him1 * m[i - 1];
-      z = (alpha - him1 * z) / li;
-      c[i] = z;
-    }
-    c[M - 1] = 0.0;
-    double next = 0.0;   // c[j + 1] before its doubling
-    for (int j = M - 2; j >= 0; --j) {
-      next = c[j] - m[j] * next;
-      c[j] = j >= 1 ? 2 * next : next;
-    }
-  }
+  carry_stage_second(tau, mu, ys, cs, Mp, M, lin ? 0 : nb * ncols, ncols);
   __syncthreads();
 
   // ---- evaluate and store: states at the target's points and at 1.0, controls at the points ---------------------
@@ -261,6 +168,57 @@ rpm_carry_kernel(const PhaseDev* __restrict__ fph, const double* __restrict__ fp
     }
 }
 
+// The plans sampled at caller-given times (rpm_sample_plan_batch*): the carry's staging, knots and recurrences for one phase's
+// columns, every column then evaluated with carry_eval at carry_coord(t) of the instance's n_times times.  Workgroup (group of
+// columns of the phase, tile of TB instances); out: per instance (nx + nu) columns of n_times rows, states first.
+__global__ void __launch_bounds__(256)
+rpm_sample_kernel(const PhaseDev* __restrict__ phd, const double* __restrict__ points, int n, const CarryGroup* __restrict__ groups,
+                  int B, int TB, const double* __restrict__ x, int n_times, const double* __restrict__ times, double* __restrict__ out) {
+  extern __shared__ __align__(16) double sample_sm[];
+  const CarryGroup v = groups[blockIdx.x];
+  const PhaseDev pf = phd[v.phase];
+  const int N = pf.N, M = N + 1, nx = pf.nx, ncols = v.ncols;
+  const CarryLds L(M, TB, ncols);
+  const int Mp = L.Mp;
+  double* pts = sample_sm + L.pts;
+  double* tau = sample_sm + L.tau;
+  double* mu = sample_sm + L.mu;
+  double* ys = sample_sm + L.y;
+  double* cs = sample_sm + L.c;
+  const int b0 = blockIdx.y * TB;
+  const int nb = B - b0 < TB ? B - b0 : TB;
+  const int tid = threadIdx.x, nt = blockDim.x;
+  const double* fp = points + pf.node0;
+  for (int k = tid; k < N; k += nt) pts[k] = fp[k];
+  carry_stage_knots(tau, Mp, fp, N, nb, [&](int bi, double* t0, double* tf) {
+    const double* xb = x + size_t(b0 + bi) * n;
+    *t0 = xb[pf.x_t0];
+    *tf = xb[pf.x_t0 + 1];
+  });
+  for (int idx = tid; idx < nb * ncols * M; idx += nt) {
+    const int k = idx % M, cl = (idx / M) % ncols, bi = idx / (M * ncols);
+    const double* xb = x + size_t(b0 + bi) * n;
+    const int col = v.col0 + cl;
+    double val = 0.0;   // a control's entry at tau = 1 is computed below
+    if (col < nx) val = xb[pf.x_state0 + col * M + k];
+    else if (k < N) val = xb[pf.x_control0 + (col - nx) * N + k];
+    ys[(bi * ncols + cl) * Mp + k] = val;
+  }
+  __syncthreads();
+  carry_stage_mu_and_ends(tau, mu, ys, pts, Mp, N, nb, ncols, [&](int r) { return v.col0 + r % ncols >= nx; });
+  __syncthreads();
+  carry_stage_second(tau, mu, ys, cs, Mp, M, nb * ncols, ncols);
+  __syncthreads();
+  const int cols = nx + pf.nu;
+  for (long long idx = tid; idx < (long long)nb * ncols * n_times; idx += nt) {
+    const int q = int(idx % n_times), r = int(idx / n_times), bi = r / ncols, cl = r % ncols;
+    const size_t b = size_t(b0 + bi);
+    const double* xb = x + b * n;
+    const double s = carry_coord(times[b * n_times + q], xb[pf.x_t0], xb[pf.x_t0 + 1], fp[0]);
+    out[(b * cols + v.col0 + cl) * n_times + q] = carry_eval(s, tau + bi * Mp, ys + r * Mp, cs + r * Mp, M);
+  }
+}
+
 static CarryRows carry_rows(const Engine& e, int phase) {
   const PhaseHost& p = e.ph[size_t(phase)];
   return CarryRows(p.con0, p.N, p.nx, p.nc, p.ne);
@@ -275,11 +233,13 @@ struct CarryPlan {
   int TB = 1, n_groups = 0;
   size_t lds = 0;
   CarryGroup* d_groups = nullptr;
+  std::vector<int> group0;         // per phase its first group, then n_groups: the sampler launches one phase's groups
 };
 struct CarryState {
   std::vector<CarryPlan> plans;
   HostForm host;    // host-pointer form: the carried block
   HostForm shift;   // host-pointer form of the shift: dt, the four inputs and the four outputs in one block
+  HostForm sample;  // host-pointer form of the sampler: the times and the samples in one block
 };
 
 size_t carry_budget(const Engine& from) {
@@ -338,35 +298,49 @@ CarryState& carry_state(Device& d) {
   return *static_cast<CarryState*>(d.carry);
 }
 
+// The launch plan of a pair of engines under from's options, made on the first call: the only allocation and the only blocking
+// copy.  Makes from's device current.
+int carry_plan_for(Engine& from, const Engine& to, int mult, const std::string& who, const CarryPlan** out) {
+  Device& d = *from.dev;
+  HIP_TRY(from, hipSetDevice(d.device_id));
+  CarryState& cs = carry_state(d);
+  for (const CarryPlan& p : cs.plans)
+    if (p.to_serial == to.serial && p.tile_opt == from.opt_carry_tile && p.lds_opt == from.opt_carry_lds && p.mult == mult) {
+      *out = &p;
+      return RPM_OK;
+    }
+  CarryPlan p;
+  std::vector<CarryGroup> groups;
+  if (!carry_plan(from, mult, &p.TB, &groups, &p.lds)) {
+    from.err = who + ": a column does not fit one workgroup's LDS";
+    return RPM_E_UNSUPPORTED;
+  }
+  p.mult = mult;
+  p.to_serial = to.serial;
+  p.tile_opt = from.opt_carry_tile;
+  p.lds_opt = from.opt_carry_lds;
+  p.n_groups = int(groups.size());
+  p.group0.assign(size_t(from.P) + 1, p.n_groups);   // groups are phase-major: phase i owns [group0[i], group0[i + 1])
+  for (int g = p.n_groups - 1; g >= 0; --g) p.group0[size_t(groups[size_t(g)].phase)] = g;
+  for (int i = from.P - 1; i >= 0; --i) p.group0[size_t(i)] = std::min(p.group0[size_t(i)], p.group0[size_t(i) + 1]);
+  HIP_TRY(from, upload(&p.d_groups, groups));
+  HIP_TRY(from, raise_dynamic_lds(reinterpret_cast<const void*>(rpm_carry_kernel), p.lds));
+  HIP_TRY(from, raise_dynamic_lds(reinterpret_cast<const void*>(rpm_sample_kernel), p.lds));
+  cs.plans.push_back(p);
+  *out = &cs.plans.back();
+  return RPM_OK;
+}
+
 // d_lam_from NULL: the solutions, x_from -> x_to; else the multipliers, lam_from -> lam_to with x_from's t0 / tf for the knots.
 // sh.dt not NULL: the shift of a plan (from == to); sh.z_from not NULL: a bound-multiplier array z_from -> x_to.
 int carry_launch(Engine& from, Engine& to, const double* d_x_from, double* d_x_to, const double* d_lam_from, double* d_lam_to,
                  int* d_nonfinite, hipStream_t st, CarryShift sh = CarryShift{}) {
   const std::string who = sh.dt ? "shift_plan_batch" : (d_lam_from ? "carry_multipliers_batch" : "carry_solution_batch");
-  Device& d = *from.dev;
-  HIP_TRY(from, hipSetDevice(d.device_id));
-  CarryState& cs = carry_state(d);
-  const CarryPlan* plan = nullptr;
   const int mult = d_lam_from ? 1 : 0;
-  for (const CarryPlan& p : cs.plans)
-    if (p.to_serial == to.serial && p.tile_opt == from.opt_carry_tile && p.lds_opt == from.opt_carry_lds && p.mult == mult) plan = &p;
-  if (!plan) {   // first call on this pair of engines: the only allocation and the only blocking copy
-    CarryPlan p;
-    std::vector<CarryGroup> groups;
-    if (!carry_plan(from, mult, &p.TB, &groups, &p.lds)) {
-      from.err = who + ": a column does not fit one workgroup's LDS";
-      return RPM_E_UNSUPPORTED;
-    }
-    p.mult = mult;
-    p.to_serial = to.serial;
-    p.tile_opt = from.opt_carry_tile;
-    p.lds_opt = from.opt_carry_lds;
-    p.n_groups = int(groups.size());
-    HIP_TRY(from, upload(&p.d_groups, groups));
-    HIP_TRY(from, raise_dynamic_lds(reinterpret_cast<const void*>(rpm_carry_kernel), p.lds));
-    cs.plans.push_back(p);
-    plan = &cs.plans.back();
-  }
+  const CarryPlan* plan = nullptr;
+  const int rc = carry_plan_for(from, to, mult, who, &plan);
+  if (rc) return rc;
+  Device& d = *from.dev;
   const int B = from.n_instances;
   CarryMult cm{};
   if (mult) cm = CarryMult{d_lam_from, d_lam_to, d.kp, to.dev->d_weights, from.m, to.m, from.P};
@@ -396,6 +370,7 @@ void carry_destroy(Device* d) {
     if (p.d_groups) (void)hipFree(p.d_groups);
   cs->host.release();
   cs->shift.release();
+  cs->sample.release();
   delete cs;
   d->carry = nullptr;
 }
@@ -624,6 +599,91 @@ int host_shift_plan_batch(Engine& e, const ShiftArrays& a, int* nonfinite) {
   if (rc == RPM_OK && a.z_L) rc = dev_download(e, a.z_U_out, dv.z_U_out, Bn, STAGE_GRAD);
   if (rc) return rc;
   return cs.shift.finish(e, nonfinite, B);
+}
+
+// ---- the plans sampled at caller-given times: one phase's columns through rpm_sample_kernel ------------------------------
+
+// every argument error of the sampler, decided on the host before a device is touched (all host or all device pointers)
+int sample_check(Engine& e, int phase, const void* x, int n_times, const void* times, const void* out) {
+  const std::string who = "sample_plan_batch: ";
+  if (!x) return carry_fail(e, RPM_E_INVALID, who + "x is NULL");
+  if (!times) return carry_fail(e, RPM_E_INVALID, who + "times is NULL");
+  if (!out) return carry_fail(e, RPM_E_INVALID, who + "out is NULL");
+  if (n_times < 1) return carry_fail(e, RPM_E_INVALID, who + "n_times must be at least 1");
+  if (phase < 0 || phase >= e.P) return carry_fail(e, RPM_E_INVALID, who + "the phase index is out of range");
+  const PhaseHost& p = e.ph[size_t(phase)];
+  const size_t B = size_t(e.n_instances), bytes_x = B * e.n * sizeof(double), bytes_t = B * size_t(n_times) * sizeof(double),
+               bytes_o = bytes_t * size_t(p.nx + p.nu);
+  auto overlap = [](const void* u, size_t nu, const void* v, size_t nv) {
+    const char *a = static_cast<const char*>(u), *b = static_cast<const char*>(v);
+    return nu && nv && a < b + nv && b < a + nu;
+  };
+  if (overlap(out, bytes_o, x, bytes_x)) return carry_fail(e, RPM_E_INVALID, who + "out and x overlap");
+  if (overlap(out, bytes_o, times, bytes_t)) return carry_fail(e, RPM_E_INVALID, who + "out and times overlap");
+  if (sharded(e)) return carry_fail(e, RPM_E_UNSUPPORTED, who + "not with interval sharding");
+  int TB = 0;
+  size_t lds = 0;
+  if (!carry_plan(e, 0, &TB, nullptr, &lds)) {
+    int most = 0;
+    for (const PhaseHost& q : e.ph) most = std::max(most, q.N + 1);
+    return carry_fail(e, RPM_E_UNSUPPORTED, who + "a column of " + std::to_string(most) + " knots does not fit one workgroup's LDS");
+  }
+  return RPM_OK;
+}
+
+namespace {
+int sample_launch(Engine& e, int phase, const double* d_x, int n_times, const double* d_times, double* d_out, int* d_nonfinite,
+                  hipStream_t st) {
+  const CarryPlan* plan = nullptr;
+  const int rc = carry_plan_for(e, e, 0, "sample_plan_batch", &plan);
+  if (rc) return rc;
+  Device& d = *e.dev;
+  const PhaseHost& p = e.ph[size_t(phase)];
+  const int B = e.n_instances, g0 = plan->group0[size_t(phase)], ng = plan->group0[size_t(phase) + 1] - g0;
+  hipLaunchKernelGGL(rpm_sample_kernel, dim3(unsigned(ng), unsigned((B + plan->TB - 1) / plan->TB)), dim3(256), plan->lds, st, d.d_phases,
+                     d.d_points, e.n, plan->d_groups + g0, B, plan->TB, d_x, n_times, d_times, d_out);
+  if (d_nonfinite) flag_launch((long long)(p.nx + p.nu) * n_times, d_out, d_nonfinite, B, st);
+  const hipError_t s = hipGetLastError();
+  if (s != hipSuccess) return carry_fail(e, RPM_E_DEVICE, std::string("sample_plan_batch launch: ") + hipGetErrorString(s));
+  return RPM_OK;
+}
+}  // namespace
+
+// device-resident: one launch (two with the verdicts) on `stream`; after the first call on an engine nothing else
+int dev_sample_plan_batch(Engine& e, int phase, const double* d_x, int n_times, const double* d_times, double* d_out, int* d_nonfinite,
+                          void* stream) {
+  int rc = sample_check(e, phase, d_x, n_times, d_times, d_out);
+  if (rc) return rc;
+  DeviceRestore restore;
+  rc = carry_devices(e, e);
+  if (rc) return rc;
+  return sample_launch(e, phase, d_x, n_times, d_times, d_out, d_nonfinite, static_cast<hipStream_t>(stream));
+}
+
+// the same through host arrays: x and the times up through the staging slots, the samples and the verdicts back; blocking
+int host_sample_plan_batch(Engine& e, int phase, const double* x, int n_times, const double* times, double* out, int* nonfinite) {
+  int rc = sample_check(e, phase, x, n_times, times, out);
+  if (rc) return rc;
+  DeviceRestore restore;
+  rc = carry_devices(e, e);
+  if (rc) return rc;
+  Device& d = *e.dev;
+  HIP_TRY(e, hipSetDevice(d.device_id));
+  CarryState& cs = carry_state(d);
+  const PhaseHost& p = e.ph[size_t(phase)];
+  const size_t B = size_t(e.n_instances), Bt = B * size_t(n_times), Bo = Bt * size_t(p.nx + p.nu);
+  rc = cs.sample.ensure(e, Bt + Bo, B);
+  if (rc) return rc;
+  double *d_times = cs.sample.out, *d_out = d_times + Bt;
+  host_new_x(e);   // d_x is about to hold other values than the callbacks' last x
+  rc = dev_upload(e, d.d_x, x, B * e.n, STAGE_X);
+  if (rc == RPM_OK) rc = dev_upload(e, d_times, times, Bt, STAGE_V);
+  if (rc) return rc;
+  rc = sample_launch(e, phase, d.d_x, n_times, d_times, d_out, nonfinite ? cs.sample.flags : nullptr, d.stream);
+  if (rc == RPM_OK) rc = cs.sample.fetch(e, nonfinite, B);
+  if (rc == RPM_OK) rc = dev_download(e, out, d_out, Bo, STAGE_G);
+  if (rc) return rc;
+  return cs.sample.finish(e, nonfinite, B);
 }
 
 // the row map of the multiplier carry on the host: phase < P: {first defect row, first path row, first event row, one past the

@@ -218,6 +218,7 @@ void device_destroy(Engine& e) {
   mesh_batch_destroy(d);
   carry_destroy(d);
   extract_destroy(d);
+  rollout_destroy(d);
   rpm_pin_release_owner(&e);   // this engine's holds; pages another engine still addresses stay registered
   dev_stage_destroy(d);
   for (auto& row : d->segtab)

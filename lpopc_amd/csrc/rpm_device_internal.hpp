@@ -126,6 +126,7 @@ struct Device {
   void* mesh_batch = nullptr;   // tables and workspace of the batched mesh-error estimate (rpm_post_kernels.hip), built on first use
   void* carry = nullptr;        // launch plans of the batched carry, one per target engine (rpm_carry_kernels.hip), built on first use
   void* extract = nullptr;      // launch plans and workspace of the batched extraction (rpm_extract_kernels.hip), built on first use
+  void* rollout = nullptr;      // host-pointer form's block of the batched roll-out (rpm_rollout_kernels.hip), built on first use
   struct SegTable { void* ptr = nullptr; int count = 0; int stride = -1; };
   SegTable segtab[2][2];        // [g|values][pack|unpack] run tables of the interval sharding
 };
@@ -238,6 +239,7 @@ void exchange_destroy(Device* d);    // rpm_peer.hip
 void mesh_batch_destroy(Device* d);  // rpm_post_kernels.hip
 void carry_destroy(Device* d);       // rpm_carry_kernels.hip
 void extract_destroy(Device* d);     // rpm_extract_kernels.hip
+void rollout_destroy(Device* d);     // rpm_rollout_kernels.hip
 
 // rpm_tile_kernels.hip: occupancy, LDS size and eligibility of the pipelined kernel for this engine (device_init)
 void tile_pipeline_setup(Engine& e, Device* d, const ProblemDims& pd, int device_id);

@@ -184,6 +184,7 @@ struct Engine {
   int opt_mesh_err_tile = 0;     // batched mesh-error estimate: instances per workgroup (0: as many of 8, 4, 2, 1 as the LDS tile holds)
   int opt_carry_tile = 0;        // batched carry: instances per workgroup (0: automatic)
   int opt_carry_lds = 0;         // batched carry: LDS bytes one workgroup may use (0: what the device offers; smaller values are for tests of the column split)
+  int opt_rollout_tile = 0;      // batched roll-out: instances per workgroup (0: automatic)
   int opt_extract_tile = 0;      // batched extraction: instances per workgroup (0: automatic)
   int opt_extract_lds = 0;       // batched extraction: LDS bytes one workgroup's staged arrays may use (0: what the device offers; smaller values are for tests of the column split)
   long long serial = 0;          // unique per rpm_create in this process: what a cached launch plan names its target engine by
@@ -286,6 +287,23 @@ struct ShiftArrays {
 int shift_check(Engine& e, const ShiftArrays& a);
 int dev_shift_plan_batch(Engine& e, const ShiftArrays& a, int* d_nonfinite, void* stream);
 int host_shift_plan_batch(Engine& e, const ShiftArrays& a, int* nonfinite);
+// one phase's plans sampled at n_times caller-given times per instance, through the carry's knots, recurrences and carry_eval
+// (rpm_carry_device.hpp); out: n_instances x (nx + nu) x n_times.  sample_check decides every argument error on the host.
+int sample_check(Engine& e, int phase, const void* x, int n_times, const void* times, const void* out);
+int dev_sample_plan_batch(Engine& e, int phase, const double* d_x, int n_times, const double* d_times, double* d_out, int* d_nonfinite,
+                          void* stream);
+int host_sample_plan_batch(Engine& e, int phase, const double* x, int n_times, const double* times, double* out, int* nonfinite);
+
+// rpm_rollout_kernels.hip: every instance's dynamics integrated under its plan's control (classical Runge-Kutta).  All host or
+// all device pointers; t_start, state0 and traj may be NULL, state_out may be state0.  rollout_check decides every argument error
+// on the host.
+struct RolloutArrays {
+  const double *x, *t_start, *dt, *state0;
+  double *state_out, *traj;
+};
+int rollout_check(Engine& e, int phase, const RolloutArrays& a, int n_steps, int hold);
+int dev_rollout_batch(Engine& e, int phase, const RolloutArrays& a, int n_steps, int hold, int* d_nonfinite, void* stream);
+int host_rollout_batch(Engine& e, int phase, const RolloutArrays& a, int n_steps, int hold, int* nonfinite);
 
 // rpm_extract_kernels.hip: Nlp2OpControl for all phases and all instances of the engine.  nlp2op_batch_layout is host only;
 // extract_check decides every error of the engine's state on the host, the two drivers call it before they touch a device.

@@ -291,6 +291,48 @@ int rpm_sweep_shift_plan(rpm_sweep* s, const double* dt, const double* x, double
       [&](size_t r) { return rpm_last_error(s->eng[r]); });
 }
 
+/* rpm_sample_plan_batch on every share, side by side: x B x n, times B x n_times, out B x (nx + nu) x n_times, nonfinite B or NULL */
+int rpm_sweep_sample_plan(rpm_sweep* s, int phase, const double* x, int n_times, const double* times, double* out, int* nonfinite) {
+  if (!s) return RPM_E_INVALID;
+  if (!x || !times || !out || n_times < 1 || phase < 0 || phase >= s->eng[0]->e.P) {
+    s->err = (!x || !times || !out) ? "rpm_sweep_sample_plan: x, times or out is NULL"
+                                    : (n_times < 1 ? "rpm_sweep_sample_plan: n_times must be at least 1" : "rpm_sweep_sample_plan: the phase index is out of range");
+    return RPM_E_INVALID;
+  }
+  const rpm::PhaseHost& p = s->eng[0]->e.ph[size_t(phase)];
+  const size_t nt = size_t(n_times), block = size_t(p.nx + p.nu) * nt;
+  return for_each_share(
+      s,
+      [&](size_t r) {
+        const size_t i0 = size_t(s->first[r]);
+        return rpm_sample_plan_batch(s->eng[r], phase, x + i0 * s->n, n_times, times + i0 * nt, out + i0 * block,
+                                     nonfinite ? nonfinite + i0 : nullptr);
+      },
+      [&](size_t r) { return rpm_last_error(s->eng[r]); });
+}
+
+/* rpm_rollout_batch on every share, side by side: x B x n, t_start (or NULL) and dt B, state0 (or NULL) and state_out B x nx, traj
+ * B x (n_steps + 1) x nx or NULL, nonfinite B or NULL */
+int rpm_sweep_rollout(rpm_sweep* s, int phase, const double* x, const double* t_start, const double* dt, int n_steps, int hold,
+                      const double* state0, double* state_out, double* traj, int* nonfinite) {
+  if (!s) return RPM_E_INVALID;
+  if (!x || !dt || !state_out || n_steps < 1 || n_steps > 65536 || phase < 0 || phase >= s->eng[0]->e.P) {
+    s->err = (!x || !dt || !state_out) ? "rpm_sweep_rollout: x, dt or state_out is NULL"
+                                       : ((n_steps < 1 || n_steps > 65536) ? "rpm_sweep_rollout: n_steps must be 1 ... 65536" : "rpm_sweep_rollout: the phase index is out of range");
+    return RPM_E_INVALID;
+  }
+  const size_t nx = size_t(s->eng[0]->e.ph[size_t(phase)].nx), row = (size_t(n_steps) + 1) * nx;
+  return for_each_share(
+      s,
+      [&](size_t r) {
+        const size_t i0 = size_t(s->first[r]);
+        return rpm_rollout_batch(s->eng[r], phase, x + i0 * s->n, t_start ? t_start + i0 : nullptr, dt + i0, n_steps, hold,
+                                 state0 ? state0 + i0 * nx : nullptr, state_out + i0 * nx, traj ? traj + i0 * row : nullptr,
+                                 nonfinite ? nonfinite + i0 : nullptr);
+      },
+      [&](size_t r) { return rpm_last_error(s->eng[r]); });
+}
+
 /* rpm_ipm_set_initial_states of every share: state0 B x nx of the phase */
 int rpm_sweep_set_initial_states(rpm_sweep* s, int phase, const double* state0) {
   if (!s) return RPM_E_INVALID;

@@ -35,6 +35,8 @@ ABI_SYMBOLS = [
     "rpm_ipm_solve_warm", "rpm_ipm_solve_warm_dev", "rpm_ipm_get_bound_multipliers", "rpm_ipm_get_bound_multipliers_dev",
     "rpm_ipm_debug_start", "rpm_sweep_solve_warm", "rpm_sweep_get_bound_multipliers",
     "rpm_shift_plan_batch_dev", "rpm_shift_plan_batch", "rpm_sweep_shift_plan",
+    "rpm_sample_plan_batch_dev", "rpm_sample_plan_batch", "rpm_sweep_sample_plan",
+    "rpm_rollout_batch_dev", "rpm_rollout_batch", "rpm_sweep_rollout",
     "rpm_ipm_set_initial_states_dev", "rpm_ipm_set_initial_states", "rpm_sweep_set_initial_states",
     "rpm_nlp2op_batch_layout", "rpm_nlp2op_batch_dev", "rpm_nlp2op_batch", "rpm_sweep_nlp2op",
     "rpm_hpliu_create", "rpm_hpliu_destroy", "rpm_hpliu_last_error", "rpm_hpliu_refine",
@@ -128,6 +130,7 @@ def lib(path=None):
     L.rpm_shift_plan_batch_dev.argtypes = [vp] * 12
     L.rpm_shift_plan_batch.argtypes = [vp] + [dp] * 9 + [ip]
     L.rpm_sweep_shift_plan.argtypes = [vp] + [dp] * 9 + [ip]
+    _abi.bind_rollout(L)
     L.rpm_ipm_set_initial_states_dev.argtypes = [vp, C.c_int, vp, vp]
     L.rpm_ipm_set_initial_states.argtypes = [vp, C.c_int, dp]
     L.rpm_sweep_set_initial_states.argtypes = [vp, C.c_int, dp]
@@ -654,6 +657,33 @@ class NLPEngine:
                                                      self._ptr(d_lambda_out), self._ptr(d_z_L), self._ptr(d_z_U), self._ptr(d_z_L_out),
                                                      self._ptr(d_z_U_out), self._ptr(d_nonfinite), self._stream(stream)))
 
+    # ---- the plans at caller-given times and the plant under them (rpm_sample_plan_batch*, rpm_rollout_batch*) ------------
+    def sample_plan_batch(self, phase, x, times):
+        """One phase's plans x (n_instances x n) at times (n_instances x n_times, the problem's time unit; outside the horizon
+        the end values are held) -> (samples: n_instances x (nx + nu) x n_times, states first; nonfinite: n_instances ints)."""
+        return _sample_plan(self._L.rpm_sample_plan_batch, self._check, self._h, self._desc, self.n_instances, self.n, phase, x, times)
+
+    def sample_plan_batch_dev(self, phase, d_x, n_times, d_times, d_out, d_nonfinite=None, stream=None):
+        """Device-resident form on torch CUDA tensors (float64; d_nonfinite int32).  Asynchronous on `stream`."""
+        self._check(self._L.rpm_sample_plan_batch_dev(self._h, int(phase), self._ptr(d_x), int(n_times), self._ptr(d_times),
+                                                      self._ptr(d_out), self._ptr(d_nonfinite), self._stream(stream)))
+
+    def rollout_batch(self, phase, x, dt, n_steps, hold=0, state0=None, t_start=None, traj=False):
+        """Every instance's own dynamics integrated under its plan x (n_instances x n) over dt (n_instances) in n_steps classical
+        Runge-Kutta steps, from state0 (n_instances x nx; None: the plan's first state values) at t_start (n_instances; None: the
+        phase's first time).  hold=1: the control of t_start for the whole call.  Controls are not clipped to their bounds.
+        -> dict(state: n_instances x nx, nonfinite: n_instances ints, and with traj=True traj: n_instances x (n_steps + 1) x nx)."""
+        return _rollout(self._L.rpm_rollout_batch, self._check, self._h, self._desc, self.n_instances, self.n, phase, x, dt, n_steps,
+                        hold, state0, t_start, traj)
+
+    def rollout_batch_dev(self, phase, d_x, d_dt, n_steps, d_state_out, hold=0, d_state0=None, d_t_start=None, d_traj=None,
+                          d_nonfinite=None, stream=None):
+        """Device-resident form on torch CUDA tensors (float64; d_nonfinite int32); d_state_out may be d_state0 (in place).
+        One launch, asynchronous on `stream`."""
+        self._check(self._L.rpm_rollout_batch_dev(self._h, int(phase), self._ptr(d_x), self._ptr(d_t_start), self._ptr(d_dt),
+                                                  int(n_steps), int(hold), self._ptr(d_state0), self._ptr(d_state_out),
+                                                  self._ptr(d_traj), self._ptr(d_nonfinite), self._stream(stream)))
+
     # ---- the extraction of a whole sweep: all phases, all instances (rpm_nlp2op_batch*) ---------------------------------
     def nlp2op_batch_layout(self):
         """(offsets, EB): per phase the offsets of time, state, control, costate, pathmult, hamiltonian, mayer_cost and
@@ -721,10 +751,7 @@ class NLPEngine:
 def _shift_plan(fn, check, handle, B, P, n, m, dt, x, lam, z):
     """The host form of the shift for an engine or a sweep: arrays checked for size, results as a dict."""
     def arr(a, cols, name):
-        a = np.ascontiguousarray(a, dtype=np.float64).ravel()
-        if a.size != B * cols:
-            raise RpmError(RPM_E_INVALID, "%s has %d entries, expected %d" % (name, a.size, B * cols))
-        return a
+        return _sized(a, B, cols, name)
     dt, x = arr(dt, P, "dt"), arr(x, n, "x")
     out = {"x": np.zeros((B, n)), "nonfinite": np.zeros(B, dtype=np.int32)}
     args = [None] * 6
@@ -735,6 +762,48 @@ def _shift_plan(fn, check, handle, B, P, n, m, dt, x, lam, z):
         out["z_L"], out["z_U"] = np.zeros((B, n)), np.zeros((B, n))
         args[2:] = [_dp(arr(z[0], n, "z_L")), _dp(arr(z[1], n, "z_U")), _dp(out["z_L"]), _dp(out["z_U"])]
     check(fn(handle, _dp(dt), _dp(x), _dp(out["x"]), *args, _ip(out["nonfinite"])))
+    return out
+
+
+def _sized(a, B, cols, name):
+    a = np.ascontiguousarray(a, dtype=np.float64).ravel()
+    if a.size != B * cols:
+        raise RpmError(RPM_E_INVALID, "%s has %d entries, expected %d" % (name, a.size, B * cols))
+    return a
+
+
+def _phase_dims(desc, phase):
+    """(nx, nu) of a phase; (0, 0) for an index out of range, which the library then refuses with its own message"""
+    phase = int(phase)
+    return (desc.phases[phase].nx, desc.phases[phase].nu) if 0 <= phase < desc.n_phases else (0, 0)
+
+
+def _sample_plan(fn, check, handle, desc, B, n, phase, x, times):
+    """The host form of the sampler for an engine or a sweep: arrays checked for size, results shaped."""
+    nx, nu = _phase_dims(desc, phase)
+    x = _sized(x, B, n, "x")
+    times = np.ascontiguousarray(times, dtype=np.float64).ravel()
+    if times.size % B:
+        raise RpmError(RPM_E_INVALID, "times has %d entries, expected a multiple of %d" % (times.size, B))
+    n_times = times.size // B
+    out = np.zeros((B, nx + nu, max(n_times, 1)))
+    flags = np.zeros(B, dtype=np.int32)
+    check(fn(handle, int(phase), _dp(x), n_times, _dp(times), _dp(out), _ip(flags)))
+    return out, flags
+
+
+def _rollout(fn, check, handle, desc, B, n, phase, x, dt, n_steps, hold, state0, t_start, traj):
+    """The host form of the roll-out for an engine or a sweep: arrays checked for size, results as a dict."""
+    nx, _ = _phase_dims(desc, phase)
+    n_steps = int(n_steps)
+    x, dt = _sized(x, B, n, "x"), _sized(dt, B, 1, "dt")
+    s0 = None if state0 is None else _sized(state0, B, nx, "state0")
+    ts = None if t_start is None else _sized(t_start, B, 1, "t_start")
+    out = {"state": np.zeros((B, nx)), "nonfinite": np.zeros(B, dtype=np.int32)}
+    if traj:
+        out["traj"] = np.zeros((B, max(n_steps, 0) + 1, nx))
+    check(fn(handle, int(phase), _dp(x), None if ts is None else _dp(ts), _dp(dt), n_steps, int(hold), None if s0 is None else _dp(s0),
+             _dp(out["state"]), _dp(out["traj"]) if traj else None, _ip(out["nonfinite"])))
     return out
 
 

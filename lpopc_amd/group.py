@@ -7,7 +7,7 @@ import ctypes as C
 import numpy as np
 
 from . import _abi
-from .engine import RPM_E_INVALID, RPM_OK, RpmError, _batch_estimate, _batch_extract, _dp, _extract_layout, _ip, _phase_shapes, _shift_plan, lib
+from .engine import RPM_E_INVALID, RPM_OK, RpmError, _batch_estimate, _batch_extract, _dp, _extract_layout, _ip, _phase_shapes, _rollout, _sample_plan, _shift_plan, lib
 
 
 class _EngineView:
@@ -250,6 +250,16 @@ class SweepGroup:
         all instances bit for bit."""
         return _shift_plan(self._L.rpm_sweep_shift_plan, self._check, self._h, self.n_instances, self.n_phases, self.n, self.m,
                            dt, x, lam, z)
+
+    def sample_plan(self, phase, x, times):
+        """rpm_sweep_sample_plan: as NLPEngine.sample_plan_batch, over all shares; equal to one engine holding all instances bit
+        for bit."""
+        return _sample_plan(self._L.rpm_sweep_sample_plan, self._check, self._h, self._desc, self.n_instances, self.n, phase, x, times)
+
+    def rollout(self, phase, x, dt, n_steps, hold=0, state0=None, t_start=None, traj=False):
+        """rpm_sweep_rollout: as NLPEngine.rollout_batch, over all shares; equal to one engine holding all instances bit for bit."""
+        return _rollout(self._L.rpm_sweep_rollout, self._check, self._h, self._desc, self.n_instances, self.n, phase, x, dt, n_steps,
+                        hold, state0, t_start, traj)
 
     def set_initial_states(self, phase, state0):
         """rpm_sweep_set_initial_states: the measured initial states of `phase`, B x nx, to every share's solver."""

@@ -12,9 +12,12 @@ bounds in to shifted plan out, is printed beside the primal + dual leg's, which 
 download, its np.interp shift and its upload; that leg shifts the states only and leaves lambda and z where they were.  A fifth leg
 is the fourth with everything around the solve replayed from two captured graphs (the bounds before it; multipliers, shift and
 the copy back into fixed buffers after it): the solve itself reads three counters per iteration on the host and cannot be captured.
-python tools/mpc_closed_loop.py [instances] [steps] [trace]
+python tools/mpc_closed_loop.py [instances] [steps] [trace] [plant]
 "trace": where the slowest primal + dual instance of a step needs more iterations than the slowest primal-only one, its accepted
-steps are printed (f, theta, mu, alpha, alpha_z, delta_w, E_0, backtracks)."""
+steps are printed (f, theta, mu, alpha, alpha_z, delta_w, E_0, backtracks).
+"plant": the next measured state comes from the true dynamics instead of the planned trajectory: rollout_batch_dev integrates every
+instance's own dae under the primal-only leg's plan over dt = 0.1 in 4 Runge-Kutta steps (hold 0), the state updated in place on the
+device and handed to the fourth leg's set_initial_states_dev without leaving it; the other legs get its download."""
 import os
 import sys
 import time
@@ -29,7 +32,8 @@ from lpopc_amd.problem import Options
 
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 256
 steps = int(sys.argv[2]) if len(sys.argv) > 2 else 10
-want_trace = len(sys.argv) > 3 and sys.argv[3] == "trace"
+want_trace = "trace" in sys.argv[3:]
+want_plant = "plant" in sys.argv[3:]
 K, NK = 8, 8
 o = Options()
 o.SetStringValue("hessian-approximation", "exact")
@@ -71,6 +75,7 @@ cur4, nxt4, cur5, nxt5 = plan_buffers(), plan_buffers(), plan_buffers(), plan_bu
 d_dt = torch.full((B, 1), dt, dtype=torch.float64, device="cuda")
 d_state4, d_state5 = (torch.zeros((B, 12), dtype=torch.float64, device="cuda") for _ in range(2))
 d_x0_idx = torch.from_numpy(x0_idx).cuda()
+d_plant = torch.from_numpy(state).cuda()              # "plant": the measured states, resident on the device
 graphs = {}
 
 
@@ -109,8 +114,11 @@ def solve_plan(solver, plan, warm):
 
 def device_step(warm):
     """the fourth leg: measured states in, shifted plan out, the next initial state read from it"""
-    d_state4.copy_(torch.from_numpy(state))
-    dev_ipm.set_initial_states_dev(0, d_state4)
+    if want_plant:                                    # the roll-out left them on the device
+        dev_ipm.set_initial_states_dev(0, d_plant)
+    else:
+        d_state4.copy_(torch.from_numpy(state))
+        dev_ipm.set_initial_states_dev(0, d_state4)
     r = solve_plan(dev_ipm, cur4, warm)
     dev_ipm.bound_multipliers_dev(cur4[2], cur4[3])
     eng.shift_plan_batch_dev(d_dt, cur4[0], nxt4[0], cur4[1], nxt4[1], cur4[2], cur4[3], nxt4[2], nxt4[3])
@@ -179,10 +187,15 @@ for step in range(steps):
     r4, step4 = timed(lambda: device_step(step > 0))
     r5, step5 = timed(lambda: graph_step(step > 0))
     X = d_x.cpu().numpy()
-    # "plant": follow the planned state trajectory for dt (the plan is dynamically consistent to the mesh accuracy)
-    for j in range(12):
-        traj = X[:, j * N1:(j + 1) * N1]
-        state[:, j] = np.array([np.interp(dt, t_at, traj[b]) for b in range(B)])
+    if want_plant:
+        # the plant: every instance's own dynamics under the plan's control for dt, from the measured state, in place
+        eng.rollout_batch_dev(0, d_x, d_dt, 4, d_plant, 0, d_plant)
+        state = d_plant.cpu().numpy()
+    else:
+        # "plant": follow the planned state trajectory for dt (the plan is dynamically consistent to the mesh accuracy)
+        for j in range(12):
+            traj = X[:, j * N1:(j + 1) * N1]
+            state[:, j] = np.array([np.interp(dt, t_at, traj[b]) for b in range(B)])
     dist = np.linalg.norm(state[:, :3] - targets, axis=1)
     print("step %2d  %d solves  %s | %s | %s | mean distance to target %.3f" % (
         step, B, leg("cold", rc, ms_c), leg("primal-only", r, ms), leg("primal + dual", r3, ms3), dist.mean()), flush=True)
