@@ -569,11 +569,48 @@ int rpm_ipm_debug_start(rpm_ipm* s, int warm, const double* x, const double* lam
  *                   alpha alpha_min dphi phi theta_max theta_min | status (the device's: 0 running, 1 converged, 6 acceptable level,
  *                   2 .. 5 as rpm_ipm_solve) iter nfilt accepted refactor npos nneg nbad ls armijo nzb pad | mode resto_it
  *                   enter_resto n_resto n_acc skip_update | th0 zeta mu_r th_r thr_max thr_min phi_r | nrfilt soc_on soc_req soc_p
- *                   use_soc n_soc | alpha_soc az_soc th_old_soc | mu_max refs[0..3] | fixed_mode nrefs n_recalc
+ *                   use_soc n_soc | alpha_soc az_soc th_old_soc | mu_max refs[0..3] | fixed_mode nrefs n_recalc | th_trial phi_trial
+ *                   (theta and phi of the last trial point the line search judged: rpm_ipm_debug_line_search)
  * The last solve's bound multipliers stay gone, as after rpm_ipm_debug_start. */
-#define RPM_IPM_RECORD_DOUBLES 64
+#define RPM_IPM_RECORD_DOUBLES 66
 int rpm_ipm_debug_pass(rpm_ipm* s, int stage, double* obj, double* grad, double* g, double* jac, double* c, double* glag, double* hess,
                        double* k_storage, double* rhs, double* dv, double* dlam, double* dzL, double* dzU, double* record);
+/* test hook (host pointers, synchronous): rounds of the filter line search on the direction rpm_ipm_debug_pass(stage 3) has just
+ * left.  Valid only directly after a stage-3 pass that left at least one instance running, or directly after itself (no solve, start
+ * or pass in between; the read-only rpm_ipm_debug_lbfgs_state and rpm_ipm_debug_slot may come between), else RPM_E_INVALID with a
+ * message.  It launches nothing of its own: every round is IpmLoop::line_search_round, the body of the solve loop's line search —
+ * where a second-order correction was asked for, its right-hand side, the substitution with the factors in place and its step
+ * lengths; then every pending instance's trial point, f and g there, and the verdict of ipm_accept_kernel.  Up to `rounds` (>= 1)
+ * rounds run; as in the loop they stop when no instance has a line search pending and none asks for a correction.
+ *   filter, filter_count   n_instances x n_filter pairs (theta, phi) and the number of them that count per instance: they replace
+ *                          every instance's filter before the first round of this call.  filter_count NULL: the filters stay as they
+ *                          are.  n_filter above the filter's capacity (1024) or a count outside 0 .. n_filter: RPM_E_INVALID.
+ * Outputs after the last round, n_instances rows each, any may be NULL, all in the solver's (scaled) problem.  An array holds what
+ * the last round that wrote it left for the instance; an instance that was not pending keeps its earlier values:
+ *   xt (n), objt (1), gt (m)   the trial point v + alpha dv (corrected step: v + alpha_soc dv2) on x, and f, g there
+ *   ct (m)                     c(trial): gt - g_l (nlp_scaling: sc g_l) on a row without slack, gt - (s + alpha ds) on a row with one
+ *   csoc (m)                   c_soc = alpha c + c(trial) after the first correction, alpha_soc c_soc + c(trial) after a later one
+ *   dv2, dzL2, dzU2 (nv), dlam2 (m)   the corrected step, valid once a correction round has run for the instance
+ *   soc_rhs, rhs (Nt, unknown order)   the right-hand side of the correction of this call's last round, written only when that
+ *                              round ran one, copied before the substitution overwrites it; the solution that stands in its place
+ *   record                     as rpm_ipm_debug_pass; th_trial, phi_trial are theta and phi of the trial point just judged
+ *   counts (2 ints)            instances whose line search is still pending, instances that ask for a correction next */
+int rpm_ipm_debug_line_search(rpm_ipm* s, int rounds, int n_filter, const double* filter, const int* filter_count, double* xt,
+                              double* objt, double* gt, double* ct, double* csoc, double* dv2, double* dlam2, double* dzL2, double* dzU2,
+                              double* soc_rhs, double* rhs, double* record, int* counts);
+/* test hook (host pointers, synchronous): IpmLoop::update — the step, the reset (16), the filter entry (22), the trace record, or
+ * the start of the restoration phase resp. of the recalc_y pass, and (limited-memory) grad_x L(x_old, lambda_new) — on what
+ * rpm_ipm_debug_line_search has just left.  Valid only directly after it, else RPM_E_INVALID with a message.  Outputs, n_instances
+ * rows each, any may be NULL, in the solver's (scaled) problem:
+ *   v, zL, zU (nv), lambda (m)     the iterate after the update
+ *   filter (n_filter pairs)        the first n_filter entries of the filter's storage; nfilt of the record says how many count
+ *   vR, dr2 (nv), pp, nn, zp, zn (m)   the restoration phase's reference point, D_R^2, p, n and their multipliers: written when an
+ *                                  instance enters the restoration phase (record: mode 2), stale otherwise
+ *   lb_gold (n)                    limited-memory only: grad_x L(x_old, lambda_new) of the running instances
+ *   record                         as rpm_ipm_debug_pass (nrfilt: the restoration filter's count)
+ * The trace record of the step is read through rpm_ipm_get_trace (option "trace"). */
+int rpm_ipm_debug_update(rpm_ipm* s, double* v, double* zL, double* zU, double* lambda, int n_filter, double* filter, double* vR,
+                         double* dr2, double* pp, double* nn, double* zp, double* zn, double* lb_gold, double* record);
 /* test hooks: KKT position of every unknown ([0,n) variables, slacks, then the m multipliers); factor + solve the
  * caller's matrices given in the band + border storage (host pointers, n_instances of each) */
 int rpm_ipm_get_permutation(rpm_ipm* s, int* pos, int capacity);

@@ -78,14 +78,22 @@ IPM_RECORD_FIELDS = (
     "th0", "zeta", "mu_r", "th_r", "thr_max", "thr_min", "phi_r",
     "nrfilt", "soc_on", "soc_req", "soc_p", "use_soc", "n_soc",
     "alpha_soc", "az_soc", "th_old_soc", "mu_max", "refs0", "refs1", "refs2", "refs3",
-    "fixed_mode", "nrefs", "n_recalc")
-RPM_IPM_RECORD_DOUBLES = len(IPM_RECORD_FIELDS)     # 64
+    "fixed_mode", "nrefs", "n_recalc", "th_trial", "phi_trial")
+RPM_IPM_RECORD_DOUBLES = len(IPM_RECORD_FIELDS)     # 66
 # its outputs after the handle and the stage, in argument order
 IPM_PASS_OUTPUTS = ("obj", "grad", "g", "jac", "c", "glag", "hess", "K", "rhs", "dv", "dlam", "dzL", "dzU", "record")
 
 
+# rpm_ipm_debug_line_search / rpm_ipm_debug_update: their double outputs in argument order (update: the filter comes after lambda)
+IPM_LINE_SEARCH_OUTPUTS = ("xt", "objt", "gt", "ct", "csoc", "dv2", "dlam2", "dzL2", "dzU2", "soc_rhs", "rhs", "record")
+IPM_UPDATE_OUTPUTS = ("v", "zL", "zU", "lambda", "filter", "vR", "dr2", "pp", "nn", "zp", "zn", "lb_gold", "record")
+IPM_FMAX = 1024                                     # filter entries an instance keeps
+
+
 def bind_ipm_debug_pass(L):
     L.rpm_ipm_debug_pass.argtypes = [C.c_void_p, C.c_int] + [c_double_p] * len(IPM_PASS_OUTPUTS)
+    L.rpm_ipm_debug_line_search.argtypes = [C.c_void_p, C.c_int, C.c_int, c_double_p, c_int_p] + [c_double_p] * len(IPM_LINE_SEARCH_OUTPUTS) + [c_int_p]
+    L.rpm_ipm_debug_update.argtypes = [C.c_void_p] + [c_double_p] * 4 + [C.c_int] + [c_double_p] * (len(IPM_UPDATE_OUTPUTS) - 4)
 
 
 def bind_rollout(L):

@@ -18,6 +18,7 @@ int debug_factor_solve(rpm_ipm* h, const double* store, double* rhs, size_t rhs_
   hipStream_t st = static_cast<hipStream_t>(dev_stream(h->eng->e));
   const size_t B = size_t(D.B);
   h->debug_started = false;
+  h->debug_ls = 0;
   inst.assign(B, IpmInst{});
   for (IpmInst& s : inst) s.refactor = 1;
   IPM_TRY(h, hipMemcpyAsync(D.inst, inst.data(), B * sizeof(IpmInst), hipMemcpyHostToDevice, st));
@@ -62,8 +63,8 @@ void pivot_signs(const std::vector<IpmInst>& inst, int* n_pos, int* n_neg) {
     if (n_neg) n_neg[bi] = inst[bi].nneg;
   }
 }
-// the instance record as rpm_ipm_debug_pass hands it out: every field up to n_recalc in declaration order, dbg left out (the order
-// is documented in rpm_hip.h and named in lpopc_amd/_abi.py: IPM_RECORD_FIELDS)
+// the instance record as the hooks hand it out: every field up to n_recalc in declaration order, then the trial point's theta and
+// phi; ic_hot and dbg left out (the order is documented in rpm_hip.h and named in lpopc_amd/_abi.py: IPM_RECORD_FIELDS)
 void flat_record(const IpmInst& S, double* r) {
   const double v[] = {S.mu, S.tau, S.f, S.theta, S.lnsum, S.dinf, S.cinf, S.comp_max, S.comp_min, S.sum_lam, S.sum_z, S.err0,
                       S.delta_w, S.delta_w_last, S.alpha_max, S.alpha_z, S.alpha, S.alpha_min, S.dphi, S.phi, S.theta_max, S.theta_min,
@@ -73,7 +74,7 @@ void flat_record(const IpmInst& S, double* r) {
                       S.th0, S.zeta, S.mu_r, S.th_r, S.thr_max, S.thr_min, S.phi_r,
                       double(S.nrfilt), double(S.soc_on), double(S.soc_req), double(S.soc_p), double(S.use_soc), double(S.n_soc),
                       S.alpha_soc, S.az_soc, S.th_old_soc, S.mu_max, S.refs[0], S.refs[1], S.refs[2], S.refs[3],
-                      double(S.fixed_mode), double(S.nrefs), double(S.n_recalc)};
+                      double(S.fixed_mode), double(S.nrefs), double(S.n_recalc), S.th_trial, S.phi_trial};
   static_assert(sizeof(v) / sizeof(v[0]) == RPM_IPM_RECORD_DOUBLES, "RPM_IPM_RECORD_DOUBLES");
   std::memcpy(r, v, sizeof(v));
 }
@@ -166,6 +167,7 @@ int rpm_ipm_debug_lbfgs_step(rpm_ipm* h, int reset, const double* x, const doubl
   hipStream_t st = static_cast<hipStream_t>(dev_stream(h->eng->e));
   const size_t B = size_t(D.B), row = size_t(p.n) * sizeof(double), pitch = size_t(p.nv) * sizeof(double);
   h->debug_started = false;
+  h->debug_ls = 0;
   IPM_TRY(h, hipMemcpyAsync(D.xt, x, B * row, hipMemcpyHostToDevice, st));
   if (reset) {
     ipm_launch_init(D, D.xt, st);
@@ -268,6 +270,7 @@ int rpm_ipm_debug_start(rpm_ipm* h, int warm, const double* x, const double* lam
     if (status_out) status_out[bi] = inst[bi].status;
   }
   h->debug_started = true;
+  h->debug_ls = 0;
   return RPM_OK;
 }
 
@@ -282,6 +285,7 @@ int rpm_ipm_debug_pass(rpm_ipm* h, int stage, double* obj, double* grad, double*
   if (stage < 1 || stage > 3) { h->err = "rpm_ipm_debug_pass: stage 1, 2 or 3"; return RPM_E_INVALID; }
   if (!h->debug_started) { h->err = "rpm_ipm_debug_pass: valid only directly after rpm_ipm_debug_start on this solver"; return RPM_E_INVALID; }
   h->debug_started = false;
+  h->debug_ls = 0;
   Engine& e = h->eng->e;
   IpmDev& D = h->D;
   const IpmPlan& p = h->plan;
@@ -308,6 +312,7 @@ int rpm_ipm_debug_pass(rpm_ipm* h, int stage, double* obj, double* grad, double*
   h->solve_pending = false;
   if (rc) return rc;
   IPM_TRY(h, hipStreamSynchronize(st));
+  h->debug_ls = stage == 3 && h->h_cnt[0] > 0 ? 1 : 0;   // a direction stands: rpm_ipm_debug_line_search may follow
   const size_t B = size_t(D.B), d8 = sizeof(double);
   auto rows = [&](double* dst, const double* src, size_t width, size_t pitch) -> hipError_t {   // B rows of `width` doubles, `pitch` apart
     if (!dst || !width) return hipSuccess;
@@ -338,6 +343,116 @@ int rpm_ipm_debug_pass(rpm_ipm* h, int stage, double* obj, double* grad, double*
     IPM_TRY(h, hipMemcpy(inst.data(), D.inst, B * sizeof(IpmInst), hipMemcpyDeviceToHost));
     for (size_t bi = 0; bi < B; ++bi) flat_record(inst[bi], record + bi * RPM_IPM_RECORD_DOUBLES);
   }
+  return RPM_OK;
+}
+
+/* test hook: rounds of the line search (IpmLoop::line_search_round, what IpmLoop::line_search repeats) on the direction that
+ * rpm_ipm_debug_pass(stage 3) has just left, or further rounds after itself; it stops early where the loop does.  filter (B x
+ * n_filter pairs theta, phi) with filter_count (B) replaces every instance's filter before the first round. */
+int rpm_ipm_debug_line_search(rpm_ipm* h, int rounds, int n_filter, const double* filter, const int* filter_count, double* xt, double* objt,
+                              double* gt, double* ct, double* csoc, double* dv2, double* dlam2, double* dzL2, double* dzU2, double* soc_rhs,
+                              double* rhs, double* record, int* counts) {
+  if (!h) return RPM_E_INVALID;
+  const char* who = "rpm_ipm_debug_line_search";
+  if (rounds < 1) { h->err = std::string(who) + ": rounds >= 1"; return RPM_E_INVALID; }
+  if (n_filter < 0 || n_filter > IPM_FMAX) { h->err = std::string(who) + ": at most " + std::to_string(IPM_FMAX) + " filter entries"; return RPM_E_INVALID; }
+  if (n_filter > 0 && (!filter || !filter_count)) { h->err = std::string(who) + ": filter entries need filter and filter_count"; return RPM_E_INVALID; }
+  if (h->debug_ls == 0) {
+    h->err = std::string(who) + ": valid only directly after rpm_ipm_debug_pass(stage 3) that left an instance running, or after itself";
+    return RPM_E_INVALID;
+  }
+  Engine& e = h->eng->e;
+  IpmDev& D = h->D;
+  const IpmPlan& p = h->plan;
+  hipStream_t st = static_cast<hipStream_t>(dev_stream(e));
+  const size_t B = size_t(D.B), d8 = sizeof(double);
+  std::vector<IpmInst> inst(B);
+  if (filter_count) {
+    for (size_t bi = 0; bi < B; ++bi)
+      if (filter_count[bi] < 0 || filter_count[bi] > n_filter) { h->err = std::string(who) + ": filter_count outside 0 .. n_filter"; return RPM_E_INVALID; }
+    IPM_TRY(h, hipStreamSynchronize(st));
+    IPM_TRY(h, hipMemcpy(inst.data(), D.inst, B * sizeof(IpmInst), hipMemcpyDeviceToHost));
+    for (size_t bi = 0; bi < B; ++bi) inst[bi].nfilt = filter_count[bi];
+    IPM_TRY(h, hipMemcpy(D.inst, inst.data(), B * sizeof(IpmInst), hipMemcpyHostToDevice));
+    if (n_filter > 0)
+      IPM_TRY(h, hipMemcpy2D(D.filt, 2 * IPM_FMAX * d8, filter, 2 * size_t(n_filter) * d8, 2 * size_t(n_filter) * d8, B, hipMemcpyHostToDevice));
+  }
+  const bool first = h->debug_ls == 1;
+  h->debug_ls = 0;
+  const IpmLoop L{h, e, D, st, D.scal_on != 0};
+  std::vector<double> rk(soc_rhs ? B * size_t(p.Nt_alloc) : 0);
+  bool corrected = false;
+  for (int r = 0; r < rounds; ++r) {
+    if (!(first && r == 0) && L.line_search_over()) break;      // (before the first round ever the counts are not on the host yet)
+    corrected = h->h_cnt[3] > 0;
+    if (int rc = L.line_search_round(soc_rhs ? rk.data() : nullptr)) return rc;
+  }
+  if (soc_rhs && corrected) from_kkt_order(p, B, rk, soc_rhs);
+  h->debug_ls = 2;
+  auto rows = [&](double* dst, const double* src, size_t width, size_t pitch) -> hipError_t {
+    if (!dst || !width) return hipSuccess;
+    return hipMemcpy2D(dst, width * d8, src, pitch * d8, width * d8, B, hipMemcpyDeviceToHost);
+  };
+  const size_t n = size_t(p.n), m = size_t(p.m), nv = size_t(p.nv);
+  IPM_TRY(h, rows(xt, D.xt, n, n));
+  IPM_TRY(h, rows(objt, D.objt, 1, 1));
+  IPM_TRY(h, rows(gt, D.gt, m, size_t(D.sg)));
+  IPM_TRY(h, rows(ct, D.ct, m, m));
+  IPM_TRY(h, rows(csoc, D.csoc, m, m));
+  IPM_TRY(h, rows(dv2, D.dv2, nv, nv));
+  IPM_TRY(h, rows(dlam2, D.dlam2, m, m));
+  IPM_TRY(h, rows(dzL2, D.dzL2, nv, nv));
+  IPM_TRY(h, rows(dzU2, D.dzU2, nv, nv));
+  if (rhs) {
+    std::vector<double> r(B * size_t(p.Nt_alloc));
+    IPM_TRY(h, hipMemcpy(r.data(), D.rhs, r.size() * d8, hipMemcpyDeviceToHost));
+    from_kkt_order(p, B, r, rhs);
+  }
+  if (record) {
+    IPM_TRY(h, hipMemcpy(inst.data(), D.inst, B * sizeof(IpmInst), hipMemcpyDeviceToHost));
+    for (size_t bi = 0; bi < B; ++bi) flat_record(inst[bi], record + bi * RPM_IPM_RECORD_DOUBLES);
+  }
+  if (counts) { counts[0] = h->h_cnt[2]; counts[1] = h->h_cnt[3]; }
+  return RPM_OK;
+}
+
+/* test hook: IpmLoop::update on what rpm_ipm_debug_line_search has just left, and what it wrote.  filter: B x n_filter pairs, the
+ * first min(nfilt, n_filter) of every instance. */
+int rpm_ipm_debug_update(rpm_ipm* h, double* v, double* zL, double* zU, double* lambda, int n_filter, double* filter, double* vR, double* dr2,
+                         double* pp, double* nn, double* zp, double* zn, double* lb_gold, double* record) {
+  if (!h) return RPM_E_INVALID;
+  if (n_filter < 0 || n_filter > IPM_FMAX || (n_filter > 0 && !filter)) { h->err = "rpm_ipm_debug_update: 0 .. " + std::to_string(IPM_FMAX) + " filter entries into filter"; return RPM_E_INVALID; }
+  if (h->debug_ls != 2) { h->err = "rpm_ipm_debug_update: valid only directly after rpm_ipm_debug_line_search on this solver"; return RPM_E_INVALID; }
+  h->debug_ls = 0;
+  Engine& e = h->eng->e;
+  IpmDev& D = h->D;
+  const IpmPlan& p = h->plan;
+  hipStream_t st = static_cast<hipStream_t>(dev_stream(e));
+  const IpmLoop L{h, e, D, st, D.scal_on != 0};
+  if (int rc = L.update()) return rc;
+  IPM_TRY(h, hipStreamSynchronize(st));
+  const size_t B = size_t(D.B), d8 = sizeof(double);
+  auto rows = [&](double* dst, const double* src, size_t width, size_t pitch) -> hipError_t {
+    if (!dst || !width) return hipSuccess;
+    return hipMemcpy2D(dst, width * d8, src, pitch * d8, width * d8, B, hipMemcpyDeviceToHost);
+  };
+  const size_t n = size_t(p.n), m = size_t(p.m), nv = size_t(p.nv);
+  IPM_TRY(h, rows(v, D.v, nv, nv));
+  IPM_TRY(h, rows(zL, D.zL, nv, nv));
+  IPM_TRY(h, rows(zU, D.zU, nv, nv));
+  IPM_TRY(h, rows(lambda, D.lam, m, m));
+  IPM_TRY(h, rows(filter, D.filt, 2 * size_t(n_filter), 2 * size_t(IPM_FMAX)));
+  IPM_TRY(h, rows(vR, D.vR, nv, nv));
+  IPM_TRY(h, rows(dr2, D.dr2, nv, nv));
+  IPM_TRY(h, rows(pp, D.pp, m, m));
+  IPM_TRY(h, rows(nn, D.nn, m, m));
+  IPM_TRY(h, rows(zp, D.zp, m, m));
+  IPM_TRY(h, rows(zn, D.zn, m, m));
+  if (h->lbfgs) IPM_TRY(h, rows(lb_gold, D.lb_gold, n, nv));
+  h->h_inst.resize(B);                     // (rpm_ipm_get_trace reads the iteration counts from here)
+  IPM_TRY(h, hipMemcpy(h->h_inst.data(), D.inst, B * sizeof(IpmInst), hipMemcpyDeviceToHost));
+  if (record)
+    for (size_t bi = 0; bi < B; ++bi) flat_record(h->h_inst[bi], record + bi * RPM_IPM_RECORD_DOUBLES);
   return RPM_OK;
 }
 

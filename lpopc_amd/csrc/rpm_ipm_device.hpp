@@ -60,6 +60,7 @@ struct IpmInst {
   double mu_max, refs[4];            // adaptive barrier update: upper bound of mu, KKT errors of the last accepted iterates
   int fixed_mode, nrefs;             // 0 = free mode (mu from the oracle every iteration), 1 = monotone rule until progress resumes
   int n_recalc, ic_hot;               // least-squares multipliers recomputed after a line search that failed at a feasible point (at most 3 times)
+  double th_trial, phi_trial;         // theta and phi of the last trial point ipm_accept_kernel judged (for rpm_ipm_debug_line_search; no decision reads them)
   long long dbg[8];   // phase clocks of the factorisation (builds with -DIPM_TIMING only)
 };
 

@@ -1,6 +1,6 @@
 // rpm_ipm_solver.hpp — private to rpm_ipm_solver.hip (create, options, the loop, the solve entry points) and rpm_ipm_debug.hip
 // (the test hooks): the solver object behind the rpm_ipm handle, the few helpers both units use and the steps of the solve loop
-// (IpmLoop), which rpm_ipm_debug_pass runs one pass of.
+// (IpmLoop), which the hooks rpm_ipm_debug_pass, rpm_ipm_debug_line_search and rpm_ipm_debug_update run one pass of.
 #pragma once
 #include <algorithm>
 #include <cstdio>
@@ -31,6 +31,8 @@ struct rpm_ipm {
   int lb_iterations = 0;         // iterations of the running solve: an upper bound of the pairs any instance holds
   bool solved = false;           // a solve has finished: D.zL / D.zU hold its bound multipliers (rpm_ipm_get_bound_multipliers)
   bool debug_started = false;    // rpm_ipm_debug_start was the last call to touch the state: rpm_ipm_debug_pass may run on it
+  int debug_ls = 0;              // 1: rpm_ipm_debug_pass(stage 3) left instances running, rpm_ipm_debug_line_search may follow; 2: it has run
+                                 // (it may run again, or rpm_ipm_debug_update); 0: neither
   double* d_host_form = nullptr; // the host-pointer entry points' device copies of x, lambda, z_L, z_U (B x (3 n + m)), on first use
   ~rpm_ipm() {
     if (attached && eng && eng->e.ipm_attached > 0) eng->e.ipm_attached -= 1;
@@ -166,31 +168,42 @@ struct IpmLoop {
     h->h_cnt[3] = 0;
     return RPM_OK;
   }
+  // one round: the corrections that were asked for, the trial points, their evaluation and the verdicts; h_cnt[2] / h_cnt[3] then
+  // hold the line searches still pending and the corrections asked for next.  soc_rhs_copy (the test hook's; B x Nt_alloc on the
+  // host, KKT order): the corrections' right-hand sides before the substitution overwrites them — a copy, no launch.
+  int line_search_round(double* soc_rhs_copy = nullptr) const {
+    int rc;
+    if (h->h_cnt[3] > 0) {
+      ipm_launch_soc_rhs(D, st);
+      if (soc_rhs_copy)
+        IPM_TRY(h, hipMemcpyAsync(soc_rhs_copy, D.rhs, size_t(D.B) * size_t(h->plan.Nt_alloc) * sizeof(double), hipMemcpyDeviceToHost, st));
+      if ((rc = factor_and_solve_launch(h, st, false, true, 2))) return rc;
+      if (h->lbfgs) lb_launch_correct(D, 2, st);
+      ipm_launch_soc_direction(D, st);
+      h->total_soc += 1;
+    }
+    ipm_launch_trial(D, st);
+    if ((rc = dev_eval_obj(e, D.xt, D.objt, nullptr, st))) return eng_fail(rc);
+    if ((rc = dev_eval_cons(e, D.xt, D.gt, nullptr, 1 | 4, st))) return eng_fail(rc);
+    if (scal) ipm_launch_scale(D, D.gt, nullptr, 0, 0, D.objt, nullptr, st);
+    IPM_TRY(h, hipMemsetAsync(D.cnt + 2, 0, 2 * sizeof(int), st));
+    ipm_launch_accept(D, st);
+    h->total_trials += 1;
+    if ((rc = fetch_counts())) return rc;
+    if (h->solve_pending) {
+      float ms = 0.f;
+      if (hipEventElapsedTime(&ms, h->ev[2], h->ev[3]) == hipSuccess) h->solve_ms += ms;
+      h->solve_pending = false;
+    }
+    return RPM_OK;
+  }
+  bool line_search_over() const { return h->h_cnt[2] == 0 && h->h_cnt[3] == 0; }
   int line_search() const {
     int rc;
     if ((rc = direction())) return rc;
     for (int ls = 0; ls <= D.o.max_ls + D.o.max_soc + 2; ++ls) {
-      if (h->h_cnt[3] > 0) {
-        ipm_launch_soc_rhs(D, st);
-        if ((rc = factor_and_solve_launch(h, st, false, true, 2))) return rc;
-        if (h->lbfgs) lb_launch_correct(D, 2, st);
-        ipm_launch_soc_direction(D, st);
-        h->total_soc += 1;
-      }
-      ipm_launch_trial(D, st);
-      if ((rc = dev_eval_obj(e, D.xt, D.objt, nullptr, st))) return eng_fail(rc);
-      if ((rc = dev_eval_cons(e, D.xt, D.gt, nullptr, 1 | 4, st))) return eng_fail(rc);
-      if (scal) ipm_launch_scale(D, D.gt, nullptr, 0, 0, D.objt, nullptr, st);
-      IPM_TRY(h, hipMemsetAsync(D.cnt + 2, 0, 2 * sizeof(int), st));
-      ipm_launch_accept(D, st);
-      h->total_trials += 1;
-      if ((rc = fetch_counts())) return rc;
-      if (h->solve_pending) {
-        float ms = 0.f;
-        if (hipEventElapsedTime(&ms, h->ev[2], h->ev[3]) == hipSuccess) h->solve_ms += ms;
-        h->solve_pending = false;
-      }
-      if (h->h_cnt[2] == 0 && h->h_cnt[3] == 0) break;
+      if ((rc = line_search_round())) return rc;
+      if (line_search_over()) break;
     }
     return RPM_OK;
   }

@@ -674,7 +674,7 @@ __device__ inline bool filter_accepts(const IpmOpts& op, double theta, double th
 __global__ void ipm_trial_kernel(IpmDev D) {
   const int bi = blockIdx.y;
   const IpmInst& S = D.inst[bi];
-  if (S.status != 0 || S.accepted) return;
+  if (S.status != 0 || S.accepted || S.enter_resto) return;   // (enter_resto: its line search gave up in an earlier round)
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= D.n) return;
   const size_t o = size_t(bi) * D.nv + i;
@@ -686,7 +686,9 @@ __global__ __launch_bounds__(1024) void ipm_accept_kernel(IpmDev D) {
   __shared__ double sh[16];
   const int bi = blockIdx.y, t = threadIdx.x, i0 = blockIdx.x * blockDim.x + threadIdx.x, stride = gridDim.x * blockDim.x;
   IpmInst& S = D.inst[bi];
-  const int go = S.status == 0 && !S.accepted, mode = S.mode, soc = S.soc_on;
+  // An instance whose line search gave up (enter_resto set) waits for the update like an accepted one: judged again in the rounds
+  // that other instances of the batch still need, it would go on halving alpha and counting ls.
+  const int go = S.status == 0 && !S.accepted && !S.enter_resto, mode = S.mode, soc = S.soc_on;
   const double a = soc ? S.alpha_soc : S.alpha;
   __syncthreads();
   if (!go) return;
@@ -734,6 +736,7 @@ __global__ __launch_bounds__(1024) void ipm_accept_kernel(IpmDev D) {
   }
   const bool dominated = block_red(dom, 1, sh) != 0.0;
   if (t != 0) return;
+  S.th_trial = th; S.phi_trial = phit_all;
   if (resto) {                  // the restoration problem's own filter line search
     if (!(fabs(phit_all) < 1e300)) bad = 1;
     bool armijo;

@@ -48,6 +48,7 @@ ABI_SYMBOLS = [
     "rpm_sweep_set_option", "rpm_sweep_set_bounds", "rpm_sweep_solve", "rpm_sweep_get_stats",
     "rpm_ipm_get_stats", "rpm_ipm_get_subproblems", "rpm_ipm_get_trace", "rpm_ipm_get_restorations", "rpm_ipm_get_kernel_times", "rpm_ipm_solve", "rpm_ipm_solve_dev", "rpm_ipm_get_permutation", "rpm_ipm_debug_solve", "rpm_ipm_debug_solve_dense", "rpm_ipm_debug_slot",
     "rpm_ipm_debug_lbfgs_step", "rpm_ipm_debug_lbfgs_state", "rpm_ipm_debug_lbfgs_solve", "rpm_ipm_debug_pass",
+    "rpm_ipm_debug_line_search", "rpm_ipm_debug_update",
 ]
 
 
@@ -1092,6 +1093,52 @@ class BatchedIPM:
         self._chk(self._L.rpm_ipm_debug_pass(self._h, int(stage), *[_dp(out[k]) for k in _abi.IPM_PASS_OUTPUTS]))
         out["obj"] = out["obj"][:, 0]
         out["inst"] = {name: out["record"][:, k] for k, name in enumerate(_abi.IPM_RECORD_FIELDS)}
+        return out
+
+    def debug_line_search(self, rounds=1, filt=None):
+        """Rounds of the line search on the direction debug_pass(3) has just left, or further rounds (rpm_ipm_debug_line_search;
+        valid only directly after debug_pass(3) with an instance left running, or after itself).  filt: per instance a sequence of
+        (theta, phi) pairs that replaces its filter before the first round.  -> dict, n_instances rows each: xt, objt, gt, ct,
+        csoc, dv2, dlam2, dzL2, dzU2, soc_rhs (the correction's right-hand side, NaN where the last round ran none), rhs (its
+        solution), record, inst (the record by field name), counts (line searches pending, corrections asked for)."""
+        B, n, m = self._e.n_instances, self._e.n, self._e.m
+        info = self.info()
+        nv, nt = n + info["n_slacks"], info["kkt_order"]
+        width = {"xt": n, "objt": 1, "gt": m, "ct": m, "csoc": m, "dv2": nv, "dlam2": m, "dzL2": nv, "dzU2": nv, "soc_rhs": nt, "rhs": nt,
+                 "record": _abi.RPM_IPM_RECORD_DOUBLES}
+        out = {k: np.full((B, width[k]), np.nan) for k in _abi.IPM_LINE_SEARCH_OUTPUTS}
+        k, pairs, count = 0, None, None
+        if filt is not None:
+            assert len(filt) == B
+            count = np.array([len(f) for f in filt], dtype=np.int32)
+            k = int(count.max()) if B else 0
+            pairs = np.zeros((B, max(k, 1), 2))
+            for b, f in enumerate(filt):
+                if len(f):
+                    pairs[b, :len(f)] = np.asarray(f, dtype=np.float64).reshape(len(f), 2)
+            pairs = np.ascontiguousarray(pairs[:, :k]) if k else None
+        counts = np.zeros(2, dtype=np.int32)
+        self._chk(self._L.rpm_ipm_debug_line_search(self._h, int(rounds), k, None if pairs is None else _dp(pairs),
+                                                    None if count is None else _ip(count),
+                                                    *[_dp(out[key]) for key in _abi.IPM_LINE_SEARCH_OUTPUTS], _ip(counts)))
+        out["objt"] = out["objt"][:, 0]
+        out["inst"] = {name: out["record"][:, i] for i, name in enumerate(_abi.IPM_RECORD_FIELDS)}
+        out["counts"] = (int(counts[0]), int(counts[1]))
+        return out
+
+    def debug_update(self, n_filter=8):
+        """IpmLoop::update on what debug_line_search has just left (rpm_ipm_debug_update; valid only directly after it).  -> dict,
+        n_instances rows each: v, zL, zU, lambda, filter (n_filter pairs, inst["nfilt"] of them count), vR, dr2, pp, nn, zp, zn,
+        lb_gold (limited-memory: grad_x L(x_old, lambda_new)), record, inst."""
+        B, n, m = self._e.n_instances, self._e.n, self._e.m
+        nv = n + self.info()["n_slacks"]
+        width = {"v": nv, "zL": nv, "zU": nv, "lambda": m, "filter": 2 * int(n_filter), "vR": nv, "dr2": nv, "pp": m, "nn": m, "zp": m, "zn": m,
+                 "lb_gold": n, "record": _abi.RPM_IPM_RECORD_DOUBLES}
+        out = {k: np.full((B, width[k]), np.nan) for k in _abi.IPM_UPDATE_OUTPUTS}
+        a = [_dp(out[k]) for k in _abi.IPM_UPDATE_OUTPUTS]
+        self._chk(self._L.rpm_ipm_debug_update(self._h, *a[:4], int(n_filter), *a[4:]))
+        out["filter"] = out["filter"].reshape(B, int(n_filter), 2)
+        out["inst"] = {name: out["record"][:, i] for i, name in enumerate(_abi.IPM_RECORD_FIELDS)}
         return out
 
     def solve_dev(self, d_x, d_lambda=None, stream=None, d_z_L=None, d_z_U=None, warm=False):

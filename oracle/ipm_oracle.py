@@ -210,8 +210,15 @@ class LimitedMemory:
         return Bm
 
 
-def solve(orc, x0, x_l=None, x_u=None, **options):
-    """-> dict(x, lambda, obj, status, iterations, kkt_error, trace); status codes as rpm_ipm_solve (0 converged, 1 acceptable level, ...)."""
+def solve(orc, x0, x_l=None, x_u=None, record_iterations=None, start_state=None, **options):
+    """-> dict(x, lambda, obj, status, iterations, kkt_error, trace); status codes as rpm_ipm_solve (0 converged, 1 acceptable level, ...).
+    Opt-in, for the fixtures of the line-search tests (tests/golden/make_ipm_line_search_states.py); neither changes anything else:
+    record_iterations: iteration numbers; the result gains "recorded", one dict per such regular iteration: the iterate at its start
+      (v, lam, zL, zU), mu after the barrier update, the filter and its bounds, theta, phi, dphi, the step lengths and alpha_min, and
+      what the line search did: events (("trial" | "soc", step length, accepted) per trial point), ls, soc, armijo, accepted, alpha.
+      Every event also carries theta and phi of its trial point.
+    start_state: dict(v, lam, zL, zU, mu[, filt, theta_max, theta_min, delta_w_last]) — the solve starts from this iterate as its iteration 0 instead of
+      from x0, with an empty filter, the filter bounds of that point and no earlier inertia correction unless they are given."""
     o = dict(DEFAULTS)
     o.update(options)
     n, m = orc.n, orc.m
@@ -247,8 +254,15 @@ def solve(orc, x0, x_l=None, x_u=None, **options):
     zL, zU = lo.astype(float), up.astype(float)
     lam = np.zeros(m)
     mu, it, dw_last = o["mu_init"], 0, 0.0
+    if start_state is not None:
+        v, lam = np.array(start_state["v"], float), np.array(start_state["lam"], float)
+        zL, zU = np.where(lo, start_state["zL"], 0.0), np.where(up, start_state["zU"], 0.0)
+        mu, dw_last = float(start_state["mu"]), float(start_state.get("delta_w_last", 0.0))
+    recorded, last_trial = [], {}
     ic_hot = False                # the last regular iteration's factorisation needed delta_w > 0
     filt, trace = [], []
+    if start_state is not None:
+        filt = [tuple(e_) for e_ in start_state.get("filt", [])]
     theta_max = theta_min = None
 
     def cons(vv, g):
@@ -466,6 +480,8 @@ def solve(orc, x0, x_l=None, x_u=None, **options):
             break
         if it == 0:
             theta_max, theta_min = 1e4 * max(1.0, theta), 1e-4 * max(1.0, theta)
+            if start_state is not None and "theta_max" in start_state:
+                theta_max, theta_min = float(start_state["theta_max"]), float(start_state["theta_min"])
         mu_min = o["tol"] / 10.0
         adaptive = o["mu_strategy"] == "adaptive" and nzb > 0
         oracle_mu = None
@@ -514,7 +530,7 @@ def solve(orc, x0, x_l=None, x_u=None, **options):
         dl, du = np.where(lo, v - vl, 1.0), np.where(up, vu - v, 1.0)
         sigma = np.where(lo, zL / dl, 0.0) + np.where(up, zU / du, 0.0)
         rd = glag - np.where(lo, mu / dl, 0.0) + np.where(up, mu / du, 0.0)
-        dw = 0.0
+        dw, dw_last_in = 0.0, dw_last
         if o["ic_hot_start"] and ic_hot and o["kw_dec"] * dw_last >= o["ic_hot_min"]:
             dw = o["kw_dec"] * dw_last
         Ksp = None
@@ -569,6 +585,12 @@ def solve(orc, x0, x_l=None, x_u=None, **options):
         amin *= o["gamma_alpha"]
         a, ls, armijo, accepted, n_soc = amax, 0, False, False, 0
         slack = 10.0 * np.finfo(float).eps * abs(phi)
+        rec = None
+        if record_iterations is not None and it in record_iterations:
+            rec = dict(it=it, v=v.copy(), lam=lam.copy(), zL=zL.copy(), zU=zU.copy(), mu=mu, filt=list(filt), theta_max=theta_max,
+                       theta_min=theta_min, theta=theta, phi=phi, dphi=dphi, alpha_max=amax, alpha_z=az, alpha_min=amin, err0=err0,
+                       delta_w=dw, delta_w_last=dw_last_in, dv=dv.copy(), dlam=dlam.copy(), events=[])
+            recorded.append(rec)
 
         def acceptable(vt, a_test):
             """filter + switching / Armijo / sufficient-decrease tests (18)-(20) at a trial point -> (ok, armijo, theta_trial, c_trial)"""
@@ -577,6 +599,7 @@ def solve(orc, x0, x_l=None, x_u=None, **options):
                 ct = cons(vt, gt)
                 tht = np.abs(ct).sum() if m else 0.0
                 phit = ft - mu * lnsum(vt)
+            last_trial.update(theta=float(tht), phi=float(phit))
             if not (np.isfinite([ft, tht, phit]).all() and tht <= theta_max):
                 return False, False, tht, ct
             if any(tht >= ft_ and phit >= fp_ for ft_, fp_ in filt):
@@ -589,6 +612,8 @@ def solve(orc, x0, x_l=None, x_u=None, **options):
 
         while True:
             ok, armijo, tht, ct = acceptable(v + a * dv, a)
+            if rec is not None:
+                rec["events"].append(("trial", a, bool(ok), last_trial["theta"], last_trial["phi"]))
             if ok:
                 accepted = True
                 break
@@ -599,6 +624,8 @@ def solve(orc, x0, x_l=None, x_u=None, **options):
                     csoc = a_soc * csoc + ct
                     dvs, dlams, dzLs, dzUs, a_soc, azs = newton(csoc)
                     ok, arm_s, ths, ct = acceptable(v + a_soc * dvs, a)
+                    if rec is not None:
+                        rec["events"].append(("soc", a_soc, bool(ok), last_trial["theta"], last_trial["phi"]))
                     if ok:
                         dv, dlam, dzL, dzU, az, a, armijo = dvs, dlams, dzLs, dzUs, azs, a_soc, arm_s
                         accepted, n_soc = True, p_soc + 1
@@ -613,6 +640,10 @@ def solve(orc, x0, x_l=None, x_u=None, **options):
             if a < amin or ls > o["max_ls"]:
                 status = 1 if err0 <= o["acceptable_tol"] else 3
                 break
+        if rec is not None:
+            rec.update(ls=ls, soc=n_soc, armijo=bool(armijo), accepted=accepted, alpha=a, alpha_z_used=az,
+                       gave_up=None if accepted else ("acceptable" if status == 1 else "restoration" if o["resto"] and theta > o["tol"] else
+                                                      "recalc_y" if o["resto"] and n_recalc < o["max_recalc_y"] else "failed"))
         if not accepted and status == 3 and o["resto"] and theta > o["tol"]:
             status = _restore()
             lm.empty()      # the point moved by another problem's steps
@@ -637,5 +668,8 @@ def solve(orc, x0, x_l=None, x_u=None, **options):
         trace.append(dict(it=it, f=f, theta=theta, mu=mu, alpha=a, alpha_z=az, delta_w=dw, err0=err0, ls=ls, soc=n_soc, dinf=dinf, cinf=cinf, comp=cmax,
                           smin=float(min(dl[lo].min(initial=1e300), du[up].min(initial=1e300)))))
         it += 1
-    return dict(x=v[:n].copy(), slack=v[n:].copy(), **{"lambda": lam * sc_u / sf_u}, obj=f / sf_u, status=status, iterations=it, kkt_error=err0, trace=trace, restorations=n_resto,
-                multiplier_recalculations=n_recalc, lm_updates=lm.updates, lm_skips=lm.skips)
+    out = dict(x=v[:n].copy(), slack=v[n:].copy(), **{"lambda": lam * sc_u / sf_u}, obj=f / sf_u, status=status, iterations=it, kkt_error=err0, trace=trace, restorations=n_resto,
+               multiplier_recalculations=n_recalc, lm_updates=lm.updates, lm_skips=lm.skips)
+    if record_iterations is not None:
+        out["recorded"] = recorded
+    return out

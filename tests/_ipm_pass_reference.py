@@ -364,3 +364,217 @@ def relative_residual(K, x, r):
     res = np.abs(K @ x - r)
     ok = den > 0
     return float((res[ok] / den[ok]).max()) if ok.any() else 0.0
+
+
+# ------------------------------------------------------------------------------------------------------------- the line search
+# Section 2.3 / Algorithm A of the paper, steps A-5.1 .. A-5.10 and A-6 .. A-7, for tests/test_ipm_line_search.py (device) and
+# tests/test_ipm_line_search_reference.py (CPU).  Constants the first half of the pass does not need:
+LS_OPTS = dict(eta_phi=1e-8, kappa_soc=0.99, max_soc=4, max_ls=40, kappa_sigma=1e10, resto=1, resto_rho=1000.0, max_recalc_y=3)
+OPTS.update(LS_OPTS)
+
+
+def _margin(a, b):
+    scale = max(abs(a), abs(b))
+    return float(abs(a - b) / scale) if scale > 0 else 1.0
+
+
+def trial_point(v, vl, vu, dv, alpha):
+    """v + alpha dv on the free unknowns (a fixed one stays), with the magnitude of the operands"""
+    free = np.asarray(vl) != np.asarray(vu)
+    step = LD(alpha) * LD(dv)
+    return np.where(free, LD(v) + step, LD(v)), np.abs(np.asarray(v, dtype=np.float64)) + np.where(free, np.abs(step).astype(np.float64), 0.0)
+
+
+def trial_constraints(lay, vt, vt_mag, gt, gl_rows):
+    """c at a trial point vt (nv) from g there: g - g_l on a row without slack, g - s on a row with one"""
+    c = LD(gt) - LD(gl_rows)
+    mag = np.abs(gt) + np.abs(gl_rows)
+    c[lay.srow] = LD(gt[lay.srow]) - LD(vt[lay.n:])
+    mag[lay.srow] = np.abs(gt[lay.srow]) + np.asarray(vt_mag, dtype=np.float64)[lay.n:]
+    return c, mag
+
+
+def theta_1(c):
+    """theta = |c|_1: value, magnitude, number of terms"""
+    t = np.abs(LD(c)).sum() if np.size(c) else LD(0)
+    return t, float(t), int(np.size(c))
+
+
+def barrier_log_sum(vt, vl, vu):
+    """sum of log(slack) over the bounds of the free unknowns at vt: value, magnitude, number of terms"""
+    _, lo, up = bound_kinds(vl, vu)
+    vt, vl, vu = LD(vt), LD(vl), LD(vu)
+    with np.errstate(all="ignore"):
+        logs = np.concatenate([np.log((vt - vl)[lo]), np.log((vu - vt)[up])])
+    return logs.sum(), float(np.abs(logs).sum()), int(logs.size)
+
+
+def barrier_objective(f, mu, lnsum):
+    """phi_mu = f - mu sum log(slack): value, magnitude"""
+    return LD(f) - LD(mu) * LD(lnsum), float(abs(f) + abs(mu * lnsum))
+
+
+def filter_accepts(o, cur, th, phit, a_test, filt, finite=True):
+    """Does the filter line search take the trial point (th, phit)?  cur: theta, theta_min, theta_max, phi, dphi of the current
+    iterate; a_test: the step length of the switching and Armijo tests — of the UNCORRECTED step also for a corrected trial point
+    (A-5.8); filt: the filter's (theta, phi) pairs.  -> (accepted, armijo, dominated, decisions) with decisions a list of
+    (name, outcome, relative margin) in the order they are taken; a composite's margin is that of its deciding part."""
+    dec = []
+    theta, phi, dphi = cur["theta"], cur["phi"], cur["dphi"]
+    slack = 10.0 * EPS * abs(phi)                       # Ipopt's allowance for rounding in the comparisons of phi
+    if not finite:
+        dec.append(("finite", False, 1.0))
+        return False, False, False, dec
+    ok_max = th <= cur["theta_max"]
+    dec.append(("theta <= theta_max", ok_max, _margin(th, cur["theta_max"])))
+    if not ok_max:
+        return False, False, False, dec
+    dominated = False
+    for k, (ft, fp) in enumerate(filt):                 # (th, phit) is in the filter when an entry is no worse in both measures
+        in_t, in_p = th >= ft, phit >= fp
+        mt, mp = _margin(th, ft), _margin(phit, fp)
+        both = in_t and in_p
+        mg = min(mt, mp) if both else max(m_ for m_, inside in ((mt, in_t), (mp, in_p)) if not inside)
+        dec.append(("filter entry %d" % k, both, mg))
+        dominated = dominated or both
+    if dominated:
+        return False, False, True, dec
+    sw = False
+    if dphi < 0:                                        # (19)
+        lhs, rhs = a_test * (-dphi) ** o["s_phi"], o["delta"] * theta ** o["s_theta"]
+        sw = lhs > rhs
+        dec.append(("switching condition (19)", sw, _margin(lhs, rhs)))
+    else:
+        dec.append(("dphi < 0", False, 1.0 if dphi > 0 else 0.0))
+    small = theta <= cur["theta_min"]
+    dec.append(("theta <= theta_min", small, _margin(theta, cur["theta_min"])))
+    if small and sw:                                    # case I: Armijo (20)
+        bound = phi + o["eta_phi"] * a_test * dphi + slack
+        ok = phit <= bound
+        dec.append(("Armijo (20)", ok, _margin(phit, bound)))
+        return ok, ok, False, dec
+    b18 = (1.0 - o["gamma_theta"]) * theta              # case II: sufficient decrease (18)
+    ok_t, m_t = th <= b18, _margin(th, b18)
+    bphi = phi - o["gamma_phi"] * theta + slack
+    ok_p, m_p = phit <= bphi, _margin(phit, bphi)
+    ok = ok_t or ok_p
+    mg = max(m_ for m_, y in ((m_t, ok_t), (m_p, ok_p)) if y) if ok else min(m_t, m_p)
+    dec.append(("sufficient decrease (18)", ok, mg))
+    return ok, False, False, dec
+
+
+LS_STATE = ("alpha", "ls", "accepted", "armijo", "soc_on", "soc_req", "soc_p", "th_old_soc", "use_soc", "n_soc", "enter_resto", "status")
+
+
+def line_search_verdict(o, S, ok, armijo, th, finite=True):
+    """What follows the test of one trial point (A-5.4 .. A-5.10), as a new copy of the state S: alpha (the uncorrected step
+    length), ls, accepted, armijo, soc_on (corrected trial points are being tried), soc_req (the next round computes a correction),
+    soc_p (corrections computed before the pending one), th_old_soc, use_soc, n_soc, enter_resto, status; S also holds theta, alpha_min,
+    err0, n_recalc.  -> (state, decisions).  Giving up (alpha < alpha_min, or more than max_ls halvings): status 6 when E_0 is at the
+    acceptable level; else the restoration phase (enter_resto 1) from an infeasible point; else, up to max_recalc_y times,
+    least-squares multipliers at this point (enter_resto 2); else status 3.
+    One step is Ipopt 3.12's and not the paper's: a corrected trial point that the filter rejects counts like any other rejected one
+    (the paper's A-5.7 ends the corrections there)."""
+    S, dec = dict(S), []
+    if armijo:
+        S["armijo"] = 1
+    if ok:
+        S["accepted"] = 1
+        if S["soc_on"]:
+            S["use_soc"], S["n_soc"] = 1, S["n_soc"] + 1
+        return S, dec
+    halve = True
+    if S["soc_on"]:                                     # A-5.9
+        more = finite and S["soc_p"] + 1 < o["max_soc"]
+        if more:
+            bound = o["kappa_soc"] * S["th_old_soc"]
+            more = th <= bound
+            dec.append(("theta_soc <= kappa_soc theta_old", more, _margin(th, bound)))
+        if more:
+            S["soc_p"], S["th_old_soc"], S["soc_req"] = S["soc_p"] + 1, th, 1
+            halve = False
+        else:
+            S["soc_on"] = 0
+    elif S["ls"] == 0 and o["max_soc"] > 0 and finite:  # A-5.5
+        opens = th >= S["theta"]
+        dec.append(("theta_trial >= theta (A-5.5)", opens, _margin(th, S["theta"])))
+        if opens:
+            S["soc_on"], S["soc_p"], S["th_old_soc"], S["soc_req"] = 1, 0, S["theta"], 1
+            halve = False
+    if not halve:
+        return S, dec
+    S["alpha"], S["ls"] = 0.5 * S["alpha"], S["ls"] + 1  # A-5.10
+    small = S["alpha"] < S["alpha_min"]
+    dec.append(("alpha < alpha_min", small, _margin(S["alpha"], S["alpha_min"])))
+    if small or S["ls"] > o["max_ls"]:
+        acc = S["err0"] <= o["acceptable_tol"]
+        dec.append(("E_0 <= acceptable_tol", acc, _margin(S["err0"], o["acceptable_tol"])))
+        if acc:
+            S["status"] = 6
+        else:
+            infeasible = S["theta"] > o["tol"]
+            dec.append(("theta > tol", infeasible, _margin(S["theta"], o["tol"])))
+            if o["resto"] and infeasible:
+                S["enter_resto"] = 1
+            elif o["resto"] and S["n_recalc"] < o["max_recalc_y"]:
+                S["enter_resto"] = 2
+            else:
+                S["status"] = 3
+    return S, dec
+
+
+def correction_constraints(c_prev, ct, mix):
+    """c_soc = mix c_prev + c(trial): A-5.5 with mix = alpha and c_prev = c, A-5.9 with mix = alpha_soc and c_prev = c_soc"""
+    t = LD(mix) * LD(c_prev)
+    return t + LD(ct), np.abs(t).astype(np.float64) + np.abs(np.asarray(ct, dtype=np.float64))
+
+
+# ------------------------------------------------------------------------------------------------------------- the step, (16), (22)
+def reset_16(o, z, s, mu):
+    """(16): z <- max(min(z, kappa_sigma mu / s), mu / (kappa_sigma s))"""
+    ks = LD(o["kappa_sigma"])
+    return np.maximum(np.minimum(z, ks * mu / s), mu / (ks * s))
+
+
+def apply_step(o, vl, vu, v_new, zL, zU, lam, dlam, dzL, dzU, a, az, mu):
+    """The duals after a step: lambda + a dlambda and z + az dz, then (16) with the slacks of the new point v_new (as given).
+    -> dict lam, zL, zU with *_mag"""
+    free, lo, up = bound_kinds(vl, vu)
+    a, az, mu, v_new = LD(a), LD(az), LD(mu), LD(v_new)
+    out = {"lam": LD(lam) + a * LD(dlam), "lam_mag": np.abs(lam) + np.abs(np.asarray(a * LD(dlam), dtype=np.float64))}
+    for key, z, dz, here, s in (("zL", zL, dzL, lo, v_new - LD(vl)), ("zU", zU, dzU, up, LD(vu) - v_new)):
+        s = np.where(here, s, LD(1))
+        t = az * LD(dz)
+        r = reset_16(o, LD(z) + t, s, mu)
+        out[key] = np.where(here, r, LD(z))
+        out[key + "_mag"] = np.where(here, np.maximum(np.abs(z) + np.abs(t).astype(np.float64), np.abs(r).astype(np.float64)), 0.0)
+    return out
+
+
+def filter_entry_22(o, theta, phi):
+    """(22): the pair added to the filter, with magnitudes"""
+    theta, phi = LD(theta), LD(phi)
+    t = LD(o["gamma_phi"]) * theta
+    return ((LD(1) - LD(o["gamma_theta"])) * theta, phi - t), (float(abs(theta)), float(abs(phi) + abs(t)))
+
+
+# ------------------------------------------------------------------------------------------------------------- (33), (34)
+def restoration_start(o, c, mu, cinf, v):
+    """The start of the restoration phase (section 3.3) at the point v with constraint values c: mu_R = max(mu, |c|_inf), zeta =
+    sqrt(mu_R), D_R^2 = 1 / max(1, |v|)^2, and the p, n that minimise rho sum(p + n) - mu_R sum(log p + log n) subject to
+    p - n = c: (33), (34), with their multipliers z = mu_R / p, mu_R / n.  n is evaluated without cancellation:
+    h + sqrt(h^2 + q) = q / (sqrt(h^2 + q) - h) for h < 0."""
+    rho, c = LD(o["resto_rho"]), LD(c)
+    mu_r = max(LD(mu), LD(cinf))
+    h = (mu_r - rho * c) / (2 * rho)
+    q = mu_r * c / (2 * rho)
+    root = np.sqrt(h * h + q)
+    with np.errstate(all="ignore"):
+        nn = np.where(h < 0, q / np.where(h < 0, root - h, LD(1)), h + root)
+    pp = c + nn
+    out = dict(mu_r=mu_r, zeta=np.sqrt(mu_r), nn=nn, pp=pp, zp=mu_r / pp, zn=mu_r / nn)
+    out["nn_mag"] = np.abs(h).astype(np.float64) + root.astype(np.float64)
+    out["pp_mag"] = np.abs(c).astype(np.float64) + out["nn_mag"]
+    sc = np.maximum(LD(1), np.abs(LD(v)))
+    out["dr2"] = 1 / (sc * sc)
+    return out
