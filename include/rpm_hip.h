@@ -657,6 +657,9 @@ int rpm_eval_h_dev(rpm_engine* e, const double* d_x, double obj_factor, const do
  * then N of tftf, then N of tft0.  out (HOST): [(instance * n_phases + p) * 3 + i], i = 0 t0t0, 1 tft0, 2 tftf, read back
  * from where rpm_eval_h stores them. */
 int rpm_debug_hess_tt(rpm_engine* e, const double* tmp, int tmp_len, double* out);
+/* Test hook of the pipelined kernel's tile orders (host arithmetic only): the slot in [0, nh * nb) of a round of tiles that
+ * half `half` of workgroup b takes in a launch of nb workgroups of nh halves under "tile_order" = order; -1: bad argument. */
+int rpm_debug_tile_slot(int order, int nh, int nb, int b, int half);
 /* block until everything queued on the engine's stream has finished */
 int rpm_synchronize(rpm_engine* e);
 
@@ -679,6 +682,12 @@ int rpm_synchronize(rpm_engine* e);
  *                    node and per perturbation role only in what the perturbed variable enters — the same operations, the
  *                    same bits; -1: where the launch skips the constant block ("persistent_values"), which is bound by the
  *                    dynamics; with all stores the extra registers cost more than the arithmetic saves
+ * "tile_order"       0 (default) | 1: in the pipelined kernel, which tiles of a round the workgroups of one XCD take: 0 a contiguous
+ *                    eighth (one instance of the 4 x 64 x 16 launch problem), 1 a quarter of each of four eighths (one phase of
+ *                    four instances); grids that are no multiple of 8 workgroups take 0.  Same bits; speed only
+ * "store_policy"     0 .. 3 = jacobian + 2 * constant, default 1: in the pipelined kernel the Jacobian stores are plain (0) or
+ *                    non-temporal (1), the stores of the constant block non-temporal (0) or write-through and non-temporal (1).
+ *                    Same bits; speed only
  * "instance_align"   1 (default) or any power of two up to 65536 doubles: in the device-resident calls with n_instances > 1 the g /
  *                    values arrays of consecutive instances are rpm_get_option "stride_g" / "stride_values" doubles
  *                    apart (m, nnz_jac rounded up to this multiple) instead of packed back to back, so that every

@@ -674,6 +674,10 @@ int rpm_eval_h_dev(rpm_engine* h, const double* d_x, double obj_factor, const do
   return rpm::dev_eval_h(h->e, d_x, obj_factor, d_lambda, d_values, stream);
   RPM_GUARD_END(h->e)
 }
+int rpm_debug_tile_slot(int order, int nh, int nb, int b, int half) {
+  if (order < 0 || order >= rpm::PL_TILE_ORDERS || nh < 1 || nb < 1 || b < 0 || b >= nb || half < 0 || half >= nh) return -1;
+  return rpm::dev_pl_tile_slot(order, nh, nb, b, half);
+}
 int rpm_debug_hess_tt(rpm_engine* h, const double* tmp, int tmp_len, double* out) {
   if (!h) return RPM_E_INVALID;
   RPM_GUARD_BEGIN
@@ -792,6 +796,12 @@ int rpm_set_option(rpm_engine* h, const char* key, int value) {
   } else if (k == "pipeline") {
     if (value < -1 || value > 1) return fail(e, RPM_E_INVALID, "pipeline must be -1 (auto), 0 or 1");
     e.opt_pipeline = value;
+  } else if (k == "tile_order") {
+    if (value < 0 || value >= rpm::PL_TILE_ORDERS) return fail(e, RPM_E_INVALID, "tile_order must be 0 (each XCD a contiguous eighth of a round) or 1 (a quarter of four eighths)");
+    e.opt_tile_order = value;
+  } else if (k == "store_policy") {
+    if (value < 0 || value >= rpm::PL_STORE_POLICIES) return fail(e, RPM_E_INVALID, "store_policy must be jacobian + 2 * constant, each 0 or 1");
+    e.opt_store_policy = value;
   } else if (k == "stage_roles") {
     if (value < -1 || value > 1) return fail(e, RPM_E_INVALID, "stage_roles must be -1 (auto), 0 or 1");
     e.opt_stage_roles = value;
@@ -823,6 +833,8 @@ int rpm_get_option(rpm_engine* h, const char* key, int* value) {
   else if (k == "n_tiles") *value = int(e.tiles.size());
   else if (k == "role_loop") *value = e.role_looped ? 1 : 0;
   else if (k == "pipeline") *value = e.opt_pipeline;
+  else if (k == "tile_order") *value = e.opt_tile_order;
+  else if (k == "store_policy") *value = e.opt_store_policy;
   else if (k == "mesh_err_tile") *value = e.opt_mesh_err_tile;
   else if (k == "carry_tile") *value = e.opt_carry_tile;
   else if (k == "carry_lds_bytes") *value = e.opt_carry_lds;

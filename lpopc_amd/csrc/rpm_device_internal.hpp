@@ -241,6 +241,40 @@ void carry_destroy(Device* d);       // rpm_carry_kernels.hip
 void extract_destroy(Device* d);     // rpm_extract_kernels.hip
 void rollout_destroy(Device* d);     // rpm_rollout_kernels.hip
 
+// XCD-aware order: workgroups b, b+8, b+16, ... are dealt to the same XCD, so workgroup b of `count` takes place
+// xcd_place(b, count) in the tile order and each XCD gets a contiguous run of tiles; neighbouring 128-byte pieces of every
+// Jacobian block then meet in one L2 and leave it as longer contiguous write-backs (speed only, correctness does not depend
+// on placement)
+__host__ __device__ inline int xcd_place(int b, int count) {
+  const int per = count >> 3, rem = count & 7, xcd = b & 7;
+  return xcd * per + (xcd < rem ? xcd : rem) + (b >> 3);
+}
+
+// Tile orders of rpm_tile_pl_kernel (engine option "tile_order").  A launch of nb workgroups x nh halves works in rounds of
+// G = nh nb tiles; half `half` of workgroup b takes slot pl_tile_slot(...) of [0, G) in every round, i.e. tiles slot, slot + G,
+// ...: a bijection of the halves onto [0, G) for every order, so each tile is visited exactly once, a half's next tile is
+// G further (the staged record of the tile after the current one), and half 0's slot is below half 1's, so that half 0 walks
+// at least as many tiles (its count is the workgroup's barrier count).
+//   0  each XCD a contiguous eighth of the round (xcd_place): one instance per XCD and round on the metric problem
+//   1  the round in two groups of four eighths; XCD 4 q + c takes quarter c of every eighth of group q: one phase of four
+//      instances per XCD and round on the metric problem.  Needs nb % 8 == 0 and G % 32 == 0; other grids take order 0.
+// (tools/ubench/store_sustained.py ranks these and three more by what the write path takes for the kernel's store streams;
+// only what it ranked above order 0 is built here.)
+__host__ __device__ inline int pl_tile_slot(int order, int nh, int nb, int b, int half) {
+  if (order == 1 && (nb & 7) == 0 && ((nh * (nb >> 3)) & 3) == 0) {
+    const int S = nh * (nb >> 3), l = nh * (b >> 3) + half, xcd = b & 7;   // slots per XCD, this half's among them
+    const int Q = S >> 2, r = l / Q, t = l - r * Q;
+    return (xcd >> 2) * 4 * S + r * S + (xcd & 3) * Q + t;
+  }
+  return nh * xcd_place(b, nb) + half;
+}
+
+// Store policies of rpm_tile_pl_kernel (engine option "store_policy" = jacobian + 2 * constant): the Jacobian stream plain (0)
+// or non-temporal (1), the constant-block stream non-temporal (0) or write-through + non-temporal (1).  0 is what the kernel
+// did before the option existed, 1 the default (fastest in the kernel); the probe ranked write-through
+// Jacobian stores and a plain constant stream at or below 0, they are not built.
+// (PL_TILE_ORDERS, PL_STORE_POLICIES: rpm_engine.hpp)
+
 // rpm_tile_kernels.hip: occupancy, LDS size and eligibility of the pipelined kernel for this engine (device_init)
 void tile_pipeline_setup(Engine& e, Device* d, const ProblemDims& pd, int device_id);
 

@@ -169,6 +169,8 @@ struct Engine {
   long long stride_values() const { return (long long)(nnz_jac + opt_instance_align - 1) / opt_instance_align * opt_instance_align; }
   int opt_stage_roles = -1;      // pipelined kernel: functors with a staged dae (problems.hpp has_stage) recompute per role only what the perturbed variable enters; -1: when the constant block is skipped
   int opt_pipeline = -1;         // rpm_tile_pl_kernel: -1 automatic (>= 2 tiles per resident workgroup), 0 never, 1 whenever the mesh fits
+  int opt_tile_order = 0;        // rpm_tile_pl_kernel: which slot of a round of tiles a half takes (pl_tile_slot, rpm_device_internal.hpp)
+  int opt_store_policy = 1;      // rpm_tile_pl_kernel: jacobian + 2 * constant; Jacobian stores 0 plain / 1 non-temporal (default: measured), constant block 0 non-temporal / 1 write-through + non-temporal
   int jac_nonfinite = -1;                 // verdict on the cached Jacobian of the fused pair launch (-1: not checked)
   const double* const_filled = nullptr;   // host `values` buffer whose LIN/CONST tail this engine wrote last (const_once)
   int opt_persistent_values = 0; // device-resident Jacobian calls: skip the constant block of a `values` array this engine filled before (rpm_hip.h)
@@ -345,6 +347,8 @@ struct ConsCall { bool want_g, want_v, cached, delta, launched_jac; };
 int host_cons_begin(Engine& e, const double* x, int new_x, double* g, double* values, ConsCall* c);
 int host_cons_end(Engine& e, double* g, double* values, const ConsCall& c, const char* who);
 int host_delta_sent_runs(Engine& e, int* sent);   // runs delivered since the previous query
+constexpr int PL_TILE_ORDERS = 2, PL_STORE_POLICIES = 4;   // values of the options "tile_order" and "store_policy" (rpm_device_internal.hpp)
+int dev_pl_tile_slot(int order, int nh, int nb, int b, int half);   // pl_tile_slot on the host (rpm_debug_tile_slot)
 int dev_pipeline_active(const Engine& e);   // 1 when the next constraint launch uses rpm_tile_pl_kernel
 int dev_upload_x(Engine& e, const double* x);
 int dev_upload(Engine& e, double* dev, const double* host, size_t count, int slot);    // slot: STAGE_* (rpm_device_internal.hpp)

@@ -263,14 +263,7 @@ __device__ __forceinline__ void store_defect(int sv, double dx, double tspan, co
   if (CHK) chk_note(bad_g, dfc);
 }
 
-// XCD-aware order: workgroups b, b+8, b+16, ... are dealt to the same XCD, so workgroup b of `count` takes place
-// xcd_place(b, count) in the tile order and each XCD gets a contiguous run of tiles; neighbouring 128-byte pieces of every
-// Jacobian block then meet in one L2 and leave it as longer contiguous write-backs (speed only, correctness does not depend
-// on placement)
-__device__ __forceinline__ int xcd_place(int b, int count) {
-  const int per = count >> 3, rem = count & 7, xcd = b & 7;
-  return xcd * per + (xcd < rem ? xcd : rem) + (b >> 3);
-}
+// (xcd_place, the XCD-aware order of the workgroups of all three kernels: rpm_device_internal.hpp)
 
 // a wave-uniform field of a tile record staged as ints (in LDS or in the constant address space)
 #define RPM_REC(rec, f) __builtin_amdgcn_readfirstlane((rec)[offsetof(TileDev, f) / 4])
@@ -737,6 +730,28 @@ __device__ __forceinline__ void pl_dma_run(const double* gsrc, double* ldst, int
 }
 
 
+// The two bulk output streams of the pipelined kernel go through pl_store<POLICY>: plain, non-temporal, or write-through +
+// non-temporal (global_store_dwordx4 ... sc1 nt: the line is not kept in the XCD's L2).  Nobody in the launch reads these
+// addresses, so the policy changes when the bytes leave L2 and nothing else.  Vector stores only.  The write-through form is
+// inline asm, which hipcc neither counts in its s_waitcnt bookkeeping (the DMA waves wait vmcnt(0) in front of every
+// barrier A themselves, and nothing reads the data) nor pads: s_nop 1 keeps the next instruction off the data registers
+// until the store has read them.
+constexpr int PL_ST_PLAIN = 0, PL_ST_NT = 1, PL_ST_WT_NT = 2;
+constexpr int pl_jac_policy(int jp) { return jp == 0 ? PL_ST_PLAIN : PL_ST_NT; }
+constexpr int pl_const_policy(int cp) { return cp == 0 ? PL_ST_NT : PL_ST_WT_NT; }
+template <int POLICY>
+__device__ __forceinline__ void pl_store(double* p, double v) {
+  static_assert(POLICY == PL_ST_PLAIN || POLICY == PL_ST_NT, "8-byte stores: plain or non-temporal");
+  if constexpr (POLICY == PL_ST_PLAIN) *p = v;
+  else __builtin_nontemporal_store(v, p);
+}
+template <int POLICY>
+__device__ __forceinline__ void pl_store(d2u* p, d2u v) {
+  static_assert(POLICY == PL_ST_NT || POLICY == PL_ST_WT_NT, "16-byte stores: non-temporal or write-through + non-temporal");
+  if constexpr (POLICY == PL_ST_NT) __builtin_nontemporal_store(v, p);
+  else asm volatile("global_store_dwordx4 %0, %1, off sc1 nt\n\ts_nop 1" ::"v"(p), "v"(v) : "memory");
+}
+
 // A tile's share of the constant Doffdiag block (LpNLPWrapper.cpp:715-718) out of the staged buffer (record at `cur`, the
 // share at cv_src): NX copies, c_stride apart, into the instance's values array; the share is dealt in 128-double
 // chunks to NPART waves (this one is `part`).
@@ -744,7 +759,7 @@ __device__ __forceinline__ void pl_dma_run(const double* gsrc, double* ldst, int
 // of 5.4 TB/s, by 64 B 5.1 (tools/ubench/store_pattern.py).  `head` elements bring the first copy to a line boundary (the
 // others follow when c_stride is a multiple of 16, e.g. on uniform meshes); they and an odd last element go out as
 // single stores.  Non-temporal: this bulk stream (55 % of the metric problem's bytes) is never read again.
-template <int NX, int NPART>
+template <int NX, int NPART, int POLICY>
 __device__ __forceinline__ void pl_const_stores(const double* cur, const double* cv_src, int inst_word, double* __restrict__ vall,
                                                 long long sv, int lane, int part) {
   constexpr int CCH = (PL_CMAX / 128 + NPART - 1) / NPART;   // 128-double chunks per wave
@@ -770,7 +785,7 @@ __device__ __forceinline__ void pl_const_stores(const double* cur, const double*
     const int q = head + (NPART * ch + part) * 128 + 2 * lane;   // 16 B per lane: 1 KB per store instruction
     if (q + 1 < c_cnt) {
 #pragma unroll
-      for (int i = 0; i < NX; ++i) __builtin_nontemporal_store(cv[ch], reinterpret_cast<d2u*>(cdst + size_t(i) * c_stride + q));
+      for (int i = 0; i < NX; ++i) pl_store<POLICY>(reinterpret_cast<d2u*>(cdst + size_t(i) * c_stride + q), cv[ch]);
     }
   }
   if (part == 0 && edge >= 0) {
@@ -799,9 +814,10 @@ constexpr PlShape pl_shape(int R) { return R <= 12 ? PlShape{2, 4, 2} : PlShape{
 // (Tried for the one-half shape, R > 12 roles: __launch_bounds__(..., 6) so that two 11-wave workgroups share a CU and one's
 // store phases overlap the other's dynamics.  The quadrotor kernel needs ~156 VGPRs; at 80 it spills 76 of them and the
 // 1024-instance sweep takes 89.9 us instead of 51 — DESIGN.md §4.)
-template <class Prob, int NH, int RG, int NDMA, bool WG, bool WJ, bool AN, bool DXM = false, bool STG = false>
+// JP, CP: the store policy of the Jacobian and of the constant-block stream (pl_jac_policy, pl_const_policy)
+template <class Prob, int NH, int RG, int NDMA, bool WG, bool WJ, bool AN, bool DXM = false, bool STG = false, int JP = 0, int CP = 0>
 __global__ __launch_bounds__(NH * 64 * (RG + NDMA), 1) void rpm_tile_pl_kernel(
-    const KParams K, int n_inst, const double* __restrict__ xall, double* __restrict__ gall,
+    const KParams K, int n_inst, int tile_order, const double* __restrict__ xall, double* __restrict__ gall,
     double* __restrict__ vall) {
   constexpr int T = 64;   // a role of a tile is one wave
   constexpr int HT = 64 * (RG + NDMA);   // threads of one half
@@ -819,12 +835,14 @@ __global__ __launch_bounds__(NH * 64 * (RG + NDMA), 1) void rpm_tile_pl_kernel(
   // XCD-aware order (xcd_place), here of halves: the tiles a round of the launch works on (w + j G over all w) leave each
   // XCD's L2 as contiguous pieces of every Jacobian block instead of 2-tile pieces interleaved with the other seven XCDs',
   // and the halves end their last tiles together (102.3 against 108.9 us per 64-iterate step)
-  const int nb = int(gridDim.x), wg = xcd_place(int(blockIdx.x), nb);   // this workgroup's place in the tile order
-  const int G = NH * nb, w = NH * wg + half;
+  // (engine option "tile_order": which slot of a round a half takes, pl_tile_slot; 0 is the order described here)
+  const int nb = int(gridDim.x);
+  const int G = NH * nb, w = pl_tile_slot(tile_order, NH, nb, int(blockIdx.x), half);   // this half's place in the tile order
+  const int w_h0 = NH > 1 ? pl_tile_slot(tile_order, NH, nb, int(blockIdx.x), 0) : w;
   const int nt = K.n_my_tiles;
   const int W = nt * n_inst;
   const int n_iter = w < W ? (W - w + G - 1) / G : 0;                 // tiles w, w + G, ... of this half
-  const int n_iter_wg = (W - NH * wg + G - 1) / G;                    // of half 0: the barrier count of the workgroup
+  const int n_iter_wg = (W - w_h0 + G - 1) / G;                       // of half 0: the barrier count of the workgroup
   const PlLds L(NX, NU, NC, NQ, K.max_span, K.max_drow, K.max_cshare, WJ, DXM);
   // (const locals for what the lambdas and the tile loops use: read as L.x there, 22 instantiations allocate registers differently)
   const int S_TT = L.tt, S_X = L.X, S_U = L.U, S_D = L.D, S_TAU = L.tau, S_DG = L.diag, S_ND = L.nodes, S_CV = L.cv, S_SIZE = L.stage;
@@ -970,7 +988,7 @@ __global__ __launch_bounds__(NH * 64 * (RG + NDMA), 1) void rpm_tile_pl_kernel(
       // in their first pass and store nothing; then the next tile's loads.  (The order matters twice: an LDS read of
       // this wave after the direct-to-LDS loads would wait for them, and the Jacobian stores of the later passes
       // should not meet these in the memory system.)
-      if (WJ && !K.skip_const && j < n_iter) pl_const_stores<NX, NDMA>(cur + L.rec, cur + S_CV, NREC, vall, K.sv, lane, dw);
+      if (WJ && !K.skip_const && j < n_iter) pl_const_stores<NX, NDMA, pl_const_policy(CP)>(cur + L.rec, cur + S_CV, NREC, vall, K.sv, lane, dw);
       RPM_PTRC(j, 17);
       if (j + 1 < n_iter) {
         stage(std::integral_constant<int, NDMA>{}, dw, lane, w + (j + 1) * G, nxt, runs_of(reinterpret_cast<const int*>(cur + L.next)));
@@ -1135,7 +1153,7 @@ __global__ __launch_bounds__(NH * 64 * (RG + NDMA), 1) void rpm_tile_pl_kernel(
               } else {
                 val = J[o];
               }
-              (vb + size_t(o * NB + bv) * N)[k] = val;
+              pl_store<pl_jac_policy(JP)>(vb + size_t(o * NB + bv) * N + k, val);
             }
           } else {                       // d/dt0 and d/dtf blocks (:748-760, :801-811); B-5 sign kept
             const double a0 = -(tau * 0.5) + 0.5, af = (tau * 0.5) + 0.5;
@@ -1151,8 +1169,8 @@ __global__ __launch_bounds__(NH * 64 * (RG + NDMA), 1) void rpm_tile_pl_kernel(
                 v0 = a0 * J[o];
                 vf = af * J[o];
               }
-              (vb + size_t(o * NB + NX + NU) * N)[k] = v0;
-              (vb + size_t(o * NB + NX + NU + 1) * N)[k] = vf;
+              pl_store<pl_jac_policy(JP)>(vb + size_t(o * NB + NX + NU) * N + k, v0);
+              pl_store<pl_jac_policy(JP)>(vb + size_t(o * NB + NX + NU + 1) * N + k, vf);
             }
           }
         }
@@ -1228,26 +1246,38 @@ static bool pl_dxm_ok(const Engine& e) {
   return e.first_derive != RPM_DERIVE_ANALYTIC && pl_lds_bytes(pd.nx, pd.nu, pd.nc, pd.nq, e.dev->kp, true) <= 160 * 1024;
 }
 
-template <class Prob, bool WG, bool WJ, bool AN, bool DXM, bool STG = false>
+template <class Prob, bool WG, bool WJ, bool AN, bool DXM, bool STG = false, int JP = 0, int CP = 0>
 static hipError_t launch_tile_pl(const Engine& e, const KParams& kp, const double* dx, double* dg, double* dv, hipStream_t st) {
+  if constexpr (WJ && JP == 0 && CP == 0) {
+    // engine option "store_policy" (jacobian + 2 * constant, rpm_device_internal.hpp); launches without a Jacobian have neither stream.
+    // Measured in the kernel, 64 iterates of the metric problem per launch, one box: 0 94.3, 1 86.4, 2 99.5, 3 90.3 us (the
+    // write-through constant stream wins in the store-only probe and loses here); 1 also wins with the constant block skipped
+    // (67.2 -> 65.2), on 1024 quadrotor instances (42.3 -> 38.1) and at 16 iterates per launch (29.0 -> 26.8)
+    switch (e.opt_store_policy) {
+      case 1: return launch_tile_pl<Prob, WG, WJ, AN, DXM, STG, 1, 0>(e, kp, dx, dg, dv, st);
+      case 2: return launch_tile_pl<Prob, WG, WJ, AN, DXM, STG, 0, 1>(e, kp, dx, dg, dv, st);
+      case 3: return launch_tile_pl<Prob, WG, WJ, AN, DXM, STG, 1, 1>(e, kp, dx, dg, dv, st);
+      default: break;
+    }
+  }
   if constexpr (!STG && !AN && has_stage<Prob>::value) {
     // engine option "stage_roles": 1 the functor's staged dynamics, 0 whole-function evaluations, -1 (default) staged when the
     // launch is bound by the dynamics and not by its stores — persistent `values` (kp.skip_const).  Measured on the metric
     // problem, 64 iterates per launch: 75.3 -> 69.5 us with the constant block skipped, but 99.2 -> 106.6 us with all stores (21
     // more registers in a kernel that waits for its stores); same bits either way
     if (e.opt_stage_roles == 1 || (e.opt_stage_roles < 0 && (kp.skip_const || stage_always<Prob>::value)))
-      return launch_tile_pl<Prob, WG, WJ, AN, DXM, true>(e, kp, dx, dg, dv, st);
+      return launch_tile_pl<Prob, WG, WJ, AN, DXM, true, JP, CP>(e, kp, dx, dg, dv, st);
   }
   const Device& d = *e.dev;
   constexpr PlShape S = pl_shape(Prob::NX + Prob::NU + 2 + prob_nq<Prob>::value);
-  auto kern = rpm_tile_pl_kernel<Prob, S.NH, S.RG, S.NDMA, WG, WJ, AN, DXM, STG>;
+  auto kern = rpm_tile_pl_kernel<Prob, S.NH, S.RG, S.NDMA, WG, WJ, AN, DXM, STG, JP, CP>;
   const size_t lds = pl_lds_bytes(Prob::NX, Prob::NU, Prob::NC, prob_nq<Prob>::value, d.kp, DXM);
   hipError_t s = allow_lds(kern, lds);
   if (s != hipSuccess) return s;
   const long long W = (long long)d.kp.n_my_tiles * e.n_instances;
   const long long halves = W < d.pl_slots ? W : d.pl_slots;   // pl_slots: resident halves (occupancy query)
   hipLaunchKernelGGL(kern, dim3(unsigned((halves + S.NH - 1) / S.NH)), dim3(S.NH * 64 * (S.RG + S.NDMA)), lds, st, kp,
-                     e.n_instances, dx, dg, dv);
+                     e.n_instances, e.opt_tile_order, dx, dg, dv);
   return hipGetLastError();
 }
 
@@ -1271,6 +1301,8 @@ static int cons_layout(const Engine& e) {
   return (use_pipeline(e) && pl_dxm_ok(e)) ? 2 : 0;   // dx_mode 1: matrix-core D.X exists in the pipelined and the one-role kernel
 }
 bool dev_cons_is_one_role(const Engine& e) { return !e.dev || cons_layout(e) == 0; }
+
+int dev_pl_tile_slot(int order, int nh, int nb, int b, int half) { return pl_tile_slot(order, nh, nb, b, half); }
 
 int dev_pipeline_active(const Engine& e) { return e.dev && cons_layout(e) == 2 ? 1 : 0; }
 

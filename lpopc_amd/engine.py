@@ -25,7 +25,7 @@ ABI_SYMBOLS = [
     "rpm_create", "rpm_destroy", "rpm_last_error", "rpm_device_init", "rpm_get_nlp_info",
     "rpm_get_bounds_info", "rpm_get_starting_point", "rpm_eval_f", "rpm_eval_grad_f", "rpm_eval_g",
     "rpm_eval_jac_g", "rpm_eval_pair", "rpm_eval_h", "rpm_finalize_solution", "rpm_get_solution", "rpm_eval_g_dev",
-    "rpm_eval_jac_g_dev", "rpm_eval_pair_dev", "rpm_eval_f_dev", "rpm_eval_grad_f_dev", "rpm_eval_h_dev", "rpm_debug_hess_tt",
+    "rpm_eval_jac_g_dev", "rpm_eval_pair_dev", "rpm_eval_f_dev", "rpm_eval_grad_f_dev", "rpm_eval_h_dev", "rpm_debug_hess_tt", "rpm_debug_tile_slot",
     "rpm_synchronize", "rpm_set_option", "rpm_get_option", "rpm_set_instance_constants", "rpm_get_phase_sizes", "rpm_get_phase_tables",
     "rpm_shard_segments", "rpm_shard_pack_dev", "rpm_shard_unpack_dev", "rpm_shard_slot_len", "rpm_shard_pack_all_dev", "rpm_shard_unpack_all_dev", "rpm_nlp2op_control", "rpm_final_result_save",
     "rpm_solution_error", "rpm_ph_refine_mesh", "rpm_ph_refine_from_error",
@@ -106,6 +106,7 @@ def lib(path=None):
     L.rpm_eval_grad_f_dev.argtypes = [vp, vp, vp, vp]
     L.rpm_eval_h_dev.argtypes = [vp, vp, C.c_double, vp, vp, vp]
     L.rpm_debug_hess_tt.argtypes = [vp, dp, C.c_int, dp]
+    L.rpm_debug_tile_slot.argtypes = [C.c_int] * 5
     L.rpm_synchronize.argtypes = [vp]
     L.rpm_set_option.argtypes = [vp, C.c_char_p, C.c_int]
     L.rpm_set_instance_constants.argtypes = [vp, C.c_int, dp, C.c_int]
