@@ -147,7 +147,7 @@ std::vector<int> ipm_long_columns(const IpmPlan& p);   // Jacobian columns of mo
 
 // Every structural slot of the KKT storage in ascending order (IpmDev::as_*): ki = kind << 28 | index — kind 0 Hessian slot hg i,
 // 1 Jacobian entry k, 2 slack s, 3 diagonal of variable i (hg: the Hessian slot that shares it, or -1), 4 diagonal of constraint r.
-// one_pass: ipm_fill_kernel can use the list (sizes below 2^28, no two writers of one slot, offsets inside the storage); ptr[c] is
+// (decoded by SlotValue, rpm_kkt_slots.hpp).  one_pass: ipm_fill_kernel (rpm_kkt_assemble.hip) can use the list (sizes below 2^28, no two writers of one slot, offsets inside the storage); ptr[c] is
 // then the first entry at or beyond chunk c (IPM_FILL_CHUNK doubles), ptr.size() - 1 chunks.
 struct IpmFillList {
   std::vector<int> dst, ki, hg, ptr;

@@ -1,5 +1,5 @@
 // rpm_ipm_device.hpp — what the HIP translation units of row f-2 share: the parameter blocks of the interior-point
-// kernels (rpm_ipm_step_kernels.hip, rpm_kkt_factor.hip, rpm_kkt_solve.hip, rpm_ipm_lbfgs.hip) and their launchers, used by the
+// kernels (rpm_ipm_step_kernels.hip, rpm_kkt_assemble.hip, rpm_kkt_factor.hip, rpm_kkt_solve.hip, rpm_ipm_lbfgs.hip) and their launchers, used by the
 // solver loop and the C ABI (rpm_ipm_solver.hip, rpm_ipm_debug.hip).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -144,7 +144,7 @@ constexpr int IPM_VEC_BLOCKS = 64;   // most workgroups per instance of a vector
 constexpr int IPM_VEC_PART = 24;     // doubles of partial results per workgroup
 constexpr int IPM_MT = 8;   // most 16-row tiles per wave of the factorisation: block columns of up to 4 x 8 x 16 = 512 rows
 
-// launchers (rpm_ipm_step_kernels.hip; assemble: rpm_kkt_factor.hip, inertia: rpm_kkt_solve.hip); all asynchronous on `st`
+// launchers (rpm_ipm_step_kernels.hip; assemble: rpm_kkt_assemble.hip, inertia: rpm_kkt_solve.hip); all asynchronous on `st`
 void ipm_launch_set_state0(const IpmDev& D, int x_state0, int M, int nx, const double* d_state0, hipStream_t st);   // vl0 = vu0 = the measured states
 void ipm_launch_init(const IpmDev& D, const double* d_x0, hipStream_t st, int warm = 0);    // warm: the warm_start_* pushes, duals left to ipm_launch_warm_duals
 void ipm_launch_init_slack(const IpmDev& D, hipStream_t st, int warm = 0);

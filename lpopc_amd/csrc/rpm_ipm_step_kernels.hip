@@ -1,12 +1,12 @@
 // rpm_ipm_step_kernels.hip — row f-2: the vector kernels of the batched primal-dual interior-point iteration, with every iterate
 // and multiplier resident in HBM (see rpm_ipm.hpp for what is restated and what is not).  One workgroup per instance (several for
 // a few large instances); the NLP callbacks are the engine's own batched launches; the KKT matrix, its LDL^T and the substitution
-// are rpm_kkt_factor.hip and rpm_kkt_solve.hip.
+// are rpm_kkt_assemble.hip, rpm_kkt_factor.hip and rpm_kkt_solve.hip.
 //
 // Per iteration (Waechter & Biegler 2006, the equation numbers below are that paper's):
 //   grad f + A^T lambda; residuals, optimality error E_0 / E_mu (5), barrier update (7) or the          ipm_jt_lambda_kernel,
 //     adaptive rule, tau (8); in restoration mode the same for the restoration problem + the test to leave it   ipm_residual_kernel
-//   K (13), LDL^T, inertia check / correction (Algorithm IC), solution           rpm_kkt_factor.hip, rpm_kkt_solve.hip
+//   K (13), LDL^T, inertia check / correction (Algorithm IC), solution           rpm_kkt_assemble.hip, rpm_kkt_factor.hip, rpm_kkt_solve.hip
 //   direction, dz (12), fraction to the boundary (15), alpha_min (23)            ipm_direction_kernel
 //   filter line search (18)-(20), (22), second-order correction (A-5.5 .. 5.9)   ipm_trial_kernel, ipm_accept_kernel, ipm_soc_rhs_kernel, ipm_soc_direction_kernel
 //   step, multiplier reset (16), filter update, entry into the restoration phase ipm_update_kernel

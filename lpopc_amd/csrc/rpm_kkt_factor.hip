@@ -1,7 +1,5 @@
-// rpm_kkt_factor.hip — row f-2: the KKT matrix of every running instance and its factorisation (the iteration around it:
-// rpm_ipm_step_kernels.hip; substitution: rpm_kkt_solve.hip).
-//   K = [[W + Sigma + dw I, A^T], [A, -dc I]] (13) and its right-hand side      ipm_fill_kernel (ipm_zero_kernel + ipm_assemble_kernel)
-//     (restoration: [[zeta D_R^2 + Sigma, A^T], [A, -(Sigma_p^-1 + Sigma_n^-1)]]; least-squares multipliers: [[I, A^T], [A, -dc I]])
+// rpm_kkt_factor.hip — row f-2: the factorisation of the KKT matrix of every running instance (the iteration around it:
+// rpm_ipm_step_kernels.hip; the matrix and its right-hand side: rpm_kkt_assemble.hip, rpm_kkt_slots.hpp; substitution: rpm_kkt_solve.hip).
 //   LDL^T without pivoting (one band, or nested dissection over the mesh intervals and, on long meshes, over groups of their
 //     separators), pivot signs for Algorithm IC                                  kkt_factor_kernel, kkt_factor_dense_kernel, kkt_gather_add_kernel
 #include <algorithm>
@@ -11,6 +9,7 @@
 
 #include "rpm_device_internal.hpp"
 #include "rpm_ipm_device.hpp"
+#include "rpm_kkt_slots.hpp"
 
 namespace rpm {
 
@@ -50,6 +49,8 @@ struct DiagStep {
       if (4 * g + 3 > K) aj[g] = bperm_d(a_col[g] + QK * 64, R[GK]);     // a(4 g + q, K) before scaling
       if (4 * g <= K) mk[g] = row_bcast_d<K>(V[g]);                       // row K of the inverse so far
     }
+    // (a reciprocal estimate with two Newton steps instead of the division: 90.5 -> 86.6 us of diagonal-block time per
+    // interval block, not worth leaving the left-looking kernel's arithmetic)
     const double lik = r > K ? ar / dk : 0.0;
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
@@ -62,189 +63,21 @@ struct DiagStep {
     if constexpr (K + 1 < IPM_W) DiagStep<K + 1>::run(R, V, q, r, a_own, a_col);
   }
 };
-
-// ------------------------------------------------------------------------------------------------ KKT matrix + rhs
-__global__ void ipm_zero_kernel(IpmDev D) {
-  const int bi = blockIdx.y;
-  const IpmInst& S = D.inst[bi];
-  if (S.status != 0 || !S.refactor) return;
-  double2* K = reinterpret_cast<double2*>(D.K + size_t(bi) * D.kstride);
-  const long long n2 = D.kstride / 2;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n2; i += (long long)gridDim.x * blockDim.x)
-    K[i] = make_double2(0.0, 0.0);
+typedef double d4 __attribute__((ext_vector_type(4)));
+// The signs of the pivots a thread has seen, for Algorithm IC's inertia; a zero, NaN or overflowed pivot is bad.  The
+// counts go in and out by value, which keeps them in registers under the branches as the factor kernels were tuned with.
+struct PivotCount { int npos, nneg, nbad; };
+__device__ __forceinline__ PivotCount count_pivot(double dk, PivotCount n) {
+  if (dk > 0) ++n.npos; else if (dk < 0) ++n.nneg; else ++n.nbad;
+  if (!(fabs(dk) < 1e300)) ++n.nbad;
+  return n;
 }
-__global__ void ipm_assemble_kernel(IpmDev D) {
-  const int bi = blockIdx.y;
-  const IpmInst& S = D.inst[bi];
-  if (S.status != 0 || !S.refactor) return;
-  double* K = D.K + size_t(bi) * D.kstride;
-  const double *v = D.v + size_t(bi) * D.nv, *vl = D.vl + size_t(bi) * D.nv, *vu = D.vu + size_t(bi) * D.nv;
-  const double *zL = D.zL + size_t(bi) * D.nv, *zU = D.zU + size_t(bi) * D.nv;
-  const int stride = gridDim.x * blockDim.x, t0 = blockIdx.x * blockDim.x + threadIdx.x;
-  // mode 0: (13).  mode 2 (restoration, p and n eliminated): [[zeta D_R^2 + Sigma_v, A^T], [A, -(Sigma_p^-1 + Sigma_n^-1)]], no
-  // Hessian (Gauss-Newton model).  mode 3 (least-squares multipliers): [[I, A^T], [A, -delta_c]].
-  const int mode = S.mode;
-  if (mode == 0 && !D.lb_on)   // duplicates of a slot (I-part / E-part of the reference's COO) are summed in COO order: bit-reproducible.  The
-    for (int i = t0; i < D.n_hg; i += stride) {   // slot may also take the diagonal term below: two atomic adds onto zero commute
-      double acc = 0.0;
-      for (int j = D.hg_ptr[i]; j < D.hg_ptr[i + 1]; ++j) acc += D.hess[size_t(bi) * D.nnz_h + D.hg_src[j]];
-      unsafeAtomicAdd(&K[D.hg_dst[i]], acc);
-    }
-  for (int k = t0; k < D.nnz_jac; k += stride)
-    if (D.jac_dst[k] >= 0) K[D.jac_dst[k]] = D.jac[size_t(bi) * D.sv + k];
-  for (int s = t0; s < D.ns; s += stride) K[D.slk_dst[s]] = -1.0;
-  double* rhs = D.rhs + size_t(bi) * D.Nt;
-  const double mu = mode == 2 ? S.mu_r : S.mu;
-  for (int i = t0; i < D.nv; i += stride) {
-    const double l = vl[i], u = vu[i];
-    double diag = 1.0, r = 0.0;
-    if (l != u) {
-      if (mode == 3) {
-        diag = 1.0 + S.delta_w;
-        r = (i < D.n ? D.grad[size_t(bi) * D.n + i] : 0.0) - zL[i] + zU[i];
-      } else {
-        diag = S.delta_w;
-        if (mode == 0 && D.lb_on && i < D.n) diag += D.lb_small[size_t(bi) * IPM_LB_SMALL];   // sigma I of the limited-memory Hessian
-        r = D.glag[size_t(bi) * D.nv + i];
-        if (mode == 2) {
-          const double w2 = S.zeta * D.dr2[size_t(bi) * D.nv + i];
-          diag += w2;
-          r += w2 * (v[i] - D.vR[size_t(bi) * D.nv + i]);
-        }
-        const double cap = D.o.sigma_cap > 0 ? D.o.sigma_cap : 1e300;
-        if (l > -IPM_INF) { const double d = v[i] - l; diag += fmin(zL[i] / d, cap); r -= mu / d; }
-        if (u < IPM_INF) { const double d = u - v[i]; diag += fmin(zU[i] / d, cap); r += mu / d; }
-      }
-    }
-    unsafeAtomicAdd(&K[D.diag_dst[i]], diag);
-    rhs[D.pos[i]] = -r;
-  }
-  for (int r = t0; r < D.m; r += stride) {
-    double k22 = -D.o.delta_c, rr = 0.0;
-    if (mode == 0) rr = -D.c[size_t(bi) * D.m + r];
-    else if (mode == 2) {
-      const size_t q = size_t(bi) * D.m + r;
-      const double pp = D.pp[q], nn = D.nn[q], sp = D.zp[q] / pp, sn = D.zn[q] / nn, lam = D.lam[q];
-      const double rp = D.o.resto_rho - lam - mu / pp, rn = D.o.resto_rho + lam - mu / nn;
-      k22 = -(1.0 / sp + 1.0 / sn);
-      rr = -(D.c[q] - pp + nn) - rp / sp + rn / sn;
-    }
-    K[D.diag_dst[D.nv + r]] = k22;
-    rhs[D.pos[D.nv + r]] = rr;
-  }
-}
-
-// The value of a structural slot of instance bi's KKT matrix in its present mode (ki / hg coded as IpmDev::as_ki / as_hg) and, for
-// a diagonal slot, the right-hand side entry that goes with it (written on the way).  Same values as ipm_assemble_kernel's, bit
-// for bit: a slot that took two atomic adds onto zero there (Hessian sum, diagonal term) gets their sum.
-struct SlotValue {
-  const IpmDev& D;
-  int bi, mode;
-  double mu, delta_w, zeta;
-  const double *v, *vl, *vu, *zL, *zU;
-  double* rhs;
-  __device__ SlotValue(const IpmDev& D_, int bi_) : D(D_), bi(bi_) {
-    const IpmInst& S = D.inst[bi];
-    mode = S.mode;
-    mu = mode == 2 ? S.mu_r : S.mu;
-    delta_w = S.delta_w;
-    zeta = S.zeta;
-    v = D.v + size_t(bi) * D.nv; vl = D.vl + size_t(bi) * D.nv; vu = D.vu + size_t(bi) * D.nv;
-    zL = D.zL + size_t(bi) * D.nv; zU = D.zU + size_t(bi) * D.nv;
-    rhs = D.rhs + size_t(bi) * D.Nt;
-  }
-  // entry e of the tables ki_tab / hg_tab (the Hessian slot that shares a diagonal is looked up only for a diagonal)
-  __device__ double operator()(const int* ki_tab, const int* hg_tab, int e) const {
-    const int ki = ki_tab[e], kind = ki >> 28, idx = ki & 0x0fffffff;
-    if (kind == 1) return D.jac[size_t(bi) * D.sv + idx];
-    if (kind == 2) return -1.0;
-    if (kind == 4) {   // diagonal of constraint row idx
-      double k22 = -D.o.delta_c, rr = 0.0;
-      if (mode == 0) rr = -D.c[size_t(bi) * D.m + idx];
-      else if (mode == 2) {
-        const size_t q = size_t(bi) * D.m + idx;
-        const double pp = D.pp[q], nn = D.nn[q], sp = D.zp[q] / pp, sn = D.zn[q] / nn, lam = D.lam[q];
-        const double rp = D.o.resto_rho - lam - mu / pp, rn = D.o.resto_rho + lam - mu / nn;
-        k22 = -(1.0 / sp + 1.0 / sn);
-        rr = -(D.c[q] - pp + nn) - rp / sp + rn / sn;
-      }
-      rhs[D.pos[D.nv + idx]] = rr;
-      return k22;
-    }
-    // 0: a Hessian slot; 3: the diagonal of variable idx (with the Hessian slot that shares it)
-    const int hgi = kind == 0 ? idx : hg_tab[e];
-    double acc = 0.0;
-    if (mode == 0 && hgi >= 0 && !D.lb_on)
-      for (int j = D.hg_ptr[hgi]; j < D.hg_ptr[hgi + 1]; ++j) acc += D.hess[size_t(bi) * D.nnz_h + D.hg_src[j]];
-    if (kind == 0) return 0.0 + acc;   // as the add onto the zeroed slot gave it (a sum of -0.0 becomes +0.0)
-    const int i = idx;
-    const double l = vl[i], u = vu[i];
-    double diag = 1.0, r = 0.0;
-    if (l != u) {
-      if (mode == 3) {
-        diag = 1.0 + delta_w;
-        r = (i < D.n ? D.grad[size_t(bi) * D.n + i] : 0.0) - zL[i] + zU[i];
-      } else {
-        diag = delta_w;
-        if (mode == 0 && D.lb_on && i < D.n) diag += D.lb_small[size_t(bi) * IPM_LB_SMALL];   // sigma I of the limited-memory Hessian
-        r = D.glag[size_t(bi) * D.nv + i];
-        if (mode == 2) {
-          const double w2 = zeta * D.dr2[size_t(bi) * D.nv + i];
-          diag += w2;
-          r += w2 * (v[i] - D.vR[size_t(bi) * D.nv + i]);
-        }
-        const double cap = D.o.sigma_cap > 0 ? D.o.sigma_cap : 1e300;
-        if (l > -IPM_INF) { const double d = v[i] - l; diag += fmin(zL[i] / d, cap); r -= mu / d; }
-        if (u < IPM_INF) { const double d = u - v[i]; diag += fmin(zU[i] / d, cap); r += mu / d; }
-      }
-    }
-    rhs[D.pos[i]] = -r;
-    // the two-kernel path adds the two terms onto zero, in either order: acc + diag, exactly
-    return (mode == 0 && hgi >= 0) ? acc + diag : diag;
-  }
-};
-
-// ipm_zero_kernel + ipm_assemble_kernel in one pass over the storage, by destination: a workgroup builds a chunk of the
-// storage in LDS (zeros, then the chunk's structural slots, as_* tables in ascending order) and writes it out in full lines,
-// so every line of the storage leaves the chip once per refactorisation instead of being zeroed, fetched again for a
-// scattered read-modify-write and written a second time (1024-instance quadrotor sweep: 0.59 + 0.72 ms per iteration for the
-// two kernels).  Chunks inside a level-1 block that kkt_factor_dense_kernel assembles itself (IpmDev::df_on) are left out.
-__global__ __launch_bounds__(256) void ipm_fill_kernel(IpmDev D) {
-  __shared__ double buf[IPM_FILL_CHUNK];
-  const int bi = blockIdx.y;
-  const IpmInst& S = D.inst[bi];
-  if (S.status != 0 || !S.refactor) return;
-  double* K = D.K + size_t(bi) * D.kstride;
-  const int tid = threadIdx.x;
-  const SlotValue value(D, bi);
-  const bool some = D.df_on && D.l1_dense_lds && D.as_live;     // only the chunks not inside a level-1 block (kkt_level1_fused)
-  const int n_here = some ? D.as_nlive : D.as_nchunk;
-  for (int ci = blockIdx.x; ci < n_here; ci += gridDim.x) {
-    const int c = some ? D.as_live[ci] : ci;
-    const long long lo = (long long)c * IPM_FILL_CHUNK, hi = min(lo + IPM_FILL_CHUNK, D.kstride);
-    const int e0 = D.as_ptr[c], e1 = D.as_ptr[c + 1];
-    // this thread's first slot: its loads are under way while the chunk is zeroed
-    const int ef = e0 + tid;
-    double val_f = 0.0;
-    int off_f = -1;
-    if (ef < e1) { off_f = int(D.as_dst[ef] - lo); val_f = value(D.as_ki, D.as_hg, ef); }
-    double2* b2 = reinterpret_cast<double2*>(buf);
-    for (int i = tid; i < IPM_FILL_CHUNK / 2; i += 256) b2[i] = make_double2(0.0, 0.0);
-    __syncthreads();
-    if (off_f >= 0) buf[off_f] = val_f;
-    for (int e = ef + 256; e < e1; e += 256) buf[D.as_dst[e] - lo] = value(D.as_ki, D.as_hg, e);
-    __syncthreads();
-    const int len = int(hi - lo);
-    if ((reinterpret_cast<size_t>(K + lo) & 15) == 0) {
-      double2* K2 = reinterpret_cast<double2*>(K + lo);
-      typedef double d2v __attribute__((ext_vector_type(2)));   // streaming stores: the storage is next read by the factorisation, from HBM either way
-      for (int i = tid; i < (len >> 1); i += 256) __builtin_nontemporal_store(d2v{b2[i].x, b2[i].y}, reinterpret_cast<d2v*>(K2 + i));
-      if ((len & 1) && tid == 0) K[hi - 1] = buf[len - 1];
-    } else {
-      for (int i = tid; i < len; i += 256) K[lo + i] = buf[i];
-    }
-    __syncthreads();   // buf is free for the next chunk
-  }
+// every thread's counts into the workgroup's cnt[3] (LDS, zeroed at the start); cnt is complete on return
+__device__ __forceinline__ void add_pivot_counts(int* cnt, PivotCount n) {
+  if (n.npos) atomicAdd(&cnt[0], n.npos);
+  if (n.nneg) atomicAdd(&cnt[1], n.nneg);
+  if (n.nbad) atomicAdd(&cnt[2], n.nbad);
+  __syncthreads();
 }
 
 // ------------------------------------------------------------------------------------------------ band + border LDL^T
@@ -262,9 +95,6 @@ __global__ __launch_bounds__(256) void ipm_fill_kernel(IpmDev D) {
 // matrix product, Y^T = L11^-1 A^T, with the accumulators fed back as the B operand.  The border x border corner lives
 // in LDS, is updated right-looking and factored there.  Operand maps (cdna_hip_programming.md §3): A: lane l holds
 // A[l&15][l>>4], B: B[l>>4][l&15], C/D: row (l>>4) + 4 reg, column l&15.
-#ifndef IPM_DIAG_SPLIT
-#define IPM_DIAG_SPLIT 1   // kkt_factor_dense_kernel's diagonal blocks over all 64 lanes of their wave (0: a whole row per lane, four copies)
-#endif
 #ifndef IPM_LB
 #define IPM_LB 2   // waves per SIMD the 4-tile factorisation is compiled for (3: 168 VGPRs, 52 of them spilled since the pivots moved to v_readlane)
 #endif
@@ -277,7 +107,6 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? (MT == 2 ? 4 : 1) : (MT == 4 ? I
   // workgroup = (instance, sub-problem sub0 + s).  partial 1: nested dissection level 1 — eliminate the band part only and
   // leave the Schur complement of the border x border corner, unfactored, in the corner's storage.  partial 2: the corner only
   // (what kkt_factor_dense_kernel left of a last level whose band part it eliminated; its pivot counts are added to).
-  typedef double d4 __attribute__((ext_vector_type(4)));
   constexpr int W = IPM_W;
   const int bi = blockIdx.x / n_here, sidx = sub0 + int(blockIdx.x) % n_here, t = threadIdx.x, nt = blockDim.x;
   const IpmInst& S = inst[bi];
@@ -295,7 +124,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? (MT == 2 ? 4 : 1) : (MT == 4 ? I
   double* C = BY + size_t(G.nb) * W;            // nb (nb + 1) / 2: the corner's lower triangle, packed by rows
   __shared__ int cnt[3];
   if (t < 3) cnt[t] = 0;
-  int npos = 0, nneg = 0, nbad = 0;
+  PivotCount pc = {0, 0, 0};
   const int nb = G.nb;
   const int wv = t >> 6, lr = t & 15, lq = (t & 63) >> 4;
 #ifdef IPM_TIMING
@@ -411,7 +240,6 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? (MT == 2 ? 4 : 1) : (MT == 4 ? I
     if (wv != 0) {
       if (J0 > 0 && nb > 0) corner_update(1, NW - 1);    // the previous block column's, while wave 0 is busy below
     } else {                    // tile 0 holds the diagonal block (rows q < w): its LDL^T and the inverse of L11 by this wave
-#if IPM_DIAG_SPLIT
       // the accumulator tile is DiagStep's layout already: lane (lq, lr) holds columns lq + 4 g of row lr
       double R[4], V[4];
       int a_col[4];
@@ -430,48 +258,6 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? (MT == 2 ? 4 : 1) : (MT == 4 ? I
         Mi[lr * W + j] = V[g];
         if (j == lr) invd[lr] = lr < w ? 1.0 / R[g] : 0.0;
       }
-#else
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int c = lq + 4 * g;
-        if (lr < w && c <= lr) Dg[lr * (W + 1) + c] = acc[0][g];
-      }
-      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      double row[W], inv[W];    // lane (l & 15) = row of the block and of L11^-1 (the same eliminations applied to I)
-#pragma unroll
-      for (int c = 0; c < W; ++c) {
-        row[c] = (lr < w && c <= lr) ? Dg[lr * (W + 1) + c] : (c == lr ? 1.0 : 0.0);
-        inv[c] = c == lr ? 1.0 : 0.0;
-      }
-#pragma unroll
-      for (int k = 0; k < W; ++k) {
-        // all cross-lane reads of the step first (they are independent), then the arithmetic.  The four groups of 16 lanes hold
-        // the same rows, so lane j of the wave serves everybody: scalar reads (v_readlane) instead of LDS-routed shuffles
-        const double dk = readlane_d(row[k], k);                   // pivot: row k's own diagonal
-        double ajk[W], mkj[W];
-#pragma unroll
-        for (int j = k + 1; j < W; ++j) ajk[j] = readlane_d(row[k], j);     // a(j, k) before scaling
-#pragma unroll
-        for (int j = 0; j <= k; ++j) mkj[j] = readlane_d(inv[j], k);        // row k of the inverse so far
-        const double lik = lr > k ? row[k] / dk : 0.0;
-        // (no `lr >= j` guard: entries right of a lane's diagonal are never read, lanes at or above row k have lik = 0, and the
-        // compare and two selects per entry were a quarter of this loop's instructions — the loop is issue-bound)
-#pragma unroll
-        for (int j = k + 1; j < W; ++j) row[j] = __builtin_fma(-lik, ajk[j], row[j]);
-#pragma unroll
-        for (int j = 0; j <= k; ++j) inv[j] = __builtin_fma(-lik, mkj[j], inv[j]);
-        if (lr > k) row[k] = lik;
-      }
-      if (lq == 0) {
-#pragma unroll
-        for (int c = 0; c < W; ++c) {
-          if (lr < w && c <= lr) Dg[lr * (W + 1) + c] = row[c];
-          Mi[lr * W + c] = inv[c];
-        }
-        invd[lr] = lr < w ? 1.0 / row[lr] : 0.0;
-      }
-#endif
     }
     __syncthreads();
     IPM_TICK(2);
@@ -497,11 +283,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? (MT == 2 ? 4 : 1) : (MT == 4 ? I
       const int di = t / W, dj = t % W;
       if (di < w && dj <= di) K[G.at(J0 + di, J0 + dj)] = di == dj ? Dg[di * (W + 1) + dj] : Mi[di * W + dj];
     }
-    if (t < w) {
-      const double dk = Dg[t * (W + 1) + t];
-      if (dk > 0) ++npos; else if (dk < 0) ++nneg; else ++nbad;
-      if (!(fabs(dk) < 1e300)) ++nbad;
-    }
+    if (t < w) pc = count_pivot(Dg[t * (W + 1) + t], pc);
     __syncthreads();
     IPM_TICK(3);
     IPM_TICK(4);
@@ -517,10 +299,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? (MT == 2 ? 4 : 1) : (MT == 4 ? I
       const int r = idx / nb, c = idx % nb;
       if (r >= c) K[G.at(G.Nb + r, G.Nb + c)] = C[ct(r, c)];
     }
-    if (npos) atomicAdd(&cnt[0], npos);
-    if (nneg) atomicAdd(&cnt[1], nneg);
-    if (nbad) atomicAdd(&cnt[2], nbad);
-    __syncthreads();
+    add_pivot_counts(cnt, pc);
     if (t < 3) piv[(size_t(bi) * n_sub + sidx) * 3 + t] = cnt[t];
 #ifdef IPM_TIMING
     if (t == 0 && sidx == IPM_TIMING_SUB)
@@ -561,16 +340,9 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? (MT == 2 ? 4 : 1) : (MT == 4 ? I
   for (int idx = t; idx < nb * nb; idx += nt) {
     const int r = idx / nb, c = idx % nb;
     if (r >= c) K[G.at(G.Nb + r, G.Nb + c)] = C[ct(r, c)];
-    if (r == c) {
-      const double dk = C[ct(r, r)];
-      if (dk > 0) ++npos; else if (dk < 0) ++nneg; else ++nbad;
-      if (!(fabs(dk) < 1e300)) ++nbad;
-    }
+    if (r == c) pc = count_pivot(C[ct(r, r)], pc);
   }
-  if (npos) atomicAdd(&cnt[0], npos);
-  if (nneg) atomicAdd(&cnt[1], nneg);
-  if (nbad) atomicAdd(&cnt[2], nbad);
-  __syncthreads();
+  add_pivot_counts(cnt, pc);
   IPM_TICK(5);
   if (t < 3) piv[(size_t(bi) * n_sub + sidx) * 3 + t] = (partial == 2 ? piv[(size_t(bi) * n_sub + sidx) * 3 + t] : 0) + cnt[t];
 #ifdef IPM_TIMING
@@ -599,7 +371,6 @@ template <bool EARLY, bool CORNER>
 __global__ __launch_bounds__(512, 1) void kkt_factor_dense_kernel(double* Kall, long long kstride, const KktSub* subs, int sub0, int n_here,
                                                                   int n_sub, IpmInst* inst, int* piv, IpmDev D, int assemble, int forward,
                                                                   int partial) {
-  typedef double d4 __attribute__((ext_vector_type(4)));
   constexpr int W = IPM_W, NWV = IPM_DENSE_TILE_WAVES, MAXS = IPM_DENSE_SLOTS;
   // the barriers of this kernel order LDS traffic only: __syncthreads() would also wait for the stores of L into the storage
   // (s_waitcnt vmcnt(0)), a trip to the L2 on the critical path of every block column
@@ -657,6 +428,7 @@ __global__ __launch_bounds__(512, 1) void kkt_factor_dense_kernel(double* Kall, 
     const double* jac = D.jac + size_t(bi) * D.sv;
 #pragma unroll 4
     for (int e = ea + t; e < eb; e += 512) vals[1 + e - ea] = jac[D.df_ki[e] & 0x0fffffff];
+    // (SlotValue's Hessian duplicate sum, restated: a loop of its own for the Hessian slots, which avoids divergence)
     const bool with_h = value.mode == 0 && !D.lb_on;
     const double* hess = D.hess + size_t(bi) * D.nnz_h;
 #pragma unroll 2
@@ -684,7 +456,7 @@ __global__ __launch_bounds__(512, 1) void kkt_factor_dense_kernel(double* Kall, 
   if (wv == NWV) {
     // ---------------- the eighth wave holds no tiles: it factors the diagonal blocks (its registers are free for that) ----------------
     __builtin_amdgcn_s_setprio(3);   // the chain of diagonal blocks is the critical path: this wave goes first on its SIMD
-    int npos = 0, nneg = 0, nbad = 0;
+    PivotCount pc = {0, 0, 0};
 #ifdef IPM_TIMING
     long long tq[4] = {0, 0, 0, 0}, tp = wall_clock64();
 #define IPM_DTICK(i) do { const long long n_ = wall_clock64(); tq[i] += n_ - tp; tp = n_; } while (0)
@@ -696,7 +468,6 @@ __global__ __launch_bounds__(512, 1) void kkt_factor_dense_kernel(double* Kall, 
       double* DgJ = Dg + (J & 1) * DGN;
       IPM_LDS_BARRIER();          // B1: the owner of tile (J, J) has put it into its copy of Dg — and, from J = 1 on, block column J - 1's panel is in LDS
       IPM_DTICK(0);
-#if IPM_DIAG_SPLIT
       {   // kkt_factor_kernel's elimination, entry for entry, over all 64 lanes (DiagStep)
         double R[4], V[4];
         int a_col[4];
@@ -719,42 +490,6 @@ __global__ __launch_bounds__(512, 1) void kkt_factor_dense_kernel(double* Kall, 
           }
         }
       }
-#else
-      double row[W], inv[W];    // lane (l & 15) = row of the block and of L11^-1 (kkt_factor_kernel's elimination, word for word)
-#pragma unroll
-      for (int c = 0; c < W; ++c) {
-        row[c] = (lr < w && c <= lr) ? DgJ[lr * (W + 1) + c] : (c == lr ? 1.0 : 0.0);
-        inv[c] = c == lr ? 1.0 : 0.0;
-      }
-#pragma unroll
-      for (int k = 0; k < W; ++k) {
-        const double dk = readlane_d(row[k], k);
-        double ajk[W], mkj[W];
-#pragma unroll
-        for (int j = k + 1; j < W; ++j) ajk[j] = readlane_d(row[k], j);
-#pragma unroll
-        for (int j = 0; j <= k; ++j) mkj[j] = readlane_d(inv[j], k);
-        // (a reciprocal estimate with two Newton steps instead of the division: 90.5 -> 86.6 us of diagonal-block time per
-        // interval block, not worth leaving the left-looking kernel's arithmetic)
-        const double lik = lr > k ? row[k] / dk : 0.0;
-        // (no `lr >= j` guard as in kkt_factor_kernel: entries right of a lane's diagonal are never read, and the compare and
-        // the two selects per entry are a quarter of this loop's instructions — it is issue-bound, 800 cycles per step)
-#pragma unroll
-        for (int j = k + 1; j < W; ++j) row[j] = __builtin_fma(-lik, ajk[j], row[j]);
-#pragma unroll
-        for (int j = 0; j <= k; ++j) inv[j] = __builtin_fma(-lik, mkj[j], inv[j]);
-        if (lr > k) row[k] = lik;
-      }
-      if (lq == 0) {
-#pragma unroll
-        for (int c = 0; c < W; ++c) {
-          if (lr < w && c <= lr) DgJ[lr * (W + 1) + c] = row[c];
-          Mi[lr * IPM_DENSE_LDS_ROW + c] = inv[c];
-        }
-        invd[lr] = lr < w ? 1.0 / row[lr] : 0.0;
-        dv[lr] = lr < w ? row[lr] : 0.0;
-      }
-#endif
       IPM_DTICK(1);
       IPM_LDS_BARRIER();          // B2: Dg, Mi, invd are there
       if (forward) {              // y = L11^-1 r of this block's unknowns (r is final: the tile waves added the last panel's share before B2),
@@ -774,17 +509,14 @@ __global__ __launch_bounds__(512, 1) void kkt_factor_dense_kernel(double* Kall, 
         const int di = idx / W, dj = idx % W;
         if (di < w && dj <= di) K[G.at(J0 + di, J0 + dj)] = di == dj ? DgJ[di * (W + 1) + dj] : Mi[di * IPM_DENSE_LDS_ROW + dj];
       }
-      if (lane < w) {
-        const double dk = DgJ[lane * (W + 1) + lane];
-        if (dk > 0) ++npos; else if (dk < 0) ++nneg; else ++nbad;
-        if (!(fabs(dk) < 1e300)) ++nbad;
-      }
+      if (lane < w) pc = count_pivot(DgJ[lane * (W + 1) + lane], pc);
       IPM_DTICK(2);
     }
     IPM_LDS_BARRIER();            // the last block column's panel is in LDS (the tile waves' last meeting point)
 #ifdef IPM_TIMING
     if (lane == 0 && sidx == 0) { inst[bi].dbg[6] = tq[0] + tq[2]; inst[bi].dbg[7] = tq[1]; }   // waiting for the tile waves | factoring
 #endif
+    int npos = pc.npos, nneg = pc.nneg, nbad = pc.nbad;
     for (int o = 32; o; o >>= 1) { npos += __shfl_xor(npos, o); nneg += __shfl_xor(nneg, o); nbad += __shfl_xor(nbad, o); }
     if (lane == 0) {
       int* pv = piv + (size_t(bi) * n_sub + sidx) * 3;
@@ -1144,6 +876,9 @@ static bool dense_early(size_t lds_bytes) { return lds_bytes > kkt_factor_dense_
 size_t kkt_factor_lds_bytes(const IpmPlan& p) {
   return p.nd ? p.max_factor_lds : ipm_factor_lds_bytes(p.b, p.nb);
 }
+// tiles_per_wave, here and in launch_factor_subs: 4 and 6 are MT tiles per wave of 4 waves (block columns of up to 256 and 384
+// rows), the two-digit codes 28 and 38 are <MT, NW> = <2, 8> and <3, 8> — the same rows over 8 waves, for a few large
+// instances —, anything else IPM_MT tiles per wave of 4 waves (512 rows)
 hipError_t kkt_factor_prepare(int tiles_per_wave, size_t lds_bytes) {
   if (lds_bytes <= 48 * 1024) return hipSuccess;
   if (tiles_per_wave == 38) return hipFuncSetAttribute(reinterpret_cast<const void*>(kkt_factor_kernel<3, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds_bytes));
@@ -1234,17 +969,6 @@ void kkt_launch_factor(const IpmDev& D, int tiles_per_wave, size_t lds_bytes, hi
     corners(D.cg2_ptr, D.cg2_src, D.cg2_dst, D.n_cg2, D.n_cg2_long);
   }
   launch_factor_subs(D, D.n_l1 + D.n_l2, 1, 0, tiles_per_wave, lds_bytes, st, D.last_dense_lds);   // last level: (group) separators + border
-}
-void ipm_launch_assemble(const IpmDev& D, int nnz_max, hipStream_t st) {
-  if (D.as_nchunk > 0) {
-    const int chunks = kkt_level1_fused(D) ? D.as_nlive : D.as_nchunk;
-    hipLaunchKernelGGL(ipm_fill_kernel, dim3(unsigned(std::max(1, std::min(chunks, 65535))), unsigned(D.B)), dim3(256), 0, st, D);
-    return;
-  }
-  const int assemble_blocks = std::max(1, std::min(D.B <= 32 ? 2048 : 64, (nnz_max + 255) / 256));   // a few large instances: the whole chip
-  const int zero_blocks = int(std::max<long long>(1, std::min<long long>(256, D.kstride / 2 / 256 + 1)));
-  hipLaunchKernelGGL(ipm_zero_kernel, dim3(unsigned(zero_blocks), unsigned(D.B)), dim3(256), 0, st, D);
-  hipLaunchKernelGGL(ipm_assemble_kernel, dim3(unsigned(assemble_blocks), unsigned(D.B)), dim3(256), 0, st, D);
 }
 
 }  // namespace rpm

@@ -1,4 +1,4 @@
-// rpm_kkt_solve.hip — row f-2: substitution with the factors of rpm_kkt_factor.hip, the right-hand-side glue of the nested
+// rpm_kkt_solve.hip — row f-2: substitution with the factors of rpm_kkt_factor.hip (in the right-hand side rpm_kkt_assemble.hip wrote), the right-hand-side glue of the nested
 // dissection and the inertia verdict of Algorithm IC      kkt_solve_kernel, kkt_gather_seq_kernel, kkt_vec_kernel, ipm_inertia_kernel
 #include <algorithm>
 #include <cmath>

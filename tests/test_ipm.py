@@ -707,14 +707,17 @@ def test_restatement_restoration_rescues_bryson_denham_on_the_default_mesh():
 
 
 @pytest.mark.gpu
-def test_restoration_and_multiplier_passes_through_the_assembling_factor_kernel(built):
+def test_restoration_and_multiplier_passes_through_the_assembling_factor_kernel(built, monkeypatch):
     """The restoration phase (mode 2: another matrix and right-hand side) and the least-squares-multiplier pass on leaving it
     (mode 3) with level 1 assembled and forward-substituted inside kkt_factor_dense_kernel: the same iterates, bit for bit, as with
-    the fill kernel and the separate substitution (option fused_fill), and restorations do happen on this run."""
+    the fill kernel and the separate substitution (option fused_fill) and as with ipm_zero_kernel + ipm_assemble_kernel
+    (RPM_IPM_TWO_PASS_FILL, read when the solver is created), and restorations do happen on this run."""
     from lpopc_amd.engine import BatchedIPM, NLPEngine
     prob = problems.bryson_denham()
     out = []
-    for fused in (1, 0):
+    for fused, two_pass in ((1, 0), (0, 0), (0, 1)):
+        if two_pass:
+            monkeypatch.setenv("RPM_IPM_TWO_PASS_FILL", "1")
         eng = NLPEngine(prob, _exact(), n_instances=2, device=0)
         eng.set_option("ipm_nested", 1)
         ipm = BatchedIPM(eng, tol=1e-6, trace=300, mu_strategy="monotone")
@@ -725,10 +728,11 @@ def test_restoration_and_multiplier_passes_through_the_assembling_factor_kernel(
         out.append((r, [ipm.trace(bi).copy() for bi in range(2)], ipm.restorations().copy()))
         ipm.close()
         eng.close()
-    (a, ta, ra), (b, tb, rb) = out
+    a, ta, ra = out[0]
     assert (a["status"] == 0).all() and (ra >= 1).all()
-    assert np.array_equal(ra, rb) and np.array_equal(a["iterations"], b["iterations"]) and np.array_equal(a["x"], b["x"])
-    assert all(np.array_equal(p, q) for p, q in zip(ta, tb))
+    for b, tb, rb in out[1:]:
+        assert np.array_equal(ra, rb) and np.array_equal(a["iterations"], b["iterations"]) and np.array_equal(a["x"], b["x"])
+        assert all(np.array_equal(p, q) for p, q in zip(ta, tb))
 
 
 @pytest.mark.gpu

@@ -1,6 +1,7 @@
 """One pass of the interior-point iteration on injected states (rpm_ipm_debug_start + rpm_ipm_debug_pass: the solve loop's own
 steps) against the long-double reference of tests/_ipm_pass_reference.py: the residual pass (ipm_jt_lambda_kernel,
-ipm_residual_kernel), the KKT assembly (ipm_fill_kernel / ipm_assemble_kernel, SlotValue) and the direction kernel.
+ipm_residual_kernel), the KKT assembly (rpm_kkt_assemble.hip: ipm_fill_kernel by destination through SlotValue of
+rpm_kkt_slots.hpp, ipm_zero_kernel + ipm_assemble_kernel by source with the rule restated, and the two against each other bit for bit) and the direction kernel.
 
 The comparison rule, the same everywhere:
   a single expression or a maximum     |dev - ref| <= 8 * 2^-52 * M,               M = sum of the magnitudes of its operands
@@ -326,6 +327,38 @@ def test_stage_2_two_kernel_assembly(built, monkeypatch, nested):
     monkeypatch.setenv("RPM_IPM_TWO_PASS_FILL", "1")
     _run_stage2("quadrotor", None, nested, "exact", 0)
     _run_stage2("bryson_denham", None, nested, "limited-memory", 1)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("hessian", ["exact", "limited-memory"])
+@pytest.mark.parametrize("nested", [0, 1], ids=["band", "nested"])
+@pytest.mark.parametrize("name", ["quadrotor", "bryson_denham"])
+def test_stage_2_both_assembly_routes_write_the_same_bits(built, monkeypatch, name, nested, hessian):
+    """the one-pass fill (by destination, SlotValue of rpm_kkt_slots.hpp) and ipm_zero_kernel + ipm_assemble_kernel (by source,
+    atomic adds onto zero) state the slot rule separately: the same state leaves the same storage and right-hand side, bit for bit —
+    duplicate sums and lone Hessian slots (exact), sigma on the diagonal (limited-memory), the sigma_cap branch (at_bounds)"""
+    one_pass = Case(name, hessian=hessian, nested=nested)
+    try:
+        monkeypatch.setenv("RPM_IPM_TWO_PASS_FILL", "1")          # read when the solver is created
+        two_pass = Case(name, hessian=hessian, nested=nested)
+        try:
+            for state in ("interior", "at_bounds"):
+                outs = []
+                for case in (one_pass, two_pass):
+                    if state == "at_bounds":
+                        case.set(**TIGHT)
+                    st = case.start(*(case.tight_inputs() if state == "at_bounds" else ()))
+                    assert not st["status"].any()
+                    outs.append(case.ipm.debug_pass(2))
+                    assert (outs[-1]["inst"]["status"] == 0).all()
+                for b in range(one_pass.B):
+                    assert np.array_equal(outs[0]["K"][b], outs[1]["K"][b]), (name, state, b, "K")
+                    assert np.array_equal(outs[0]["rhs"][b], outs[1]["rhs"][b]), (name, state, b, "rhs")
+                assert outs[0]["K"].any() and outs[0]["rhs"].any()
+        finally:
+            two_pass.close()
+    finally:
+        one_pass.close()
 
 
 @pytest.mark.gpu
