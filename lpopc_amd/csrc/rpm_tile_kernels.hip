@@ -1,28 +1,53 @@
 // rpm_tile_kernels.hip — the constraint / Jacobian kernels for gfx950 (MI355X / CDNA4) and their launchers.
 //
 // Kernels (DESIGN.md §Kernels has the roofline of each):
-//   rpm_tile_kernel   K1+K2+K3 fused: per-node dynamics/path evaluation, forward-difference (or
+//   tile kernels      K1+K2+K3 fused: per-node dynamics/path evaluation, forward-difference (or
 //                     analytic) node Jacobian, LGR defect D.X - (dt/2) f, and the coalesced block
-//                     scatter of the COO Jacobian values, plus this workgroup's share of the
-//                     constant Doffdiag block.  Replaces NLPWrapper::GetConsFun (LpNLPWrapper.cpp:55-229),
+//                     scatter of the COO Jacobian values, plus the tile's share of the
+//                     constant Doffdiag block.  Replace NLPWrapper::GetConsFun (LpNLPWrapper.cpp:55-229),
 //                     GetPhaseJacbi (:524-862), LpFDderive::DerivDae (LpFiniteDifferenceDerive.cpp:194-324)
-//                     and dsmatrix::operator* (SparseMatrix/LpSparseMatrix.cpp:127-155).
+//                     and dsmatrix::operator* (SparseMatrix/LpSparseMatrix.cpp:127-155).  Three thread
+//                     layouts of the same arithmetic, bit-identical results, chosen by launch size (cons_layout):
+//     rpm_tile_kernel      one role per thread, tiles of <= T nodes: the shortest critical path
+//     rpm_tile_rl_kernel   role-looped: 64 nodes x RG role groups, a wave is one role of 64 nodes
+//     rpm_tile_pl_kernel   pipelined: the role loop made persistent, DMA waves stage the next tile
 //   endpoint block    K4: events, linkages, A_lin.x rows and their Jacobian entries
 //                     (LpNLPWrapper.cpp:125-136,180-211,406-522,833-861; :45,:242); one extra workgroup
-//                     of the same launch.
+//                     of the same launch, or (pipelined) one DMA wave.
 //
-// Thread layout of rpm_tile_kernel: a workgroup owns a tile of <= T consecutive collocation nodes of one
-// phase; thread = (role, node) with node fastest, so that the N-long diagonal runs of every Jacobian
+// A workgroup (a half of one in the pipelined kernel) works on a tile of consecutive collocation nodes of one
+// phase; the node is the fastest thread index, so that the N-long diagonal runs of every Jacobian
 // block are written by consecutive lanes (coalesced 8-byte stores).  Role 0 evaluates the unperturbed
-// dynamics, role 1+v the dynamics with variable v perturbed (v = states, controls, time) — the
-// reference's (2+nx+nu) whole-vector user calls become (2+nx+nu) roles evaluated concurrently.
+// dynamics, role 1+v the dynamics with variable v perturbed (v = states, controls, time, static parameters) —
+// the reference's (2+nx+nu+nq) whole-vector user calls become (2+nx+nu+nq) roles.
 // State roles also compute their state's D.X row from the LDS-staged D rows and X tile.
+// What a role computes is written once, in the shared rules below the endpoint block (role_dynamics ...
+// jacobian_blocks); a layout adds its thread layout, its loads, its synchronisation and how a value is stored.
 #include "rpm_device_internal.hpp"
 
 namespace rpm {
 
 
 // ------------------------------------------------------------------------------------------
+// The base values of an endpoint work item (the first n of lane 0's outputs val[NV]) to every lane, for the differences
+// against the base: a lane shuffle where one wave does the item (WAVE), else LDS plus a workgroup barrier.
+template <int NV, bool WAVE>
+__device__ __forceinline__ void base_to_lanes(const double* val, int n, int lane, double* lds, double* base) {
+  if constexpr (WAVE) {
+#pragma unroll
+    for (int i = 0; i < NV; ++i) base[i] = __shfl(val[i], 0, 64);
+  } else {
+    if (lane == 0) {
+#pragma unroll
+      for (int i = 0; i < NV; ++i)
+        if (i < n) lds[i] = val[i];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < NV; ++i) base[i] = lds[i];
+  }
+}
+
 // endpoint rows: events, linkages, linear rows.  Each work item (TaskDev) is one workgroup of the same
 // launch, so the three kinds run concurrently on different CUs.
 // WAVE = true: the work item is done by ONE wave (lanes = perturbations, the base values travel by lane shuffle, no
@@ -86,24 +111,13 @@ __device__ void endpoint_block(const KParams& K, const TaskDev task, const doubl
 #pragma unroll
     for (int i = 0; i < NE; ++i) ev[i] = 0.0;
     if (act && (pi == 0 || !AN)) pf_event<Prob>(ph.phase_num, t0, x0, tf, xf, pp, c, ev);
-    double base[NE];
-    if constexpr (WAVE) {
-#pragma unroll
-      for (int i = 0; i < NE; ++i) base[i] = __shfl(ev[i], 0, 64);
-    }
-    if (pi == 0) {
+    if (WG && pi == 0) {
 #pragma unroll
       for (int i = 0; i < NE; ++i)
-        if (i < ph.ne) {
-          if (!WAVE) lds[i] = ev[i];
-          if (WG) { g[ph.g0 + (NX + Prob::NC) * ph.N + i] = ev[i]; chk_note(bad_g, ev[i]); }
-        }
+        if (i < ph.ne) { g[ph.g0 + (NX + Prob::NC) * ph.N + i] = ev[i]; chk_note(bad_g, ev[i]); }
     }
-    if constexpr (!WAVE) {
-      __syncthreads();
-#pragma unroll
-      for (int i = 0; i < NE; ++i) base[i] = lds[i];
-    }
+    double base[NE];
+    base_to_lanes<NE, WAVE>(ev, ph.ne, pi, lds, base);
     if (WJ && act && pi >= 1) {
       const int v = pi - 1;
       double de[NE];
@@ -160,24 +174,13 @@ __device__ void endpoint_block(const KParams& K, const TaskDev task, const doubl
 #pragma unroll
     for (int i = 0; i < NL; ++i) lo[i] = 0.0;
     if (act && (pi == 0 || !AN)) pf_link<Prob>(lk.left + 1, lk.right + 1, xl, xr, ql, qr, c, lk.nlink, lo);
-    double base[NL];
-    if constexpr (WAVE) {
-#pragma unroll
-      for (int i = 0; i < NL; ++i) base[i] = __shfl(lo[i], 0, 64);
-    }
-    if (pi == 0) {
+    if (WG && pi == 0) {
 #pragma unroll
       for (int i = 0; i < NL; ++i)
-        if (i < lk.nlink) {
-          if (!WAVE) lds[i] = lo[i];
-          if (WG) { g[lk.g0 + i] = lo[i]; chk_note(bad_g, lo[i]); }
-        }
+        if (i < lk.nlink) { g[lk.g0 + i] = lo[i]; chk_note(bad_g, lo[i]); }
     }
-    if constexpr (!WAVE) {
-      __syncthreads();
-#pragma unroll
-      for (int i = 0; i < NL; ++i) base[i] = lds[i];
-    }
+    double base[NL];
+    base_to_lanes<NL, WAVE>(lo, lk.nlink, pi, lds, base);
     if (WJ && act && pi >= 1) {
       const int v = pi - 1;
       double dl[NL];
@@ -197,9 +200,13 @@ __device__ void endpoint_block(const KParams& K, const TaskDev task, const doubl
 
 // ------------------------------------------------------------------------------------------
 // The per-node role arithmetic of the three tile layouts (rpm_tile_kernel, rpm_tile_rl_kernel, rpm_tile_pl_kernel).  One
-// copy, so that the layouts stay bit-identical; each layout keeps its own thread layout, loads, staging, synchronisation and
-// store address form.  A thread works on node k of its tile (lane kk of the [..][T] LDS rows) for one role: role 0 is the
-// unperturbed dynamics, role 1 + v the dynamics with variable v = [states, controls, time, static parameters] perturbed.
+// copy, so that the layouts stay bit-identical: the dynamics (role_dynamics), the perturbation (perturb_uniform), the published
+// base (publish_base), the defect (store_defect) and what becomes of a role's outputs (jacobian_blocks; the pipelined kernel
+// restates it, see there); stage_tile_inputs is the LDS staging of the two kernels without DMA waves.  Each layout keeps its
+// own thread layout, loads of the node's point, D.X sum, synchronisation, constant-block stores and the one expression that
+// stores a Jacobian value (the lambda it hands to jacobian_blocks).  A thread works on node k of its tile (lane kk of the
+// [..][T] LDS rows) for one role: role 0 is the unperturbed dynamics, role 1 + v the dynamics with variable
+// v = [states, controls, time, static parameters] perturbed.
 // CHK: the one-role kernel notes NaN/Inf among the values it stores (host-pointer path); the others pass false.
 
 // The dynamics of a role at (tk, xs, us = [controls, static parameters]): f and c, or with AN column v of the node
@@ -217,6 +224,25 @@ __device__ __forceinline__ void role_dynamics(int phase_num, int role, double tk
   } else if constexpr (AN) {
     pf_dae_jac_col<Prob>(phase_num, v, tk, xs, us, us + Prob::NU, c, f, cp);  // f, cp now hold column v of the Jacobian
   }
+}
+
+// The one-role and the role-looped kernel stage a tile's X rows, U rows and (WG) D rows in LDS with all nthr threads
+// (coalesced: every run is contiguous in HBM); the caller's barrier follows.  The pipelined kernel's DMA waves copy the same
+// runs straight into LDS instead (`stage` there).  (x without __restrict__: with it one role-looped instantiation takes 4
+// more VGPRs and loses a wave of occupancy.)
+template <int NX, int NU, int T, bool WG>
+__device__ __forceinline__ void stage_tile_inputs(const KParams& K, const TileDev& tl, const double* x, int tid, int nthr,
+                                                  double* Xs, double* Us, double* Ds) {
+  for (int q = tid; q < NX * tl.span_len; q += nthr) {
+    const int i = q / tl.span_len, r = q - i * tl.span_len;
+    Xs[i * K.max_span + r] = x[tl.x_state0 + i * (tl.N + 1) + tl.span0 + r];
+  }
+  for (int q = tid; q < NU * tl.cnt; q += nthr) {
+    const int j = q / tl.cnt, r = q - j * tl.cnt;
+    Us[j * T + r] = x[tl.x_control0 + j * tl.N + tl.k0 + r];
+  }
+  if (WG)
+    for (int q = tid; q < tl.drow_len; q += nthr) Ds[q] = K.dvals[tl.drow0 + q];
 }
 
 // Finite-difference step of a wave-uniform role: h = tol (1+|v|), v+h  (LpFiniteDifferenceDerive.cpp:208-214).  The caller
@@ -263,6 +289,58 @@ __device__ __forceinline__ void store_defect(int sv, double dx, double tspan, co
   if (CHK) chk_note(bad_g, dfc);
 }
 
+// What becomes of the outputs f, cp of role 1 + v at node k: the column J = (perturbed - unperturbed) / h of the node Jacobian
+// (AN: f, cp already hold it) and from it this role's entry of every Jacobian block, handed to store(blk, val) with
+// blk = o * NB + column block for output row o — the caller's store puts it at values[v_nl0 + blk * N + k].
+//   v != time: blocks d/dx_v, d/du_v or d/dp_j of every output row (:698-743, :763-769, :776-796, :814-820), Ddiag - ret on
+//     the diagonal block (:712); the parameter blocks follow the two time blocks and take their derivative column, not the
+//     time column — SURVEY B-6, B-7
+//   v == time: the d/dt0 and d/dtf blocks (:748-760, :801-811); B-5 sign of the reference kept
+template <class Prob, int T, bool AN, class Store>
+__device__ __forceinline__ void jacobian_blocks(int v, double h, const double* f, const double* cp, const double* Fb, int kk,
+                                                double tau, double t0, double tf, double ddiag, Store store) {
+  constexpr int NX = Prob::NX, NU = Prob::NU, NC = Prob::NC, NQ = prob_nq<Prob>::value;
+  constexpr int NO = NX + NC;              // outputs per node: f then c
+  constexpr int NB = NX + NU + 2 + NQ;     // Jacobian blocks per output row: x.., u.., t0, tf, p..
+  double J[NO];
+#pragma unroll
+  for (int o = 0; o < NO; ++o) {
+    const double pert = o < NX ? f[o < NX ? o : 0] : cp[o >= NX ? o - NX : 0];
+    J[o] = AN ? pert : (pert - Fb[o * T + kk]) / h;
+  }
+  if (v != NX + NU) {
+    const int bv = v < NX + NU ? v : v + 1;
+#pragma unroll
+    for (int o = 0; o < NO; ++o) {
+      double val;
+      if (o < NX) {
+        const double ret = J[o] * (tf - t0) / 2.0;
+        val = (o == v) ? ddiag - ret : -ret;
+      } else {
+        val = J[o];
+      }
+      store(o * NB + bv, val);
+    }
+  } else {
+    const double a0 = -(tau * 0.5) + 0.5, af = (tau * 0.5) + 0.5;
+#pragma unroll
+    for (int o = 0; o < NO; ++o) {
+      double v0, vf;
+      if (o < NX) {
+        const double fb = Fb[o * T + kk];
+        const double dt = J[o] * (tf - t0) / 2.0;
+        v0 = fb * (0.5) - a0 * dt;
+        vf = -fb * (0.5) + af * dt;
+      } else {
+        v0 = a0 * J[o];
+        vf = af * J[o];
+      }
+      store(o * NB + NX + NU, v0);
+      store(o * NB + NX + NU + 1, vf);
+    }
+  }
+}
+
 // (xcd_place, the XCD-aware order of the workgroups of all three kernels: rpm_device_internal.hpp)
 
 // a wave-uniform field of a tile record staged as ints (in LDS or in the constant address space)
@@ -273,9 +351,7 @@ template <class Prob, int T, bool WG, bool WJ, bool AN, bool DXM = false>
 __global__ void rpm_tile_kernel(const KParams K, const double* __restrict__ xall,
                                 double* __restrict__ gall, double* __restrict__ vall) {
   constexpr int NX = Prob::NX, NU = Prob::NU, NC = Prob::NC, NQ = prob_nq<Prob>::value;
-  constexpr int NO = NX + NC;              // outputs per node: f then c
   constexpr int NV = NX + NU + 1 + NQ;     // perturbation variables: states, controls, time, static parameters
-  constexpr int NB = NX + NU + 2 + NQ;     // Jacobian blocks per output row: x.., u.., t0, tf, p..
   constexpr int R = WJ ? NV + 1 : (NX > 0 ? NX : 1);
   constexpr int NCs = NC > 0 ? NC : 1;
   extern __shared__ double lds[];
@@ -313,17 +389,7 @@ __global__ void rpm_tile_kernel(const KParams K, const double* __restrict__ xall
     }
   }
 
-  // ---- stage X tile, U tile and D rows in LDS (coalesced: every run below is contiguous in HBM) ----
-  for (int q = tid; q < NX * tl.span_len; q += nthr) {
-    const int i = q / tl.span_len, r = q - i * tl.span_len;
-    Xs[i * K.max_span + r] = x[ph.x_state0 + i * (ph.N + 1) + tl.span0 + r];
-  }
-  for (int q = tid; q < NU * tl.cnt; q += nthr) {
-    const int j = q / tl.cnt, r = q - j * tl.cnt;
-    Us[j * T + r] = x[ph.x_control0 + j * ph.N + tl.k0 + r];
-  }
-  if (WG)
-    for (int q = tid; q < tl.drow_len; q += nthr) Ds[q] = K.dvals[tl.drow0 + q];
+  stage_tile_inputs<NX, NU, T, WG>(K, tl, x, tid, nthr, Xs, Us, Ds);
   const double t0 = x[ph.x_t0], tf = x[ph.x_t0 + 1];
   __syncthreads();
 
@@ -409,50 +475,11 @@ __global__ void rpm_tile_kernel(const KParams K, const double* __restrict__ xall
     const int N = ph.N;
     if (WG && sv >= 0 && sv < NX) store_defect<T, true>(sv, DXM ? DXs[sv * T + kk] : dx, tspan, Fb, kk, g, ph.g0, N, k, bad_g);
     if (WJ && role >= 1) {
-      double J[NO];
-#pragma unroll
-      for (int o = 0; o < NO; ++o) {
-        const double pert = o < NX ? f[o < NX ? o : 0] : cp[o >= NX ? o - NX : 0];
-        J[o] = AN ? pert : (pert - Fb[o * T + kk]) / h;
-      }
       double* vb = vals + ph.v_nl0 + k;
-      if (v != NX + NU) {
-        // blocks d/dx_v, d/du_v or d/dp_j of every output row (:698-743, :763-769, :776-796, :814-820; the parameter
-        // blocks follow the two time blocks and take their derivative column, not the time column — SURVEY B-6, B-7)
-        const int bv = v < NX + NU ? v : v + 1;
-#pragma unroll
-        for (int o = 0; o < NO; ++o) {
-          double val;
-          if (o < NX) {
-            const double ret = J[o] * (tf - t0) / 2.0;
-            val = (o == v) ? ddiag - ret : -ret;          // Ddiag - ret on the diagonal block, :712
-          } else {
-            val = J[o];
-          }
-          vb[size_t(o * NB + bv) * N] = val;
-          chk_note(bad_j, val);
-        }
-      } else {
-        // d/dt0 and d/dtf blocks (:748-760, :801-811); B-5 sign of the reference kept
-        const double a0 = -(tau * 0.5) + 0.5, af = (tau * 0.5) + 0.5;
-#pragma unroll
-        for (int o = 0; o < NO; ++o) {
-          double v0, vf;
-          if (o < NX) {
-            const double fb = Fb[o * T + kk];
-            const double dt = J[o] * (tf - t0) / 2.0;
-            v0 = fb * (0.5) - a0 * dt;
-            vf = -fb * (0.5) + af * dt;
-          } else {
-            v0 = a0 * J[o];
-            vf = af * J[o];
-          }
-          vb[size_t(o * NB + NX + NU) * N] = v0;
-          vb[size_t(o * NB + NX + NU + 1) * N] = vf;
-          chk_note(bad_j, v0);
-          chk_note(bad_j, vf);
-        }
-      }
+      jacobian_blocks<Prob, T, AN>(v, h, f, cp, Fb, kk, tau, t0, tf, ddiag, [&](int blk, double val) {
+        vb[size_t(blk) * N] = val;
+        chk_note(bad_j, val);
+      });
     }
   }
   chk_report(K.chk, bad_g, bad_j);
@@ -497,7 +524,7 @@ template <class Prob, int T, int RG, bool WG, bool WJ, bool AN>
 __global__ __launch_bounds__(T* RG) void rpm_tile_rl_kernel(const KParams K, const double* __restrict__ xall,
                                                             double* __restrict__ gall, double* __restrict__ vall) {
   constexpr int NX = Prob::NX, NU = Prob::NU, NC = Prob::NC, NQ = prob_nq<Prob>::value;
-  constexpr int NO = NX + NC, NV = NX + NU + 1 + NQ, NB = NX + NU + 2 + NQ;
+  constexpr int NV = NX + NU + 1 + NQ;
   constexpr int R = WJ ? NV + 1 : (NX > 0 ? NX : 1);
   constexpr int NCs = NC > 0 ? NC : 1;
   constexpr int NTHR = T * RG;
@@ -523,16 +550,7 @@ __global__ __launch_bounds__(T* RG) void rpm_tile_rl_kernel(const KParams K, con
   const double tau = K.points[nidx];
   const NodeDev nd = K.nodes[nidx];
   const double ddiag = WJ ? K.diag[nidx] : 0.0;
-  for (int q = tid; q < NX * tl.span_len; q += NTHR) {
-    const int i = q / tl.span_len, r = q - i * tl.span_len;
-    Xs[i * K.max_span + r] = x[ph.x_state0 + i * (ph.N + 1) + tl.span0 + r];
-  }
-  for (int q = tid; q < NU * tl.cnt; q += NTHR) {
-    const int j = q / tl.cnt, r = q - j * tl.cnt;
-    Us[j * T + r] = x[ph.x_control0 + j * ph.N + tl.k0 + r];
-  }
-  if (WG)
-    for (int q = tid; q < tl.drow_len; q += NTHR) Ds[q] = K.dvals[tl.drow0 + q];
+  stage_tile_inputs<NX, NU, T, WG>(K, tl, x, tid, NTHR, Xs, Us, Ds);
   const double t0 = x[ph.x_t0], tf = x[ph.x_t0 + 1];
   RPM_TRC(1);
   __syncthreads();
@@ -581,44 +599,9 @@ __global__ __launch_bounds__(T* RG) void rpm_tile_rl_kernel(const KParams K, con
     if (act) {
       if (WG && sv >= 0 && sv < NX) store_defect<T, false>(sv, dx, tspan, Fb, kk, g, ph.g0, N, k, no_chk);
       if (WJ && role >= 1) {
-        double J[NO];
-#pragma unroll
-        for (int o = 0; o < NO; ++o) {
-          const double pert = o < NX ? f[o < NX ? o : 0] : cp[o >= NX ? o - NX : 0];
-          J[o] = AN ? pert : (pert - Fb[o * T + kk]) / h;
-        }
         double* vb = vals + ph.v_nl0 + k;
-        if (v != NX + NU) {           // blocks d/dx_v, d/du_v or d/dp_j of every output row (:698-743, :763-769, :776-796, :814-820)
-          const int bv = v < NX + NU ? v : v + 1;
-#pragma unroll
-          for (int o = 0; o < NO; ++o) {
-            double val;
-            if (o < NX) {
-              const double ret = J[o] * (tf - t0) / 2.0;
-              val = (o == v) ? ddiag - ret : -ret;
-            } else {
-              val = J[o];
-            }
-            vb[size_t(o * NB + bv) * N] = val;
-          }
-        } else {                       // d/dt0 and d/dtf blocks (:748-760, :801-811); B-5 sign kept
-          const double a0 = -(tau * 0.5) + 0.5, af = (tau * 0.5) + 0.5;
-#pragma unroll
-          for (int o = 0; o < NO; ++o) {
-            double v0, vf;
-            if (o < NX) {
-              const double fb = Fb[o * T + kk];
-              const double dt = J[o] * (tf - t0) / 2.0;
-              v0 = fb * (0.5) - a0 * dt;
-              vf = -fb * (0.5) + af * dt;
-            } else {
-              v0 = a0 * J[o];
-              vf = af * J[o];
-            }
-            vb[size_t(o * NB + NX + NU) * N] = v0;
-            vb[size_t(o * NB + NX + NU + 1) * N] = vf;
-          }
-        }
+        jacobian_blocks<Prob, T, AN>(v, h, f, cp, Fb, kk, tau, t0, tf, ddiag,
+                                     [&](int blk, double val) { vb[size_t(blk) * N] = val; });
       }
     }
   }
@@ -1135,6 +1118,8 @@ __global__ __launch_bounds__(NH * 64 * (RG + NDMA), 1) void rpm_tile_pl_kernel(
           store_defect<T, false>(sv, dx, tf - t0, Fb, kk, g, g0, N, k, no_chk);
         }
         if (WJ && role >= 1) {
+          // The rule of jacobian_blocks, restated: through the helper the staged quadrotor instantiations (168 VGPRs, the
+          // 1024-instance sweep's kernels) spill 20 instead of 12 bytes per lane.  Keep the two in step.
           double J[NO];
 #pragma unroll
           for (int o = 0; o < NO; ++o) {
@@ -1142,7 +1127,7 @@ __global__ __launch_bounds__(NH * 64 * (RG + NDMA), 1) void rpm_tile_pl_kernel(
             J[o] = AN ? pert : (pert - Fb[o * T + kk]) / h;
           }
           double* __restrict__ vb = vals + v_nl0;   // block bases stay scalar; the node index k is the only per-lane part
-          if (v != NX + NU) {           // blocks d/dx_v, d/du_v or d/dp_j of every output row (:698-743, :763-769, :776-796, :814-820)
+          if (v != NX + NU) {
             const int bv = v < NX + NU ? v : v + 1;
 #pragma unroll
             for (int o = 0; o < NO; ++o) {
@@ -1155,7 +1140,7 @@ __global__ __launch_bounds__(NH * 64 * (RG + NDMA), 1) void rpm_tile_pl_kernel(
               }
               pl_store<pl_jac_policy(JP)>(vb + size_t(o * NB + bv) * N + k, val);
             }
-          } else {                       // d/dt0 and d/dtf blocks (:748-760, :801-811); B-5 sign kept
+          } else {
             const double a0 = -(tau * 0.5) + 0.5, af = (tau * 0.5) + 0.5;
 #pragma unroll
             for (int o = 0; o < NO; ++o) {

@@ -19,6 +19,8 @@ from oracle import oracle as orc
 G_TOL, JFD_TOL = 1e-12, 1e-8
 PROBLEMS = [("param_sled", lambda: problems.param_sled(4, 8)), ("param_oscillator", lambda: problems.param_oscillator()),
             ("param_oscillator_ragged", lambda: _ragged())]
+# phase 1 has 70 nodes: one full 64-node tile and a partial one (the layouts' comparison; the other problems fit one tile)
+TWO_TILES = ("param_oscillator_70", lambda: problems.param_oscillator((5, 3), (14, 9)))
 
 
 def _ragged():
@@ -153,7 +155,7 @@ def test_gpu_callbacks_against_the_oracle(built, name, make, tile):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("name,make", PROBLEMS[1:], ids=[p[0] for p in PROBLEMS[1:]])
+@pytest.mark.parametrize("name,make", PROBLEMS[1:] + [TWO_TILES], ids=[p[0] for p in PROBLEMS[1:] + [TWO_TILES]])
 def test_gpu_layouts_batches_and_sharding_are_bit_identical(built, name, make):
     import torch
     from lpopc_amd.group import EngineGroup
