@@ -242,55 +242,33 @@ struct CarryState {
   HostForm sample;  // host-pointer form of the sampler: the times and the samples in one block
 };
 
-size_t carry_budget(const Engine& from) {
-  return from.opt_carry_lds > 0 ? std::min(size_t(from.opt_carry_lds), kCuLdsBytes) : kCuLdsBytes;
-}
-
 // Host planner: instances per workgroup and the split of every phase's columns over workgroups.  Columns are independent,
 // so a phase whose columns do not fit one workgroup's LDS is dealt over several; the tile shrinks before one column is refused.
 bool carry_plan(const Engine& from, int mult, int* TB_out, std::vector<CarryGroup>* groups, size_t* lds_out) {
-  const size_t budget = carry_budget(from) / sizeof(double);
+  const size_t budget = lds_budget(from.opt_carry_lds, kCuLdsBytes) / sizeof(double);
+  auto fits = [&](const PhaseHost& p, int TB, int ncols) { return size_t(CarryLds(p.N + 1, TB, ncols).total) <= budget; };
   // automatic: 2 instances per workgroup (reasoned; tools/bench_sweep_carry.py measures every value)
-  int TB = clamp_tile(from.opt_carry_tile > 0 ? from.opt_carry_tile : 2, from.n_instances);
-  for (;; TB >>= 1) {
-    bool fits = true;
-    for (const PhaseHost& p : from.ph) fits = fits && size_t(CarryLds(p.N + 1, TB, 1).total) <= budget;
-    if (fits) break;
-    if (TB == 1) return false;
-  }
+  const int TB = halve_tile(clamp_tile(from.opt_carry_tile > 0 ? from.opt_carry_tile : 2, from.n_instances), [&](int tb) {
+    return std::all_of(from.ph.begin(), from.ph.end(), [&](const PhaseHost& p) { return fits(p, tb, 1); });
+  });
+  if (!TB) return false;
   size_t lds = 0;
   if (groups) groups->clear();
   for (size_t ip = 0; ip < from.ph.size(); ++ip) {
     const PhaseHost& p = from.ph[ip];
-    const int cols = p.nx + (mult ? p.nc : p.nu);
-    int most = 1;   // the most columns that fit next to the per-instance rows
-    while (most < cols && size_t(CarryLds(p.N + 1, TB, most + 1).total) <= budget) ++most;
-    const auto [n_groups, per] = deal_columns(cols, most);
-    for (int g = 0, col0 = 0; g < n_groups; ++g, col0 += per) {
-      const CarryGroup cg{int(ip), col0, std::min(per, cols - col0), g == 0 ? 1 : 0};
-      lds = std::max(lds, size_t(CarryLds(p.N + 1, TB, cg.ncols).total) * sizeof(double));
-      if (groups) groups->push_back(cg);
+    for (const auto& [col0, ncols] : split_columns(p.nx + (mult ? p.nc : p.nu), [&](int nc) { return fits(p, TB, nc); })) {
+      lds = std::max(lds, size_t(CarryLds(p.N + 1, TB, ncols).total) * sizeof(double));
+      if (groups) groups->push_back(CarryGroup{int(ip), col0, ncols, col0 == 0 ? 1 : 0});
     }
   }
   *TB_out = TB;
   *lds_out = lds;
   return true;
 }
-
-int carry_devices(Engine& from, Engine& to) {
-  int id = from.dev ? from.dev->device_id : (to.dev ? to.dev->device_id : 0);
-  if (!from.dev) {
-    const int rc = device_init(from, id);
-    if (rc) return rc;
-  }
-  if (!to.dev) {
-    const int rc = device_init(to, id);
-    if (rc) {
-      from.err = to.err;
-      return rc;
-    }
-  }
-  return RPM_OK;
+bool carry_fits(const Engine& e, int mult) {
+  int TB = 0;
+  size_t lds = 0;
+  return carry_plan(e, mult, &TB, nullptr, &lds);
 }
 
 CarryState& carry_state(Device& d) {
@@ -299,11 +277,9 @@ CarryState& carry_state(Device& d) {
 }
 
 // The launch plan of a pair of engines under from's options, made on the first call: the only allocation and the only blocking
-// copy.  Makes from's device current.
+// copy.  from's device is current (dev_bind).
 int carry_plan_for(Engine& from, const Engine& to, int mult, const std::string& who, const CarryPlan** out) {
-  Device& d = *from.dev;
-  HIP_TRY(from, hipSetDevice(d.device_id));
-  CarryState& cs = carry_state(d);
+  CarryState& cs = carry_state(*from.dev);
   for (const CarryPlan& p : cs.plans)
     if (p.to_serial == to.serial && p.tile_opt == from.opt_carry_tile && p.lds_opt == from.opt_carry_lds && p.mult == mult) {
       *out = &p;
@@ -311,10 +287,7 @@ int carry_plan_for(Engine& from, const Engine& to, int mult, const std::string& 
     }
   CarryPlan p;
   std::vector<CarryGroup> groups;
-  if (!carry_plan(from, mult, &p.TB, &groups, &p.lds)) {
-    from.err = who + ": a column does not fit one workgroup's LDS";
-    return RPM_E_UNSUPPORTED;
-  }
+  if (!carry_plan(from, mult, &p.TB, &groups, &p.lds)) return step_fail(from, RPM_E_UNSUPPORTED, who + ": a column does not fit one workgroup's LDS");
   p.mult = mult;
   p.to_serial = to.serial;
   p.tile_opt = from.opt_carry_tile;
@@ -335,7 +308,7 @@ int carry_plan_for(Engine& from, const Engine& to, int mult, const std::string& 
 // sh.dt not NULL: the shift of a plan (from == to); sh.z_from not NULL: a bound-multiplier array z_from -> x_to.
 int carry_launch(Engine& from, Engine& to, const double* d_x_from, double* d_x_to, const double* d_lam_from, double* d_lam_to,
                  int* d_nonfinite, hipStream_t st, CarryShift sh = CarryShift{}) {
-  const std::string who = sh.dt ? "shift_plan_batch" : (d_lam_from ? "carry_multipliers_batch" : "carry_solution_batch");
+  const char* who = sh.dt ? "shift_plan_batch" : (d_lam_from ? "carry_multipliers_batch" : "carry_solution_batch");
   const int mult = d_lam_from ? 1 : 0;
   const CarryPlan* plan = nullptr;
   const int rc = carry_plan_for(from, to, mult, who, &plan);
@@ -348,17 +321,7 @@ int carry_launch(Engine& from, Engine& to, const double* d_x_from, double* d_x_t
                      d.d_phases, d.d_points, from.n, to.dev->d_phases, to.dev->d_points, to.n, plan->d_groups, B, plan->TB, d_x_from,
                      d_x_to, cm, sh);
   if (d_nonfinite) flag_launch(mult ? to.m : to.n, mult ? d_lam_to : d_x_to, d_nonfinite, B, st);
-  const hipError_t s = hipGetLastError();
-  if (s != hipSuccess) {
-    from.err = who + " launch: " + hipGetErrorString(s);
-    return RPM_E_DEVICE;
-  }
-  return RPM_OK;
-}
-
-int carry_fail(Engine& e, int code, const std::string& msg) {
-  e.err = msg;
-  return code;
+  return step_launched(from, who);
 }
 
 }  // namespace
@@ -389,35 +352,26 @@ int carry_check(Engine& from, const Engine& to, const void* x_from, const void* 
   for (int i = 0; i < std::min(from.P, to.P); ++i) {   // the sizes first: they say more than "another problem"
     const PhaseHost &a = from.ph[size_t(i)], &b = to.ph[size_t(i)];
     const std::string tag = " differs in phase " + std::to_string(i + 1);
-    if (a.nx != b.nx) return carry_fail(from, RPM_E_INVALID, who + "nx" + tag);
-    if (a.nu != b.nu) return carry_fail(from, RPM_E_INVALID, who + "nu" + tag);
-    if (a.nq != b.nq) return carry_fail(from, RPM_E_INVALID, who + "nq" + tag);
-    if (mult && a.nc != b.nc) return carry_fail(from, RPM_E_INVALID, who + "nc" + tag);
-    if (mult && a.ne != b.ne) return carry_fail(from, RPM_E_INVALID, who + "ne" + tag);
+    if (a.nx != b.nx) return step_fail(from, RPM_E_INVALID, who + "nx" + tag);
+    if (a.nu != b.nu) return step_fail(from, RPM_E_INVALID, who + "nu" + tag);
+    if (a.nq != b.nq) return step_fail(from, RPM_E_INVALID, who + "nq" + tag);
+    if (mult && a.nc != b.nc) return step_fail(from, RPM_E_INVALID, who + "nc" + tag);
+    if (mult && a.ne != b.ne) return step_fail(from, RPM_E_INVALID, who + "ne" + tag);
   }
-  if (from.P != to.P) return carry_fail(from, RPM_E_INVALID, who + "the engines have different phase counts");
-  if (from.problem_id != to.problem_id) return carry_fail(from, RPM_E_INVALID, who + "the engines hold different problems");
+  if (from.P != to.P) return step_fail(from, RPM_E_INVALID, who + "the engines have different phase counts");
+  if (from.problem_id != to.problem_id) return step_fail(from, RPM_E_INVALID, who + "the engines hold different problems");
   if (from.n_instances != to.n_instances)
-    return carry_fail(from, RPM_E_INVALID, who + "n_instances differs (" + std::to_string(from.n_instances) + " and " +
+    return step_fail(from, RPM_E_INVALID, who + "n_instances differs (" + std::to_string(from.n_instances) + " and " +
                                                std::to_string(to.n_instances) + ")");
   if (from.dev && to.dev && from.dev->device_id != to.dev->device_id)
-    return carry_fail(from, RPM_E_INVALID, who + "the engines are bound to different devices");
-  const char* a = static_cast<const char*>(x_from);
-  const char* b = static_cast<const char*>(x_to);
-  const size_t na = size_t(from.n_instances) * (mult ? from.m : from.n) * sizeof(double);
-  const size_t nb = size_t(to.n_instances) * (mult ? to.m : to.n) * sizeof(double);
-  if (a < b + nb && b < a + na)
-    return carry_fail(from, RPM_E_INVALID, who + (mult ? "lambda_from and lambda_to overlap" : "x_from and x_to overlap"));
+    return step_fail(from, RPM_E_INVALID, who + "the engines are bound to different devices");
+  const size_t B = size_t(from.n_instances) * sizeof(double);   // two ranges, named in the arguments' order
+  const ByteRange a{mult ? "lambda_from" : "x_from", x_from, B * (mult ? from.m : from.n)}, b{mult ? "lambda_to" : "x_to", x_to, B * (mult ? to.m : to.n)};
+  if (const int rc = step_overlap(from, who, &a, 1, &b, 1)) return rc;
   if (mult && from.P > 0 && from.m - carry_rows(from, from.P - 1).end != to.m - carry_rows(to, to.P - 1).end)
-    return carry_fail(from, RPM_E_INVALID, who + "the rows after the last phase differ in number");
-  if (sharded(from) || sharded(to)) return carry_fail(from, RPM_E_UNSUPPORTED, who + "not with interval sharding");
-  int TB = 0;
-  size_t lds = 0;
-  if (!carry_plan(from, mult, &TB, nullptr, &lds)) {
-    int most = 0;
-    for (const PhaseHost& p : from.ph) most = std::max(most, p.N + 1);
-    return carry_fail(from, RPM_E_UNSUPPORTED, who + "a column of " + std::to_string(most) + " knots does not fit one workgroup's LDS");
-  }
+    return step_fail(from, RPM_E_INVALID, who + "the rows after the last phase differ in number");
+  if (sharded(from) || sharded(to)) return step_fail(from, RPM_E_UNSUPPORTED, who + "not with interval sharding");
+  if (!carry_fits(from, mult)) return step_no_fit(from, who, "knots", 1);
   return RPM_OK;
 }
 
@@ -426,7 +380,7 @@ int dev_carry_batch(Engine& from, Engine& to, const double* d_x_from, double* d_
   int rc = carry_check(from, to, d_x_from, d_x_to);
   if (rc) return rc;
   DeviceRestore restore;
-  rc = carry_devices(from, to);
+  rc = dev_bind(from, &to);
   if (rc) return rc;
   return carry_launch(from, to, d_x_from, d_x_to, nullptr, nullptr, d_nonfinite, static_cast<hipStream_t>(stream));
 }
@@ -435,54 +389,37 @@ int dev_carry_mult_batch(Engine& from, Engine& to, const double* d_x_from, const
   int rc = carry_check(from, to, d_lam_from, d_lam_to, 1);
   if (rc) return rc;
   DeviceRestore restore;
-  rc = carry_devices(from, to);
+  rc = dev_bind(from, &to);
   if (rc) return rc;
   return carry_launch(from, to, d_x_from, nullptr, d_lam_from, d_lam_to, d_nonfinite, static_cast<hipStream_t>(stream));
 }
 
-// the same through host arrays: x_from up through the staging slot, the carried block and the verdicts back; blocking
+// the same through host arrays: x_from (and lam_from) up through the staging slots, the carried block and the verdicts back; blocking
 int host_carry_batch(Engine& from, Engine& to, const double* x_from, double* x_to, int* nonfinite) {
   int rc = carry_check(from, to, x_from, x_to);
   if (rc) return rc;
   DeviceRestore restore;
-  rc = carry_devices(from, to);
+  rc = dev_bind(from, &to);
   if (rc) return rc;
   Device& d = *from.dev;
-  HIP_TRY(from, hipSetDevice(d.device_id));
-  CarryState& cs = carry_state(d);
   const size_t B = size_t(from.n_instances), count = B * to.n;
-  rc = cs.host.ensure(from, count, B);
-  if (rc) return rc;
-  host_new_x(from);   // d_x is about to hold other values than the callbacks' last x
-  rc = dev_upload(from, d.d_x, x_from, B * from.n, STAGE_X);
-  if (rc) return rc;
-  rc = carry_launch(from, to, d.d_x, cs.host.out, nullptr, nullptr, nonfinite ? cs.host.flags : nullptr, d.stream);
-  if (rc == RPM_OK) rc = cs.host.fetch(from, nonfinite, B);
-  if (rc == RPM_OK) rc = dev_download(from, x_to, cs.host.out, count, STAGE_G);
-  if (rc) return rc;
-  return cs.host.finish(from, nonfinite, B);
+  return carry_state(d).host.run(
+      from, count, {{d.d_x, 0, x_from, B * from.n, STAGE_X}},
+      [&](double* out, int* flags) { return carry_launch(from, to, d.d_x, out, nullptr, nullptr, flags, d.stream); },
+      {{x_to, nullptr, 0, count, STAGE_G}}, nonfinite);
 }
 int host_carry_mult_batch(Engine& from, Engine& to, const double* x_from, const double* lam_from, double* lam_to, int* nonfinite) {
   int rc = carry_check(from, to, lam_from, lam_to, 1);
   if (rc) return rc;
   DeviceRestore restore;
-  rc = carry_devices(from, to);
+  rc = dev_bind(from, &to);
   if (rc) return rc;
   Device& d = *from.dev;
-  HIP_TRY(from, hipSetDevice(d.device_id));
-  CarryState& cs = carry_state(d);
   const size_t B = size_t(from.n_instances), count = B * to.m;
-  rc = cs.host.ensure(from, count, B);
-  if (rc) return rc;
-  host_new_x(from);   // d_x is about to hold other values than the callbacks' last x
-  rc = dev_upload(from, d.d_x, x_from, B * from.n, STAGE_X);
-  if (rc == RPM_OK) rc = dev_upload(from, d.d_lambda, lam_from, B * from.m, STAGE_LAMBDA);
-  if (rc) return rc;
-  rc = carry_launch(from, to, d.d_x, nullptr, d.d_lambda, cs.host.out, nonfinite ? cs.host.flags : nullptr, d.stream);
-  if (rc == RPM_OK) rc = cs.host.fetch(from, nonfinite, B);
-  if (rc == RPM_OK) rc = dev_download(from, lam_to, cs.host.out, count, STAGE_G);
-  if (rc) return rc;
-  return cs.host.finish(from, nonfinite, B);
+  return carry_state(d).host.run(
+      from, count, {{d.d_x, 0, x_from, B * from.n, STAGE_X}, {d.d_lambda, 0, lam_from, B * from.m, STAGE_LAMBDA}},
+      [&](double* out, int* flags) { return carry_launch(from, to, d.d_x, nullptr, d.d_lambda, out, flags, d.stream); },
+      {{lam_to, nullptr, 0, count, STAGE_G}}, nonfinite);
 }
 
 // ---- the receding-horizon shift of a plan: the carry onto the engine's own mesh, every point moved by the instance's dt ----
@@ -506,36 +443,18 @@ __global__ void __launch_bounds__(256) rpm_shift_flag_kernel(ShiftFlagged f, int
 // every argument error of the shift, decided on the host before a device is touched (all host or all device pointers)
 int shift_check(Engine& e, const ShiftArrays& a) {
   const std::string who = "shift_plan_batch: ";
-  if (!a.dt) return carry_fail(e, RPM_E_INVALID, who + "dt is NULL");
-  if (!a.x) return carry_fail(e, RPM_E_INVALID, who + "x is NULL");
-  if (!a.x_out) return carry_fail(e, RPM_E_INVALID, who + "x_out is NULL");
-  if (!a.lambda != !a.lambda_out) return carry_fail(e, RPM_E_INVALID, who + "lambda and lambda_out are given together or both NULL");
+  if (!a.dt) return step_fail(e, RPM_E_INVALID, who + "dt is NULL");
+  if (!a.x) return step_fail(e, RPM_E_INVALID, who + "x is NULL");
+  if (!a.x_out) return step_fail(e, RPM_E_INVALID, who + "x_out is NULL");
+  if (!a.lambda != !a.lambda_out) return step_fail(e, RPM_E_INVALID, who + "lambda and lambda_out are given together or both NULL");
   if (!a.z_L != !a.z_U || !a.z_L != !a.z_L_out || !a.z_L != !a.z_U_out)
-    return carry_fail(e, RPM_E_INVALID, who + "z_L, z_U, z_L_out and z_U_out are given together or all NULL");
+    return step_fail(e, RPM_E_INVALID, who + "z_L, z_U, z_L_out and z_U_out are given together or all NULL");
   const size_t B = size_t(e.n_instances), Bn = B * e.n * sizeof(double), Bm = B * e.m * sizeof(double);
-  struct Range { const char* name; const void* p; size_t bytes; };
-  const Range in[5] = {{"dt", a.dt, B * e.P * sizeof(double)}, {"x", a.x, Bn}, {"lambda", a.lambda, Bm}, {"z_L", a.z_L, Bn}, {"z_U", a.z_U, Bn}};
-  const Range out[4] = {{"x_out", a.x_out, Bn}, {"lambda_out", a.lambda_out, Bm}, {"z_L_out", a.z_L_out, Bn}, {"z_U_out", a.z_U_out, Bn}};
-  auto overlap = [](const Range& u, const Range& v) {
-    const char *p = static_cast<const char*>(u.p), *q = static_cast<const char*>(v.p);
-    return p && q && u.bytes && v.bytes && p < q + v.bytes && q < p + u.bytes;
-  };
-  for (int o = 0; o < 4; ++o) {
-    for (const Range& r : in)
-      if (overlap(out[o], r)) return carry_fail(e, RPM_E_INVALID, who + out[o].name + " and " + r.name + " overlap");
-    for (int o2 = o + 1; o2 < 4; ++o2)
-      if (overlap(out[o], out[o2])) return carry_fail(e, RPM_E_INVALID, who + out[o].name + " and " + out[o2].name + " overlap");
-  }
-  if (sharded(e)) return carry_fail(e, RPM_E_UNSUPPORTED, who + "not with interval sharding");
-  for (int mult = 0; mult < (a.lambda ? 2 : 1); ++mult) {
-    int TB = 0;
-    size_t lds = 0;
-    if (!carry_plan(e, mult, &TB, nullptr, &lds)) {
-      int most = 0;
-      for (const PhaseHost& p : e.ph) most = std::max(most, p.N + 1);
-      return carry_fail(e, RPM_E_UNSUPPORTED, who + "a column of " + std::to_string(most) + " knots does not fit one workgroup's LDS");
-    }
-  }
+  const ByteRange in[5] = {{"dt", a.dt, B * e.P * sizeof(double)}, {"x", a.x, Bn}, {"lambda", a.lambda, Bm}, {"z_L", a.z_L, Bn}, {"z_U", a.z_U, Bn}};
+  const ByteRange out[4] = {{"x_out", a.x_out, Bn}, {"lambda_out", a.lambda_out, Bm}, {"z_L_out", a.z_L_out, Bn}, {"z_U_out", a.z_U_out, Bn}};
+  if (const int rc = step_overlap(e, who, out, 4, in, 5)) return rc;
+  if (sharded(e)) return step_fail(e, RPM_E_UNSUPPORTED, who + "not with interval sharding");
+  if (!carry_fits(e, 0) || (a.lambda && !carry_fits(e, 1))) return step_no_fit(e, who, "knots", 1);
   return RPM_OK;
 }
 
@@ -550,9 +469,7 @@ int shift_launch(Engine& e, const ShiftArrays& a, int* d_nonfinite, hipStream_t 
   if (rc || !d_nonfinite) return rc;
   const ShiftFlagged f{{a.x_out, a.lambda_out, a.z_L_out, a.z_U_out}, {e.n, e.m, e.n, e.n}};
   hipLaunchKernelGGL(rpm_shift_flag_kernel, dim3(unsigned(e.n_instances)), dim3(256), 0, st, f, d_nonfinite);
-  const hipError_t s = hipGetLastError();
-  if (s != hipSuccess) return carry_fail(e, RPM_E_DEVICE, std::string("shift_plan_batch launch: ") + hipGetErrorString(s));
-  return RPM_OK;
+  return step_launched(e, "shift_plan_batch");
 }
 }  // namespace
 
@@ -561,7 +478,7 @@ int dev_shift_plan_batch(Engine& e, const ShiftArrays& a, int* d_nonfinite, void
   int rc = shift_check(e, a);
   if (rc) return rc;
   DeviceRestore restore;
-  rc = carry_devices(e, e);
+  rc = dev_bind(e);
   if (rc) return rc;
   return shift_launch(e, a, d_nonfinite, static_cast<hipStream_t>(stream));
 }
@@ -571,34 +488,25 @@ int host_shift_plan_batch(Engine& e, const ShiftArrays& a, int* nonfinite) {
   int rc = shift_check(e, a);
   if (rc) return rc;
   DeviceRestore restore;
-  rc = carry_devices(e, e);
+  rc = dev_bind(e);
   if (rc) return rc;
-  Device& d = *e.dev;
-  HIP_TRY(e, hipSetDevice(d.device_id));
-  CarryState& cs = carry_state(d);
   const size_t B = size_t(e.n_instances), Bp = B * e.P, Bn = B * e.n, Bm = B * e.m;
-  rc = cs.shift.ensure(e, Bp + 6 * Bn + 2 * Bm, B);
-  if (rc) return rc;
-  double* base = cs.shift.out;
-  ShiftArrays dv{};
-  double *d_dt = base, *d_x = d_dt + Bp, *d_lam = d_x + Bn, *d_zl = d_lam + Bm, *d_zu = d_zl + Bn;
-  dv.dt = d_dt; dv.x = d_x; dv.x_out = d_zu + Bn;
-  if (a.lambda) { dv.lambda = d_lam; dv.lambda_out = dv.x_out + Bn; }
-  if (a.z_L) { dv.z_L = d_zl; dv.z_U = d_zu; dv.z_L_out = dv.x_out + Bn + Bm; dv.z_U_out = dv.z_L_out + Bn; }
-  rc = dev_upload(e, d_dt, a.dt, Bp, STAGE_V);
-  if (rc == RPM_OK) rc = dev_upload(e, d_x, a.x, Bn, STAGE_X);
-  if (rc == RPM_OK && a.lambda) rc = dev_upload(e, d_lam, a.lambda, Bm, STAGE_LAMBDA);
-  if (rc == RPM_OK && a.z_L) rc = dev_upload(e, d_zl, a.z_L, Bn, STAGE_G);
-  if (rc == RPM_OK && a.z_L) rc = dev_upload(e, d_zu, a.z_U, Bn, STAGE_GRAD);
-  if (rc) return rc;
-  rc = shift_launch(e, dv, nonfinite ? cs.shift.flags : nullptr, d.stream);
-  if (rc == RPM_OK) rc = cs.shift.fetch(e, nonfinite, B);
-  if (rc == RPM_OK) rc = dev_download(e, a.x_out, dv.x_out, Bn, STAGE_X);
-  if (rc == RPM_OK && a.lambda) rc = dev_download(e, a.lambda_out, dv.lambda_out, Bm, STAGE_LAMBDA);
-  if (rc == RPM_OK && a.z_L) rc = dev_download(e, a.z_L_out, dv.z_L_out, Bn, STAGE_G);
-  if (rc == RPM_OK && a.z_L) rc = dev_download(e, a.z_U_out, dv.z_U_out, Bn, STAGE_GRAD);
-  if (rc) return rc;
-  return cs.shift.finish(e, nonfinite, B);
+  // the block: dt, x, lambda, z_L, z_U, then x_out, lambda_out, z_L_out, z_U_out
+  const size_t o_x = Bp, o_lam = o_x + Bn, o_zl = o_lam + Bm, o_zu = o_zl + Bn, o_xo = o_zu + Bn, o_lo = o_xo + Bn, o_zlo = o_lo + Bm,
+               o_zuo = o_zlo + Bn;
+  return carry_state(*e.dev).shift.run(
+      e, o_zuo + Bn,
+      {{nullptr, 0, a.dt, Bp, STAGE_V}, {nullptr, o_x, a.x, Bn, STAGE_X}, {nullptr, o_lam, a.lambda, Bm, STAGE_LAMBDA},
+       {nullptr, o_zl, a.z_L, Bn, STAGE_G}, {nullptr, o_zu, a.z_U, Bn, STAGE_GRAD}},
+      [&](double* b, int* flags) {
+        auto at = [&](const double* given, size_t off) { return given ? b + off : nullptr; };
+        const ShiftArrays dv{b, b + o_x, b + o_xo, at(a.lambda, o_lam), at(a.lambda, o_lo), at(a.z_L, o_zl), at(a.z_L, o_zu),
+                             at(a.z_L, o_zlo), at(a.z_L, o_zuo)};
+        return shift_launch(e, dv, flags, e.dev->stream);
+      },
+      {{a.x_out, nullptr, o_xo, Bn, STAGE_X}, {a.lambda_out, nullptr, o_lo, Bm, STAGE_LAMBDA}, {a.z_L_out, nullptr, o_zlo, Bn, STAGE_G},
+       {a.z_U_out, nullptr, o_zuo, Bn, STAGE_GRAD}},
+      nonfinite);
 }
 
 // ---- the plans sampled at caller-given times: one phase's columns through rpm_sample_kernel ------------------------------
@@ -606,28 +514,18 @@ int host_shift_plan_batch(Engine& e, const ShiftArrays& a, int* nonfinite) {
 // every argument error of the sampler, decided on the host before a device is touched (all host or all device pointers)
 int sample_check(Engine& e, int phase, const void* x, int n_times, const void* times, const void* out) {
   const std::string who = "sample_plan_batch: ";
-  if (!x) return carry_fail(e, RPM_E_INVALID, who + "x is NULL");
-  if (!times) return carry_fail(e, RPM_E_INVALID, who + "times is NULL");
-  if (!out) return carry_fail(e, RPM_E_INVALID, who + "out is NULL");
-  if (n_times < 1) return carry_fail(e, RPM_E_INVALID, who + "n_times must be at least 1");
-  if (phase < 0 || phase >= e.P) return carry_fail(e, RPM_E_INVALID, who + "the phase index is out of range");
+  if (!x) return step_fail(e, RPM_E_INVALID, who + "x is NULL");
+  if (!times) return step_fail(e, RPM_E_INVALID, who + "times is NULL");
+  if (!out) return step_fail(e, RPM_E_INVALID, who + "out is NULL");
+  if (n_times < 1) return step_fail(e, RPM_E_INVALID, who + "n_times must be at least 1");
+  if (phase < 0 || phase >= e.P) return step_fail(e, RPM_E_INVALID, who + "the phase index is out of range");
   const PhaseHost& p = e.ph[size_t(phase)];
   const size_t B = size_t(e.n_instances), bytes_x = B * e.n * sizeof(double), bytes_t = B * size_t(n_times) * sizeof(double),
                bytes_o = bytes_t * size_t(p.nx + p.nu);
-  auto overlap = [](const void* u, size_t nu, const void* v, size_t nv) {
-    const char *a = static_cast<const char*>(u), *b = static_cast<const char*>(v);
-    return nu && nv && a < b + nv && b < a + nu;
-  };
-  if (overlap(out, bytes_o, x, bytes_x)) return carry_fail(e, RPM_E_INVALID, who + "out and x overlap");
-  if (overlap(out, bytes_o, times, bytes_t)) return carry_fail(e, RPM_E_INVALID, who + "out and times overlap");
-  if (sharded(e)) return carry_fail(e, RPM_E_UNSUPPORTED, who + "not with interval sharding");
-  int TB = 0;
-  size_t lds = 0;
-  if (!carry_plan(e, 0, &TB, nullptr, &lds)) {
-    int most = 0;
-    for (const PhaseHost& q : e.ph) most = std::max(most, q.N + 1);
-    return carry_fail(e, RPM_E_UNSUPPORTED, who + "a column of " + std::to_string(most) + " knots does not fit one workgroup's LDS");
-  }
+  const ByteRange o{"out", out, bytes_o}, in[2] = {{"x", x, bytes_x}, {"times", times, bytes_t}};
+  if (const int rc = step_overlap(e, who, &o, 1, in, 2)) return rc;
+  if (sharded(e)) return step_fail(e, RPM_E_UNSUPPORTED, who + "not with interval sharding");
+  if (!carry_fits(e, 0)) return step_no_fit(e, who, "knots", 1);
   return RPM_OK;
 }
 
@@ -643,9 +541,7 @@ int sample_launch(Engine& e, int phase, const double* d_x, int n_times, const do
   hipLaunchKernelGGL(rpm_sample_kernel, dim3(unsigned(ng), unsigned((B + plan->TB - 1) / plan->TB)), dim3(256), plan->lds, st, d.d_phases,
                      d.d_points, e.n, plan->d_groups + g0, B, plan->TB, d_x, n_times, d_times, d_out);
   if (d_nonfinite) flag_launch((long long)(p.nx + p.nu) * n_times, d_out, d_nonfinite, B, st);
-  const hipError_t s = hipGetLastError();
-  if (s != hipSuccess) return carry_fail(e, RPM_E_DEVICE, std::string("sample_plan_batch launch: ") + hipGetErrorString(s));
-  return RPM_OK;
+  return step_launched(e, "sample_plan_batch");
 }
 }  // namespace
 
@@ -655,7 +551,7 @@ int dev_sample_plan_batch(Engine& e, int phase, const double* d_x, int n_times, 
   int rc = sample_check(e, phase, d_x, n_times, d_times, d_out);
   if (rc) return rc;
   DeviceRestore restore;
-  rc = carry_devices(e, e);
+  rc = dev_bind(e);
   if (rc) return rc;
   return sample_launch(e, phase, d_x, n_times, d_times, d_out, d_nonfinite, static_cast<hipStream_t>(stream));
 }
@@ -665,25 +561,15 @@ int host_sample_plan_batch(Engine& e, int phase, const double* x, int n_times, c
   int rc = sample_check(e, phase, x, n_times, times, out);
   if (rc) return rc;
   DeviceRestore restore;
-  rc = carry_devices(e, e);
+  rc = dev_bind(e);
   if (rc) return rc;
   Device& d = *e.dev;
-  HIP_TRY(e, hipSetDevice(d.device_id));
-  CarryState& cs = carry_state(d);
   const PhaseHost& p = e.ph[size_t(phase)];
-  const size_t B = size_t(e.n_instances), Bt = B * size_t(n_times), Bo = Bt * size_t(p.nx + p.nu);
-  rc = cs.sample.ensure(e, Bt + Bo, B);
-  if (rc) return rc;
-  double *d_times = cs.sample.out, *d_out = d_times + Bt;
-  host_new_x(e);   // d_x is about to hold other values than the callbacks' last x
-  rc = dev_upload(e, d.d_x, x, B * e.n, STAGE_X);
-  if (rc == RPM_OK) rc = dev_upload(e, d_times, times, Bt, STAGE_V);
-  if (rc) return rc;
-  rc = sample_launch(e, phase, d.d_x, n_times, d_times, d_out, nonfinite ? cs.sample.flags : nullptr, d.stream);
-  if (rc == RPM_OK) rc = cs.sample.fetch(e, nonfinite, B);
-  if (rc == RPM_OK) rc = dev_download(e, out, d_out, Bo, STAGE_G);
-  if (rc) return rc;
-  return cs.sample.finish(e, nonfinite, B);
+  const size_t B = size_t(e.n_instances), Bt = B * size_t(n_times), Bo = Bt * size_t(p.nx + p.nu);   // the block: the times, the samples
+  return carry_state(d).sample.run(
+      e, Bt + Bo, {{d.d_x, 0, x, B * e.n, STAGE_X}, {nullptr, 0, times, Bt, STAGE_V}},
+      [&](double* b, int* flags) { return sample_launch(e, phase, d.d_x, n_times, b, b + Bt, flags, d.stream); },
+      {{out, nullptr, Bt, Bo, STAGE_G}}, nonfinite);
 }
 
 // the row map of the multiplier carry on the host: phase < P: {first defect row, first path row, first event row, one past the

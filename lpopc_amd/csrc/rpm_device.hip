@@ -540,10 +540,15 @@ int dev_stage_download(Engine& e, int slot, double* host, const double* dev, siz
 }
 
 // ---- small helpers used by the C ABI (rpm_abi.cpp) ---------------------------------------------
-int dev_bind(Engine& e) {
+int dev_bind(Engine& e, Engine* to) {
+  const int id = e.dev ? e.dev->device_id : (to && to->dev ? to->dev->device_id : 0);
   if (!e.dev) {
-    int rc = device_init(e, 0);
+    int rc = device_init(e, id);
     if (rc) return rc;
+  }
+  if (to && !to->dev) {
+    int rc = device_init(*to, id);
+    if (rc) return step_fail(e, rc, to->err);
   }
   HIP_TRY(e, hipSetDevice(e.dev->device_id));
   return RPM_OK;
@@ -617,6 +622,43 @@ void HostForm::release() {
   if (flags) (void)hipFree(flags);
   if (h_flags) (void)hipHostFree(h_flags);
   *this = HostForm{};
+}
+int HostForm::run(Engine& e, size_t doubles, std::initializer_list<Up> ups, const std::function<int(double* block, int* flags)>& launch,
+                  std::initializer_list<Down> downs, int* nonfinite) {
+  const size_t B = size_t(e.n_instances);
+  int rc = ensure(e, doubles, B);
+  for (const Up& u : ups) {
+    if (rc || !u.host) continue;
+    if (u.dev == e.dev->d_x) host_new_x(e);   // d_x is about to hold other values than the callbacks' last x
+    rc = dev_upload(e, (u.dev ? u.dev : out) + u.off, u.host, u.count, u.slot);
+  }
+  if (rc == RPM_OK) rc = launch(out, nonfinite ? flags : nullptr);
+  if (rc == RPM_OK) rc = fetch(e, nonfinite, B);
+  for (const Down& w : downs)
+    if (rc == RPM_OK && w.host) rc = dev_download(e, w.host, (w.dev ? w.dev : out) + w.off, w.count, w.slot);
+  return rc ? rc : finish(e, nonfinite, B);
+}
+
+int step_fail(Engine& e, int code, const std::string& msg) {
+  e.err = msg;
+  return code;
+}
+int step_launched(Engine& e, const char* step, hipError_t before) {
+  const hipError_t s = before != hipSuccess ? before : hipGetLastError();
+  return s == hipSuccess ? RPM_OK : step_fail(e, RPM_E_DEVICE, std::string(step) + " launch: " + hipGetErrorString(s));
+}
+int step_no_kernels(Engine& e, const char* step) {
+  return step_fail(e, RPM_E_UNSUPPORTED, std::string(step) + ": this library has no kernels for the engine's problem");
+}
+int step_no_fit(Engine& e, const std::string& who, const char* noun, int extra) {
+  int most = 0;
+  for (const PhaseHost& p : e.ph) most = std::max(most, p.N + extra);
+  return step_fail(e, RPM_E_UNSUPPORTED, who + "a column of " + std::to_string(most) + " " + noun + " does not fit one workgroup's LDS");
+}
+int step_overlap(Engine& e, const std::string& who, const ByteRange* out, int n_out, const ByteRange* in, int n_in) {
+  const ByteRange* hit[2];
+  if (!first_overlap(out, n_out, in, n_in, hit)) return RPM_OK;
+  return step_fail(e, RPM_E_INVALID, who + hit[0]->name + " and " + hit[1]->name + " overlap");
 }
 
 int dev_sync(Engine& e) {

@@ -8,6 +8,8 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
+#include <initializer_list>
 #include <string>
 #include <utility>
 #include <vector>
@@ -205,8 +207,20 @@ inline hipError_t upload(T** dst, const std::vector<T>& src) {
 
 
 // ------------------------------------------------------------------------------------------
-// what the entry points of the sweep steps (mesh-error estimate, carry, extraction) share on the host; rpm_device.hip
-int dev_bind(Engine& e);   // device_init on device 0 unless the engine has a device, then that device made current
+// what the entry points of the sweep steps (mesh-error estimate, carry, shift, sampler, roll-out, extraction) share on the
+// host; rpm_device.hip.  Every entry point is: the step's check (host only), DeviceRestore, dev_bind, then the step's launch
+// (device form) or HostForm::run around it (host-pointer form).
+// dev_bind: device_init on device 0 unless the engine has a device, then that device made current.  With a target engine: an
+// engine without a device joins the other's, and the target's error is reported on `e`.
+int dev_bind(Engine& e, Engine* to = nullptr);
+int step_fail(Engine& e, int code, const std::string& msg);   // e.err = msg; returns code
+// the launches queued so far (or `before`, when that already failed): RPM_OK, or "<step> launch: <hip string>", RPM_E_DEVICE
+int step_launched(Engine& e, const char* step, hipError_t before = hipSuccess);
+int step_no_kernels(Engine& e, const char* step);   // with_problem knew no functor: "<step>: this library has no kernels ..."
+// "<who>a column of <largest N + extra> <noun> does not fit one workgroup's LDS", RPM_E_UNSUPPORTED (knots: extra 1, nodes: 0)
+int step_no_fit(Engine& e, const std::string& who, const char* noun, int extra);
+// first_overlap (rpm_engine.hpp) as a refusal: RPM_OK, or "<who><a> and <b> overlap", RPM_E_INVALID
+int step_overlap(Engine& e, const std::string& who, const ByteRange* out, int n_out, const ByteRange* in, int n_in);
 constexpr size_t kCuLdsBytes = 160 * 1024;   // LDS of one CU of the MI355X
 // dynamic LDS above the 64 KiB every kernel may have: raises the kernel's hipFuncAttributeMaxDynamicSharedMemorySize to the
 // CU's LDS on the current device (the attribute is per device and only ever raised); below that nothing
@@ -220,10 +234,21 @@ struct HostForm {
   double* out = nullptr;
   int *flags = nullptr, *h_flags = nullptr;
   size_t out_cap = 0, flag_cap = 0;
+  // a copy between a caller's array and dev + off (dev NULL: the block) through staging slot `slot`; host NULL: skipped.  Two
+  // copies of one list never share a slot.
+  struct Up { double* dev; size_t off; const double* host; size_t count; int slot; };
+  struct Down { double* host; const double* dev; size_t off; size_t count; int slot; };
+  // The whole host-pointer form, blocking: the block grown to `doubles`, the uploads (one into the engine's d_x first drops what
+  // the callbacks cached, host_new_x), launch(block, verdicts or NULL) on the engine's stream, the verdicts' copy queued, the
+  // downloads, the stream synchronised and the verdicts handed out.  The first failure ends it.
+  int run(Engine& e, size_t doubles, std::initializer_list<Up> ups, const std::function<int(double* block, int* flags)>& launch,
+          std::initializer_list<Down> downs, int* nonfinite);
+  void release();
+
+ private:
   int ensure(Engine& e, size_t doubles, size_t B);
   int fetch(Engine& e, const int* nonfinite, size_t B);   // queues the verdicts' copy to the mirror (nonfinite NULL: nothing)
   int finish(Engine& e, int* nonfinite, size_t B);        // synchronises the engine's stream, then hands the verdicts out
-  void release();
 };
 
 void host_path_destroy(Device* d);   // rpm_host_path.hip

@@ -6,6 +6,7 @@
 //   PhaseHost  <- struct ps + struct indices, Core/LpCalculateData.hpp:29-41
 //   Engine     <- LpCalculateData, Core/LpCalculateData.hpp:43-111 (the per-mesh blackboard)
 #pragma once
+#include <algorithm>
 #include <cstddef>
 #include <string>
 #include <utility>
@@ -215,6 +216,47 @@ inline std::pair<int, int> deal_columns(int cols, int most) {
 inline int clamp_tile(int TB, int B) {
   while (TB > 1 && TB / 2 >= B) TB >>= 1;
   return TB;
+}
+// halve_tile: the largest of TB, TB / 2, TB / 4 ... 1 instances per workgroup for which fits(TB) holds; 0: not even one fits.
+template <class Fits>
+inline int halve_tile(int TB, Fits fits) {
+  while (TB >= 1 && !fits(TB)) TB >>= 1;
+  return TB;
+}
+// split_columns: a phase's `cols` columns as groups (first column, count), deal_columns at the most columns for which
+// fits(ncols) holds (one column is taken to fit: halve_tile decided that).  No columns: deal_columns' one group of none.
+template <class Fits>
+inline std::vector<std::pair<int, int>> split_columns(int cols, Fits fits) {
+  int most = 1;
+  while (most < cols && fits(most + 1)) ++most;
+  const auto [n_groups, per] = deal_columns(cols, most);
+  std::vector<std::pair<int, int>> groups;
+  for (int g = 0, col0 = 0; g < n_groups; ++g, col0 += per) groups.push_back({col0, std::min(per, cols - col0)});
+  return groups;
+}
+// lds_budget: the LDS bytes one workgroup may use under a "*_lds_bytes" option (0: what the device offers, never more than that)
+inline size_t lds_budget(int option, size_t device) { return option > 0 ? std::min(size_t(option), device) : device; }
+
+// May these arrays overlap: a named byte range, and the first overlapping pair of the walk "every output against every input,
+// then against every later output".  A NULL or empty range overlaps nothing.
+struct ByteRange {
+  const char* name;
+  const void* p;
+  size_t bytes;
+};
+inline bool ranges_overlap(const ByteRange& u, const ByteRange& v) {
+  const char *p = static_cast<const char*>(u.p), *q = static_cast<const char*>(v.p);
+  return p && q && u.bytes && v.bytes && p < q + v.bytes && q < p + u.bytes;
+}
+inline bool first_overlap(const ByteRange* out, int n_out, const ByteRange* in, int n_in, const ByteRange* hit[2]) {
+  for (int o = 0; o < n_out; ++o) {
+    hit[0] = &out[o];
+    for (int r = 0; r < n_in; ++r)
+      if (ranges_overlap(out[o], *(hit[1] = &in[r]))) return true;
+    for (int o2 = o + 1; o2 < n_out; ++o2)
+      if (ranges_overlap(out[o], *(hit[1] = &out[o2]))) return true;
+  }
+  return false;
 }
 
 // rpm_setup.cpp

@@ -184,8 +184,7 @@ struct ExtractState {
 // doubles the staged arrays of one workgroup may take: what the device offers less the partial sums of the largest tile, or
 // the option when that is smaller
 size_t extract_budget(const Engine& e) {
-  const size_t most = kCuLdsBytes - 8 * 256 * sizeof(double);
-  return (e.opt_extract_lds > 0 ? std::min(size_t(e.opt_extract_lds), most) : most) / sizeof(double);
+  return lds_budget(e.opt_extract_lds, kCuLdsBytes - 8 * 256 * sizeof(double)) / sizeof(double);
 }
 
 // Host planner.  Fused (one launch): every phase's spline columns fit one workgroup's LDS next to the Lagrangian rows; the
@@ -198,44 +197,28 @@ bool extract_plan(const Engine& e, ExtractPlan* plan, std::vector<ExtractGroup>*
   pl.tile_opt = e.opt_extract_tile;
   pl.lds_opt = e.opt_extract_lds;
   if (groups) groups->clear();
-  for (int TB = TB0; TB >= 1; TB >>= 1) {
-    bool fits = true;
-    size_t lds = 0;
-    for (const PhaseHost& p : e.ph) {
-      const ExtractLds L(p.N, TB, p.nu + p.nc, TB, TB);
-      fits = fits && size_t(L.staged()) <= budget;
-      lds = std::max(lds, size_t(L.total) * sizeof(double));
-    }
-    if (fits) {
-      pl.TB = TB;
-      pl.fused = 1;
-      pl.lds_node = lds;
-      *plan = pl;
-      return true;
-    }
+  auto all_fit = [&](auto fits) { return std::all_of(e.ph.begin(), e.ph.end(), fits); };
+  pl.TB = halve_tile(TB0, [&](int TB) {
+    return all_fit([&](const PhaseHost& p) { return size_t(ExtractLds(p.N, TB, p.nu + p.nc, TB, TB).staged()) <= budget; });
+  });
+  if (pl.TB) {
+    pl.fused = 1;
+    for (const PhaseHost& p : e.ph) pl.lds_node = std::max(pl.lds_node, size_t(ExtractLds(p.N, pl.TB, p.nu + p.nc, pl.TB, pl.TB).total) * sizeof(double));
+    *plan = pl;
+    return true;
   }
-  int TB = TB0;
-  for (;; TB >>= 1) {
-    bool fits = true;
-    for (const PhaseHost& p : e.ph) fits = fits && (p.nu + p.nc == 0 || size_t(ExtractLds(p.N, TB, 1, 0, 0).total) <= budget);
-    if (fits) break;
-    if (TB == 1) return false;
-  }
-  pl.TB = TB;
+  auto fits = [&](const PhaseHost& p, int TB, int ncols) { return size_t(ExtractLds(p.N, TB, ncols, 0, 0).total) <= budget; };
+  pl.TB = halve_tile(TB0, [&](int TB) { return all_fit([&](const PhaseHost& p) { return p.nu + p.nc == 0 || fits(p, TB, 1); }); });
+  if (!pl.TB) return false;
   pl.fused = 0;
-  pl.lds_node = size_t(ExtractLds(1, TB, 0, TB, 0).total) * sizeof(double);
+  pl.lds_node = size_t(ExtractLds(1, pl.TB, 0, pl.TB, 0).total) * sizeof(double);
   for (size_t ip = 0; ip < e.ph.size(); ++ip) {
     const PhaseHost& p = e.ph[ip];
-    const int cols = p.nu + p.nc;
-    if (cols == 0) continue;
-    int most = 1;   // the most columns of TB instances that fit
-    while (most < cols && size_t(ExtractLds(p.N, TB, most + 1, 0, 0).total) <= budget) ++most;
-    const int per = deal_columns(cols, most).second;
-    for (int col0 = 0; col0 < cols; col0 += per) {
-      const ExtractGroup g{int(ip), col0, std::min(per, cols - col0)};
-      pl.lds_spline = std::max(pl.lds_spline, size_t(ExtractLds(p.N, TB, g.ncols, 0, 0).total) * sizeof(double));
+    if (p.nu + p.nc == 0) continue;   // no spline columns: no workgroup of the spline launch
+    for (const auto& [col0, ncols] : split_columns(p.nu + p.nc, [&](int nc) { return fits(p, pl.TB, nc); })) {
+      pl.lds_spline = std::max(pl.lds_spline, size_t(ExtractLds(p.N, pl.TB, ncols, 0, 0).total) * sizeof(double));
       ++pl.n_groups;
-      if (groups) groups->push_back(g);
+      if (groups) groups->push_back(ExtractGroup{int(ip), col0, ncols});
     }
   }
   *plan = pl;
@@ -258,11 +241,6 @@ ExtractState& extract_state(Device& d) {
   return *static_cast<ExtractState*>(d.extract);
 }
 
-int extract_fail(Engine& e, int code, const std::string& msg) {
-  e.err = msg;
-  return code;
-}
-
 int extract_launch(Engine& e, const double* d_x, const double* d_lambda, double* d_out, int* d_nonfinite, hipStream_t st) {
   Device& d = *e.dev;
   ExtractState& es = extract_state(d);
@@ -274,7 +252,7 @@ int extract_launch(Engine& e, const double* d_x, const double* d_lambda, double*
   if (!plan) {   // first call under these options: the only allocations and the only blocking copy
     ExtractPlan p;
     std::vector<ExtractGroup> groups;
-    if (!extract_plan(e, &p, &groups)) return extract_fail(e, RPM_E_UNSUPPORTED, "nlp2op_batch: a column does not fit one workgroup's LDS");
+    if (!extract_plan(e, &p, &groups)) return step_fail(e, RPM_E_UNSUPPORTED, "nlp2op_batch: a column does not fit one workgroup's LDS");
     if (!p.fused) {
       HIP_TRY(e, upload(&p.d_groups, groups));
       if (!es.ends_ws) {
@@ -304,11 +282,9 @@ int extract_launch(Engine& e, const double* d_x, const double* d_lambda, double*
     hipLaunchKernelGGL((rpm_extract_kernel<P>), dim3(unsigned(e.P), tiles), dim3(256), plan->lds_node, st, d.kp, Bi, TB, plan->fused,
                        EB, d_x, d_lambda, es.ends_ws, ET, extract_ecols(e), es.lag_ws, NT, d_out);
   });
-  if (!known) return extract_fail(e, RPM_E_UNSUPPORTED, "nlp2op_batch: this library has no kernels for the engine's problem");
+  if (!known) return step_no_kernels(e, "nlp2op_batch");
   if (d_nonfinite) flag_launch(EB, d_out, d_nonfinite, Bi, st);
-  const hipError_t s = hipGetLastError();
-  if (s != hipSuccess) return extract_fail(e, RPM_E_DEVICE, std::string("nlp2op_batch launch: ") + hipGetErrorString(s));
-  return RPM_OK;
+  return step_launched(e, "nlp2op_batch");
 }
 
 }  // namespace
@@ -355,15 +331,11 @@ int extract_group_count(const Engine& e) {
 // every error of the engine's state, decided on the host before a device is touched
 int extract_check(Engine& e) {
   const std::string who = "nlp2op_batch: ";
-  if (sharded(e)) return extract_fail(e, RPM_E_UNSUPPORTED, who + "not with interval sharding");
+  if (sharded(e)) return step_fail(e, RPM_E_UNSUPPORTED, who + "not with interval sharding");
   for (const PhaseHost& p : e.ph)   // the path multipliers' unshifted index stays inside the instance's own lambda block
-    if ((long long)p.N * (p.nx + p.nc) > e.m) return extract_fail(e, RPM_E_UNSUPPORTED, who + "a phase's path multipliers would be read past the instance's multipliers");
+    if ((long long)p.N * (p.nx + p.nc) > e.m) return step_fail(e, RPM_E_UNSUPPORTED, who + "a phase's path multipliers would be read past the instance's multipliers");
   ExtractPlan p;
-  if (!extract_plan(e, &p, nullptr)) {
-    int most = 0;
-    for (const PhaseHost& q : e.ph) most = std::max(most, q.N);
-    return extract_fail(e, RPM_E_UNSUPPORTED, who + "a column of " + std::to_string(most) + " nodes does not fit one workgroup's LDS");
-  }
+  if (!extract_plan(e, &p, nullptr)) return step_no_fit(e, who, "nodes", 0);
   return RPM_OK;
 }
 
@@ -386,21 +358,13 @@ int host_nlp2op_batch(Engine& e, const double* x, const double* lambda, double* 
   rc = dev_bind(e);
   if (rc) return rc;
   Device& d = *e.dev;
-  ExtractState& es = extract_state(d);
   const size_t B = size_t(e.n_instances);
   long long EB = 0;
   nlp2op_batch_layout(e, 0, nullptr, &EB);
-  rc = es.host.ensure(e, B * size_t(EB), B);
-  if (rc) return rc;
-  host_new_x(e);   // d_x is about to hold other values than the callbacks' last x
-  rc = dev_upload(e, d.d_x, x, B * e.n, STAGE_X);
-  if (rc == RPM_OK) rc = dev_upload(e, d.d_lambda, lambda, B * e.m, STAGE_LAMBDA);
-  if (rc) return rc;
-  rc = extract_launch(e, d.d_x, d.d_lambda, es.host.out, nonfinite ? es.host.flags : nullptr, d.stream);
-  if (rc == RPM_OK) rc = es.host.fetch(e, nonfinite, B);
-  if (rc == RPM_OK) rc = dev_download(e, out, es.host.out, B * size_t(EB), STAGE_G);
-  if (rc) return rc;
-  return es.host.finish(e, nonfinite, B);
+  return extract_state(d).host.run(
+      e, B * size_t(EB), {{d.d_x, 0, x, B * e.n, STAGE_X}, {d.d_lambda, 0, lambda, B * e.m, STAGE_LAMBDA}},
+      [&](double* blocks, int* flags) { return extract_launch(e, d.d_x, d.d_lambda, blocks, flags, d.stream); },
+      {{out, nullptr, 0, B * size_t(EB), STAGE_G}}, nonfinite);
 }
 
 }  // namespace rpm

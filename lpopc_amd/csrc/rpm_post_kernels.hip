@@ -535,10 +535,6 @@ int mesh_batch_setup(Engine& e) {
     m.nx_max = std::max(m.nx_max, p.nx);
   }
   ph_iv0.push_back(int(ivs.size()));
-  if (m.inst_doubles * sizeof(double) > kMeshLdsLimit) {
-    e.err = "solution_error_batch: a mesh interval has too many nodes for the estimator's LDS tile";
-    return RPM_E_UNSUPPORTED;
-  }
   const size_t B = size_t(e.n_instances);
   const size_t nd = tt.size() + Hs.size() + Ss.size() + Hc.size() + Sc.size() + A.size() + (3 * B + kMaxChunks) * size_t(m.RT);
   const size_t ni = hit_s.size() + hit_c.size() + ph_iv0.size() + kMaxChunks;
@@ -575,33 +571,37 @@ int mesh_batch_setup(Engine& e) {
   put(m.ivs, ivs.data(), ivs.size() * sizeof(MeshIvBatch));
   if (s != hipSuccess) {
     (void)hipFree(m.block);
-    e.err = std::string("solution_error_batch: ") + hipGetErrorString(s);
-    return RPM_E_DEVICE;
+    return step_fail(e, RPM_E_DEVICE, std::string("solution_error_batch: ") + hipGetErrorString(s));
   }
   d.mesh_batch = new MeshBatch(m);
   return RPM_OK;
 }
 
-}  // namespace
+// what the engine's mesh refuses, decided on the host before a device is touched (the arguments: rpm_abi.cpp)
+int mesh_check(Engine& e) {
+  size_t inst_doubles = 0;   // one instance's Xs / Us / Fs arrays of the largest interval
+  for (const PhaseHost& p : e.ph)
+    for (const int n : p.nk) inst_doubles = std::max(inst_doubles, (size_t(n) + 1) * size_t(2 * p.nx + p.nu));
+  if (inst_doubles * sizeof(double) > kMeshLdsLimit)
+    return step_fail(e, RPM_E_UNSUPPORTED, "solution_error_batch: a mesh interval has too many nodes for the estimator's LDS tile");
+  return RPM_OK;
+}
 
-// device-resident: three or four launches on `stream`; after the first call on an engine nothing else
-int dev_solution_error_batch(Engine& e, const double* d_x, const int* d_mask, double* d_interval_error, double* d_rel_err_max,
-                             double* d_rel_err, int* d_nonfinite, void* stream) {
-  DeviceRestore restore;
-  int rc = dev_bind(e);
-  if (rc == RPM_OK) rc = mesh_batch_setup(e);
+// three or four launches on `st`; the engine's device is current
+int mesh_launch(Engine& e, const double* d_x, const int* d_mask, double* d_interval_error, double* d_rel_err_max, double* d_rel_err,
+                int* d_nonfinite, hipStream_t st) {
+  const int rc = mesh_batch_setup(e);
   if (rc) return rc;
   Device& d = *e.dev;
   const MeshBatch& m = *static_cast<MeshBatch*>(d.mesh_batch);
   const int B = e.n_instances;
-  // instances per workgroup: the largest of 8, 4, 2, 1 (or the option) whose arrays fit next to the staged tables
-  int TB = e.opt_mesh_err_tile > 0 ? e.opt_mesh_err_tile : 8;
+  // instances per workgroup: the largest of 8, 4, 2, 1 (or the option) whose arrays fit next to the staged tables (one always
+  // does: mesh_check), then no more than the sweep has
   const int stage = (m.tab_doubles + m.inst_doubles) * sizeof(double) <= kMeshLdsLimit ? 1 : 0;
   const size_t tab = stage ? m.tab_doubles : 0;
-  while (TB > 1 && (tab + size_t(TB) * m.inst_doubles) * sizeof(double) > kMeshLdsLimit) TB >>= 1;
-  TB = clamp_tile(TB, B);
-  const size_t lds = (tab + size_t(TB) * m.inst_doubles) * sizeof(double);
-  hipStream_t st = static_cast<hipStream_t>(stream);
+  auto bytes = [&](int tb) { return (tab + size_t(tb) * m.inst_doubles) * sizeof(double); };
+  const int TB = clamp_tile(std::max(1, halve_tile(e.opt_mesh_err_tile > 0 ? e.opt_mesh_err_tile : 8, [&](int tb) { return bytes(tb) <= kMeshLdsLimit; })), B);
+  const size_t lds = bytes(TB);
   double* rel = d_rel_err ? d_rel_err : (d_rel_err_max ? m.rel : nullptr);
   with_problem(e.problem_id, [&](auto prob) {
     using P = decltype(prob);
@@ -625,47 +625,50 @@ int dev_solution_error_batch(Engine& e, const double* d_x, const int* d_mask, do
       hipLaunchKernelGGL(rpm_mesh_max_kernel, dim3(gx), dim3(256), 0, st, m.RT, chunks, chunks, m.part_has, m.part, d_rel_err_max, no_has);
     }
   }
-  const hipError_t s = hipGetLastError();
-  if (s != hipSuccess) {
-    e.err = std::string("solution_error_batch launch: ") + hipGetErrorString(s);
-    return RPM_E_DEVICE;
-  }
-  return RPM_OK;
+  return step_launched(e, "solution_error_batch");
+}
+
+}  // namespace
+
+// device-resident: three or four launches on `stream`; after the first call on an engine nothing else
+int dev_solution_error_batch(Engine& e, const double* d_x, const int* d_mask, double* d_interval_error, double* d_rel_err_max,
+                             double* d_rel_err, int* d_nonfinite, void* stream) {
+  int rc = mesh_check(e);
+  if (rc) return rc;
+  DeviceRestore restore;
+  rc = dev_bind(e);
+  if (rc) return rc;
+  return mesh_launch(e, d_x, d_mask, d_interval_error, d_rel_err_max, d_rel_err, d_nonfinite, static_cast<hipStream_t>(stream));
 }
 
 // the same through host arrays: x (and the mask) up through the staging slots, the requested results back; blocking
 int host_solution_error_batch(Engine& e, const double* x, const int* mask, double* interval_error, double* rel_err_max,
                               double* rel_err, int* nonfinite) {
+  int rc = mesh_check(e);
+  if (rc) return rc;
   DeviceRestore restore;
-  int rc = dev_bind(e);
+  rc = dev_bind(e);
   if (rc == RPM_OK) rc = mesh_batch_setup(e);
   if (rc) return rc;
   Device& d = *e.dev;
   MeshBatch& m = *static_cast<MeshBatch*>(d.mesh_batch);
-  const size_t B = size_t(e.n_instances);
-  rc = m.host.ensure(e, B * m.KT + size_t(m.RT), B);
-  if (rc) return rc;
-  double *o_iv = m.host.out, *o_max = o_iv + B * m.KT;
+  const size_t B = size_t(e.n_instances), o_max = B * m.KT;   // the block: the interval errors, then the maximum
   if (mask && !m.o_mask) {   // sized once, unlike `host`: an engine's n_instances never changes
     HIP_TRY(e, hipMalloc(reinterpret_cast<void**>(&m.o_mask), B * sizeof(int)));
     HIP_TRY(e, hipHostMalloc(reinterpret_cast<void**>(&m.h_mask), B * sizeof(int), hipHostMallocDefault));
   }
-  rc = dev_upload(e, d.d_x, x, B * e.n, STAGE_X);
-  if (rc) return rc;
-  if (mask) {
-    std::memcpy(m.h_mask, mask, B * sizeof(int));
-    HIP_TRY(e, hipMemcpyAsync(m.o_mask, m.h_mask, B * sizeof(int), hipMemcpyHostToDevice, d.stream));
-  }
-  rc = dev_solution_error_batch(e, d.d_x, mask ? m.o_mask : nullptr, interval_error ? o_iv : nullptr,
-                                rel_err_max ? o_max : nullptr, rel_err ? m.rel : nullptr, nonfinite ? m.host.flags : nullptr, d.stream);
-  if (rc) return rc;
-  HIP_TRY(e, hipSetDevice(d.device_id));   // dev_solution_error_batch put the caller's device back
-  rc = m.host.fetch(e, nonfinite, B);
-  if (rc == RPM_OK && interval_error) rc = dev_download(e, interval_error, o_iv, B * m.KT, STAGE_G);
-  if (rc == RPM_OK && rel_err_max) rc = dev_download(e, rel_err_max, o_max, size_t(m.RT), STAGE_V);
-  if (rc == RPM_OK && rel_err) rc = dev_download(e, rel_err, m.rel, B * size_t(m.RT), STAGE_HESS);
-  if (rc) return rc;
-  return m.host.finish(e, nonfinite, B);
+  return m.host.run(
+      e, o_max + size_t(m.RT), {{d.d_x, 0, x, B * e.n, STAGE_X}},
+      [&](double* b, int* flags) -> int {
+        if (mask) {
+          std::memcpy(m.h_mask, mask, B * sizeof(int));
+          HIP_TRY(e, hipMemcpyAsync(m.o_mask, m.h_mask, B * sizeof(int), hipMemcpyHostToDevice, d.stream));
+        }
+        return mesh_launch(e, d.d_x, mask ? m.o_mask : nullptr, interval_error ? b : nullptr, rel_err_max ? b + o_max : nullptr,
+                           rel_err ? m.rel : nullptr, flags, d.stream);
+      },
+      {{interval_error, nullptr, 0, o_max, STAGE_G}, {rel_err_max, nullptr, o_max, size_t(m.RT), STAGE_V}, {rel_err, m.rel, 0, B * size_t(m.RT), STAGE_HESS}},
+      nonfinite);
 }
 
 }  // namespace rpm

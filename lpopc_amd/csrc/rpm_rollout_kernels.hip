@@ -134,26 +134,16 @@ RolloutState& rollout_state(Device& d) {
   return *static_cast<RolloutState*>(d.rollout);
 }
 
-int rollout_fail(Engine& e, int code, const std::string& msg) {
-  e.err = msg;
-  return code;
-}
-
 // Host planner: instances per workgroup, halved until the knots and the nu control columns of the tile fit the LDS one workgroup
 // may use (option "carry_lds_bytes" lowers it, as for the carry); false: they do not fit even at one instance per workgroup.
 bool rollout_plan(const Engine& e, int phase, int* TB_out, size_t* lds_out) {
-  const size_t budget = e.opt_carry_lds > 0 ? std::min(size_t(e.opt_carry_lds), kCuLdsBytes) : kCuLdsBytes;
+  const size_t budget = lds_budget(e.opt_carry_lds, kCuLdsBytes);
   const PhaseHost& p = e.ph[size_t(phase)];
-  int TB = clamp_tile(e.opt_rollout_tile > 0 ? e.opt_rollout_tile : kRolloutAutoTile, e.n_instances);
-  for (;; TB >>= 1) {
-    const size_t lds = size_t(CarryLds(p.N + 1, TB, p.nu).total) * sizeof(double);
-    if (lds <= budget) {
-      *TB_out = TB;
-      *lds_out = lds;
-      return true;
-    }
-    if (TB == 1) return false;
-  }
+  auto bytes = [&](int TB) { return size_t(CarryLds(p.N + 1, TB, p.nu).total) * sizeof(double); };
+  *TB_out = halve_tile(clamp_tile(e.opt_rollout_tile > 0 ? e.opt_rollout_tile : kRolloutAutoTile, e.n_instances),
+                       [&](int TB) { return bytes(TB) <= budget; });
+  *lds_out = *TB_out ? bytes(*TB_out) : 0;
+  return *TB_out > 0;
 }
 
 int rollout_launch(Engine& e, int phase, const RolloutArrays& a, int n_steps, int hold, int* d_nonfinite, hipStream_t st) {
@@ -161,7 +151,7 @@ int rollout_launch(Engine& e, int phase, const RolloutArrays& a, int n_steps, in
   RolloutState& rs = rollout_state(d);
   int TB = 1;
   size_t lds = 0;
-  if (!rollout_plan(e, phase, &TB, &lds)) return rollout_fail(e, RPM_E_UNSUPPORTED, "rollout_batch: the control columns do not fit one workgroup's LDS");
+  if (!rollout_plan(e, phase, &TB, &lds)) return step_fail(e, RPM_E_UNSUPPORTED, "rollout_batch: the control columns do not fit one workgroup's LDS");
   const int B = e.n_instances;
   hipError_t s = hipSuccess;
   const bool known = with_problem(e.problem_id, [&](auto prob) {
@@ -173,11 +163,9 @@ int rollout_launch(Engine& e, int phase, const RolloutArrays& a, int n_steps, in
     if (s != hipSuccess) return;
     hipLaunchKernelGGL((rpm_rollout_kernel<P>), dim3(unsigned((B + TB - 1) / TB)), dim3(256), lds, st, d.kp, phase, B, TB, a.x, a.t_start,
                        a.dt, n_steps, hold, a.state0, a.state_out, a.traj, d_nonfinite);
-    s = hipGetLastError();
   });
-  if (!known) return rollout_fail(e, RPM_E_UNSUPPORTED, "rollout_batch: this library has no kernels for the engine's problem");
-  if (s != hipSuccess) return rollout_fail(e, RPM_E_DEVICE, std::string("rollout_batch launch: ") + hipGetErrorString(s));
-  return RPM_OK;
+  if (!known) return step_no_kernels(e, "rollout_batch");
+  return step_launched(e, "rollout_batch", s);
 }
 
 }  // namespace
@@ -193,33 +181,27 @@ void rollout_destroy(Device* d) {
 // every argument error of the roll-out, decided on the host before a device is touched (all host or all device pointers)
 int rollout_check(Engine& e, int phase, const RolloutArrays& a, int n_steps, int hold) {
   const std::string who = "rollout_batch: ";
-  if (!a.x) return rollout_fail(e, RPM_E_INVALID, who + "x is NULL");
-  if (!a.dt) return rollout_fail(e, RPM_E_INVALID, who + "dt is NULL");
-  if (!a.state_out) return rollout_fail(e, RPM_E_INVALID, who + "state_out is NULL");
-  if (n_steps < 1 || n_steps > 65536) return rollout_fail(e, RPM_E_INVALID, who + "n_steps must be 1 ... 65536");
-  if (hold != 0 && hold != 1) return rollout_fail(e, RPM_E_INVALID, who + "hold must be 0 or 1");
-  if (phase < 0 || phase >= e.P) return rollout_fail(e, RPM_E_INVALID, who + "the phase index is out of range");
+  if (!a.x) return step_fail(e, RPM_E_INVALID, who + "x is NULL");
+  if (!a.dt) return step_fail(e, RPM_E_INVALID, who + "dt is NULL");
+  if (!a.state_out) return step_fail(e, RPM_E_INVALID, who + "state_out is NULL");
+  if (n_steps < 1 || n_steps > 65536) return step_fail(e, RPM_E_INVALID, who + "n_steps must be 1 ... 65536");
+  if (hold != 0 && hold != 1) return step_fail(e, RPM_E_INVALID, who + "hold must be 0 or 1");
+  if (phase < 0 || phase >= e.P) return step_fail(e, RPM_E_INVALID, who + "the phase index is out of range");
   const PhaseHost& p = e.ph[size_t(phase)];
   const size_t B = size_t(e.n_instances), Bs = B * p.nx * sizeof(double);
-  struct Range { const char* name; const void* p; size_t bytes; };
-  const Range in[4] = {{"x", a.x, B * e.n * sizeof(double)}, {"t_start", a.t_start, B * sizeof(double)}, {"dt", a.dt, B * sizeof(double)},
-                       {"state0", a.state0, Bs}};
-  const Range out[2] = {{"state_out", a.state_out, Bs}, {"traj", a.traj, Bs * (size_t(n_steps) + 1)}};
-  auto overlap = [](const Range& u, const Range& v) {
-    const char *p = static_cast<const char*>(u.p), *q = static_cast<const char*>(v.p);
-    return p && q && u.bytes && v.bytes && p < q + v.bytes && q < p + u.bytes;
-  };
-  for (int o = 0; o < 2; ++o)
-    for (int r = 0; r < 4; ++r) {
-      if (o == 0 && r == 3 && a.state_out == a.state0) continue;   // a state updated in place
-      if (overlap(out[o], in[r])) return rollout_fail(e, RPM_E_INVALID, who + out[o].name + " and " + in[r].name + " overlap");
-    }
-  if (overlap(out[0], out[1])) return rollout_fail(e, RPM_E_INVALID, who + "state_out and traj overlap");
-  if (sharded(e)) return rollout_fail(e, RPM_E_UNSUPPORTED, who + "not with interval sharding");
+  const ByteRange in[4] = {{"x", a.x, B * e.n * sizeof(double)}, {"t_start", a.t_start, B * sizeof(double)}, {"dt", a.dt, B * sizeof(double)},
+                           {"state0", a.state0, Bs}};
+  const ByteRange out[2] = {{"state_out", a.state_out, Bs}, {"traj", a.traj, Bs * (size_t(n_steps) + 1)}};
+  // each output against the inputs before the outputs against each other; state0 last, left out for a state updated in place
+  int rc = step_overlap(e, who, &out[0], 1, in, a.state_out == a.state0 ? 3 : 4);
+  if (rc == RPM_OK) rc = step_overlap(e, who, &out[1], 1, in, 4);
+  if (rc == RPM_OK) rc = step_overlap(e, who, out, 2, in, 0);
+  if (rc) return rc;
+  if (sharded(e)) return step_fail(e, RPM_E_UNSUPPORTED, who + "not with interval sharding");
   int TB = 0;
   size_t lds = 0;
   if (!rollout_plan(e, phase, &TB, &lds))
-    return rollout_fail(e, RPM_E_UNSUPPORTED, who + "the " + std::to_string(p.nu) + " control columns of " + std::to_string(p.N + 1) +
+    return step_fail(e, RPM_E_UNSUPPORTED, who + "the " + std::to_string(p.nu) + " control columns of " + std::to_string(p.N + 1) +
                                                   " knots do not fit one workgroup's LDS");
   return RPM_OK;
 }
@@ -242,24 +224,17 @@ int host_rollout_batch(Engine& e, int phase, const RolloutArrays& a, int n_steps
   rc = dev_bind(e);
   if (rc) return rc;
   Device& d = *e.dev;
-  RolloutState& rs = rollout_state(d);
   const size_t B = size_t(e.n_instances), Bs = B * size_t(e.ph[size_t(phase)].nx), Bt = a.traj ? Bs * (size_t(n_steps) + 1) : 0;
-  rc = rs.host.ensure(e, 2 * B + 2 * Bs + Bt, B);
-  if (rc) return rc;
-  double *d_ts = rs.host.out, *d_dt = d_ts + B, *d_s0 = d_dt + B, *d_so = d_s0 + Bs, *d_traj = d_so + Bs;
-  host_new_x(e);   // d_x is about to hold other values than the callbacks' last x
-  rc = dev_upload(e, d.d_x, a.x, B * e.n, STAGE_X);
-  if (rc == RPM_OK) rc = dev_upload(e, d_dt, a.dt, B, STAGE_G);
-  if (rc == RPM_OK && a.t_start) rc = dev_upload(e, d_ts, a.t_start, B, STAGE_V);
-  if (rc == RPM_OK && a.state0) rc = dev_upload(e, d_s0, a.state0, Bs, STAGE_GRAD);
-  if (rc) return rc;
-  const RolloutArrays dv{d.d_x, a.t_start ? d_ts : nullptr, d_dt, a.state0 ? d_s0 : nullptr, d_so, a.traj ? d_traj : nullptr};
-  rc = rollout_launch(e, phase, dv, n_steps, hold, nonfinite ? rs.host.flags : nullptr, d.stream);
-  if (rc == RPM_OK) rc = rs.host.fetch(e, nonfinite, B);
-  if (rc == RPM_OK) rc = dev_download(e, a.state_out, d_so, Bs, STAGE_G);
-  if (rc == RPM_OK && a.traj) rc = dev_download(e, a.traj, d_traj, Bt, STAGE_LAMBDA);
-  if (rc) return rc;
-  return rs.host.finish(e, nonfinite, B);
+  const size_t o_dt = B, o_s0 = o_dt + B, o_so = o_s0 + Bs, o_traj = o_so + Bs;   // the block: t_start first
+  return rollout_state(d).host.run(
+      e, o_traj + Bt,
+      {{d.d_x, 0, a.x, B * e.n, STAGE_X}, {nullptr, o_dt, a.dt, B, STAGE_G}, {nullptr, 0, a.t_start, B, STAGE_V},
+       {nullptr, o_s0, a.state0, Bs, STAGE_GRAD}},
+      [&](double* b, int* flags) {
+        const RolloutArrays dv{d.d_x, a.t_start ? b : nullptr, b + o_dt, a.state0 ? b + o_s0 : nullptr, b + o_so, a.traj ? b + o_traj : nullptr};
+        return rollout_launch(e, phase, dv, n_steps, hold, flags, d.stream);
+      },
+      {{a.state_out, nullptr, o_so, Bs, STAGE_G}, {a.traj, nullptr, o_traj, Bt, STAGE_LAMBDA}}, nonfinite);
 }
 
 }  // namespace rpm

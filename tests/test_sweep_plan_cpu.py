@@ -1,5 +1,6 @@
-"""The launch-planning arithmetic shared by the sweep steps (deal_columns, clamp_tile in lpopc_amd/csrc/rpm_engine.hpp) on the
-CPU: tests/native/sweep_plan_test.cpp walks every small input, plain and under AddressSanitizer + UBSan."""
+"""The host arithmetic shared by the sweep steps (deal_columns, clamp_tile, halve_tile, split_columns, lds_budget and the overlap
+rule first_overlap in lpopc_amd/csrc/rpm_engine.hpp) on the CPU: tests/native/sweep_plan_test.cpp walks every small input, plain
+and under AddressSanitizer + UBSan."""
 import os
 import subprocess
 
