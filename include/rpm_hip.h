@@ -540,6 +540,52 @@ int rpm_ipm_solve_warm_dev(rpm_ipm* s, double* d_x, double* d_lambda, double* d_
                            int* iterations, double* kkt_error, void* stream);
 int rpm_ipm_get_bound_multipliers(rpm_ipm* s, double* z_L, double* z_U);
 int rpm_ipm_get_bound_multipliers_dev(rpm_ipm* s, double* d_z_L, double* d_z_U, void* stream);
+/* Solution sensitivities to variables that are FIXED in the solver's plan (x_l == x_u; the pattern is shared by all instances):
+ * the measured initial states of a receding-horizon sweep, t0, tf.  Call v = (x, slacks), lambda, z_L, z_U and the relaxed bounds
+ * "the state": what the solver holds after a finished solve of either kind, or directly after rpm_ipm_debug_start /
+ * rpm_ipm_debug_pass.  Column k (k < n_par, 1 <= n_par <= 32, j = var_index[k]) solves the solver's own reduced system (13),
+ *   [ W + Sigma + delta_w I   A' ] [dv]     [ W[free, j] ]
+ *   [ A                 -delta_c I ] [dl] = - [ A[:, j]    ]
+ * with W the exact Hessian of the Lagrangian at (x, lambda), A the constraint Jacobian (-1 at every slack), Sigma = z_L / (v - v_l)
+ * + z_U / (v_u - v) on the free unknowns: the matrix of an iteration, assembled and factored by the same launchers.  delta_w starts
+ * at 0 and follows the iteration's inertia correction; where it ends is reported.  The right-hand side, in unknown order: free
+ * variable i -(h_1 + h_2 + ...) over the Hessian triplets at {i, j} in ascending triplet index, one addition after the other;
+ * constraint row r -(the Jacobian triplets at (r, j), likewise; there is at most one); slacks and fixed unknowns 0.  Results,
+ * instance-major: dx (n_instances x n_par x n) = dv on the free variables, 1 at variable j, 0 at every other fixed variable;
+ * dlambda (n_instances x n_par x m, or NULL) = dl.  Sigma is taken at the barrier parameter the state ended at, so these are the
+ * sensitivities of the barrier problem, and W is as good as the engine's finite-difference-tol makes it.
+ *   delta_w (host, n_instances, or NULL)  the regularisation the factorisation ended at (NaN where info is 2)
+ *   info    (host, n_instances, or NULL)  0 computed with delta_w = 0; 1 computed with delta_w > 0 (the matrix was regularised: not
+ *           a strict local minimum at this mu); 2 left out — the instance's state is non-finite (device status 5) or the
+ *           factorisation gave up —, its blocks are NaN and no other instance is touched
+ * Ordering contract of the _dev form: that of rpm_ipm_solve_dev (runs on the engine's private stream after what the caller queued
+ * on `stream`, returns when drained); var_index, delta_w and info are host arrays.  It reads host counters for the inertia
+ * correction, so it is not capturable into a graph.  The work space (n_instances x n_par x right-hand-side length doubles) is
+ * allocated on first use, kept, and grows only for a larger n_par.  The iterate, the multipliers, the instance records,
+ * rpm_ipm_get_bound_multipliers and the statistics of the last solve are what they were before the call: a following
+ * rpm_ipm_solve[_warm] is bit for bit what it is without the call in between.  The calling thread's current device is restored.
+ * Refusals, all decided on the host before anything is queued — RPM_E_INVALID with a message: NULL var_index or dx, n_par outside
+ * 1 .. 32, an index out of range, a duplicate, a free variable (named), no state to take them at; RPM_E_UNSUPPORTED:
+ * hessian-approximation = limited-memory (a quasi-Newton W gives no sensitivities), nlp_scaling = 1.
+ * rpm_ipm_initial_state_variables (host only): the nx variables rpm_ipm_set_initial_states writes, x_state0 + j (N + 1). */
+int rpm_ipm_initial_state_variables(rpm_ipm* s, int phase, int* var_index /* nx */);
+int rpm_ipm_sensitivities_dev(rpm_ipm* s, int n_par, const int* var_index, double* d_dx, double* d_dlambda, double* delta_w, int* info,
+                              void* stream);
+int rpm_ipm_sensitivities(rpm_ipm* s, int n_par, const int* var_index, double* dx, double* dlambda, double* delta_w, int* info);
+/* The predictor (the tangential step of advanced-step NMPC): x_out[b] = x[b], then for k ascending x_out[b] = x_out[b] +
+ * dx[b][k] * delta[b][k] — product, then sum —, delta n_instances x n_par (the move of every listed variable); lambda likewise
+ * when dlambda, lambda and lambda_out are all given.  Nothing is clipped to the bounds: the pushes of the warm start that follows
+ * deal with them.  The _dev form is one launch on `stream`: it allocates nothing, copies nothing and never synchronises
+ * (capturable); the host form goes through a device block of the solver's, blocking.  An output that overlaps an input or the other
+ * output, a NULL dx / delta / x / x_out, a bad list (as above): RPM_E_INVALID with a message. */
+int rpm_ipm_apply_sensitivities_dev(rpm_ipm* s, int n_par, const int* var_index, const double* d_dx, const double* d_dlambda,
+                                    const double* d_delta, const double* d_x, double* d_x_out, const double* d_lambda,
+                                    double* d_lambda_out, void* stream);
+int rpm_ipm_apply_sensitivities(rpm_ipm* s, int n_par, const int* var_index, const double* dx, const double* dlambda, const double* delta,
+                                const double* x, double* x_out, const double* lambda, double* lambda_out);
+/* test hook (host pointers, synchronous): the evaluation and the right-hand-side gather of rpm_ipm_sensitivities only; rhs:
+ * n_instances x n_par x kkt_order in unknown order (variables, slacks, multipliers).  Same refusals. */
+int rpm_ipm_debug_sensitivity_rhs(rpm_ipm* s, int n_par, const int* var_index, double* rhs);
 /* test hook (host pointers): exactly the launches that precede the iteration loop — warm = 0 the cold start (lambda, z_L, z_U
  * ignored), else the warm start above — then the state: v (n_instances x nv: x, then the slacks), zL, zU (n_instances x nv),
  * lambda (n_instances x m), mu and status (n_instances; status 0, or 5 after a non-finite input), all in the solver's (scaled)
@@ -861,6 +907,8 @@ int rpm_sweep_carry_multipliers(rpm_sweep* from, rpm_sweep* to, const double* x_
 int rpm_sweep_solve_warm(rpm_sweep* s, double* x, double* lambda, double* z_L, double* z_U, double* obj, int* status, int* iterations,
                          double* kkt_error);
 int rpm_sweep_get_bound_multipliers(rpm_sweep* s, double* z_L, double* z_U);
+/* rpm_ipm_sensitivities of every share: dx B x n_par x n, dlambda B x n_par x m or NULL, delta_w and info B or NULL */
+int rpm_sweep_sensitivities(rpm_sweep* s, int n_par, const int* var_index, double* dx, double* dlambda, double* delta_w, int* info);
 /* rpm_shift_plan_batch / rpm_ipm_set_initial_states on every share side by side (host arrays, all B instances: dt B x n_phases,
  * state0 B x nx): what one engine holding all B instances computes, bit for bit */
 int rpm_sweep_shift_plan(rpm_sweep* s, const double* dt, const double* x, double* x_out, const double* lambda, double* lambda_out,

@@ -171,4 +171,22 @@ struct IpmFusedFill {
 };
 IpmFusedFill ipm_fused_fill(const IpmSubList& s, const IpmFillList& fill);
 
+// Solution sensitivities to fixed variables (rpm_ipm_sens.hip): column k answers "how does the solution move with fixed variable
+// var_index[k]", so its right-hand side is minus column var_index[k] of the KKT matrix's off-diagonal blocks — the Hessian entries
+// {i, var_index[k]} on the rows of the free variables i, the Jacobian entries (r, var_index[k]) on the constraint rows — and zero
+// on slacks and fixed unknowns.  The source table: group g writes rhs[par[g]][dst[g]] = -(sum of its sources src[ptr[g] ..
+// ptr[g + 1]) in list order); a source is kind << 28 | triplet, kind 0 a Hessian triplet, 1 a Jacobian triplet.  Groups are sorted
+// by (parameter, KKT position) — consecutive threads of the gather write ascending positions —, the sources of a group ascend
+// (all Hessian triplets, then the Jacobian ones: a group holds one kind only, since a position is a variable's or a row's).
+constexpr int IPM_SENS_MAX_PAR = 32;   // parameters of one call (right-hand sides per instance of its substitution)
+struct IpmSensTable {
+  std::vector<int> ptr, par, dst, src;
+  int n_groups() const { return int(dst.size()); }
+};
+// Checks the parameter list (RPM_E_INVALID with *why: NULL list, n_par outside 1 .. IPM_SENS_MAX_PAR, an index outside [0, n), a
+// duplicate, a variable that is free in the plan) and builds the table.  hes_i / hes_j: the nnz_h Hessian triplets (either
+// triangle).  A pure function of its arguments.
+int ipm_sens_table(const IpmPlan& p, int nnz_h, const int* hes_i, const int* hes_j, int n_par, const int* var_index, IpmSensTable* t,
+                   std::string* why);
+
 }  // namespace rpm

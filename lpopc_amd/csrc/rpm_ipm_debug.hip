@@ -18,6 +18,7 @@ int debug_factor_solve(rpm_ipm* h, const double* store, double* rhs, size_t rhs_
   hipStream_t st = static_cast<hipStream_t>(dev_stream(h->eng->e));
   const size_t B = size_t(D.B);
   h->debug_started = false;
+  h->state_held = false;
   h->debug_ls = 0;
   inst.assign(B, IpmInst{});
   for (IpmInst& s : inst) s.refactor = 1;
@@ -167,6 +168,7 @@ int rpm_ipm_debug_lbfgs_step(rpm_ipm* h, int reset, const double* x, const doubl
   hipStream_t st = static_cast<hipStream_t>(dev_stream(h->eng->e));
   const size_t B = size_t(D.B), row = size_t(p.n) * sizeof(double), pitch = size_t(p.nv) * sizeof(double);
   h->debug_started = false;
+  h->state_held = false;
   h->debug_ls = 0;
   IPM_TRY(h, hipMemcpyAsync(D.xt, x, B * row, hipMemcpyHostToDevice, st));
   if (reset) {
@@ -257,6 +259,7 @@ int rpm_ipm_debug_start(rpm_ipm* h, int warm, const double* x, const double* lam
   }
   IPM_TRY(h, hipStreamSynchronize(st));
   h->solved = false;   // D.v, D.zL, D.zU and D.lam are about to hold a start state, not a solve's result
+  h->state_held = false;
   if ((rc = ipm_start(h, warm != 0, d_x, d_l, warm && z_L ? d_zL : nullptr, warm && z_L ? d_zU : nullptr, st))) return rc;
   IPM_TRY(h, hipStreamSynchronize(st));
   if (v_out) IPM_TRY(h, hipMemcpy(v_out, D.v, Bv * sizeof(double), hipMemcpyDeviceToHost));
@@ -270,6 +273,7 @@ int rpm_ipm_debug_start(rpm_ipm* h, int warm, const double* x, const double* lam
     if (status_out) status_out[bi] = inst[bi].status;
   }
   h->debug_started = true;
+  h->state_held = true;
   h->debug_ls = 0;
   return RPM_OK;
 }
@@ -379,6 +383,7 @@ int rpm_ipm_debug_line_search(rpm_ipm* h, int rounds, int n_filter, const double
   }
   const bool first = h->debug_ls == 1;
   h->debug_ls = 0;
+  h->state_held = false;   // trial points and, next, the update: no longer the state of a start or a pass
   const IpmLoop L{h, e, D, st, D.scal_on != 0};
   std::vector<double> rk(soc_rhs ? B * size_t(p.Nt_alloc) : 0);
   bool corrected = false;

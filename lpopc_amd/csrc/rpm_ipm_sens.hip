@@ -1,0 +1,392 @@
+// rpm_ipm_sens.hip — row f-2: first-order sensitivities of a solution to variables that are fixed in the solver's plan (the measured
+// initial states of a receding-horizon sweep, t0, tf), and the predictor that applies them.  Column k solves the solver's own
+// reduced system (13) — assembled and factored at the state the solver holds by the launchers of an iteration — against minus
+// column var_index[k] of the matrix's off-diagonal blocks; all columns of all instances go through ONE pass of the substitution
+// kernels (IpmDev::rhs_mult).  Three kernels of its own: the right-hand-side gather, the unpack and the predictor.  DESIGN.md f-2.
+#include <cstdint>
+#include <limits>
+#include <vector>
+
+#include "rpm_device_restore.hpp"
+#include "rpm_ipm_solver.hpp"
+
+using namespace rpm;
+
+namespace rpm {
+
+struct SensPars {   // the parameter list, by value
+  int n_par;
+  int idx[IPM_SENS_MAX_PAR];
+};
+
+// One thread per group of the source table (IpmSensTable, rpm_ipm.hpp): ws[par][instance][dst] = -(sum of the group's sources in list
+// order, one IEEE addition after the other).  Groups ascend by (parameter, position), so a wave writes ascending positions of
+// one right-hand side; what no group writes stays at the zero the work space was filled with.
+__global__ __launch_bounds__(256) void ipm_sens_rhs_kernel(IpmDev D, const int* __restrict__ ptr, const int* __restrict__ par,
+                                                          const int* __restrict__ dst, const int* __restrict__ src, int n_groups,
+                                                          double* __restrict__ ws) {
+  const int bi = blockIdx.y, g = blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= n_groups) return;
+  const double *hess = D.hess + size_t(bi) * D.nnz_h, *jac = D.jac + size_t(bi) * D.sv;
+  auto value = [&](int s) { return (s >> 28) ? jac[s & 0x0fffffff] : hess[s & 0x0fffffff]; };
+  const int j0 = ptr[g], j1 = ptr[g + 1];
+  double acc = value(src[j0]);
+  for (int j = j0 + 1; j < j1; ++j) acc += value(src[j]);
+  ws[(size_t(par[g]) * D.B + bi) * D.Nt + dst[g]] = -acc;
+}
+
+// KKT order -> dx (B x n_par x n) and dlambda (B x n_par x m, or NULL): free variables and rows through pos, 1 at the column's own
+// variable, 0 at every other fixed one; an instance whose record says it was left out (status != 0) gets NaN.
+__global__ __launch_bounds__(256) void ipm_sens_unpack_kernel(IpmDev D, SensPars P, const int* __restrict__ fixed,
+                                                             const double* __restrict__ ws, double* __restrict__ dx,
+                                                             double* __restrict__ dlam) {
+  const int bi = blockIdx.y, k = blockIdx.z, i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= D.n + D.m) return;
+  const bool left_out = D.inst[bi].status != 0;
+  const double nan = __longlong_as_double(0x7ff8000000000000ll);
+  const double* w = ws + (size_t(k) * D.B + bi) * D.Nt;
+  const size_t col = size_t(bi) * P.n_par + k;
+  if (i < D.n) {
+    const double v = fixed[i] ? (i == P.idx[k] ? 1.0 : 0.0) : w[D.pos[i]];
+    dx[col * D.n + i] = left_out ? nan : v;
+  } else if (dlam) {
+    const int r = i - D.n;
+    dlam[col * D.m + r] = left_out ? nan : w[D.pos[D.nv + r]];
+  }
+}
+
+// The predictor: out[b] = in[b], then for k ascending out[b] = out[b] + S[b][k] * delta[b][k] (product, then sum: the build keeps
+// them separate roundings), for x (blocks [0, xblocks) of the grid's x) and, when given, for lambda (the blocks after them).
+// Bandwidth bound — n_par rows of S are read per row written —: a thread takes two neighbouring entries and reads a row's pair
+// with one 16-byte load wherever the pair is 16-byte aligned (every row when the length is even; every other row otherwise).
+__global__ __launch_bounds__(256) void ipm_sens_apply_kernel(int n, int m, int n_par, int xblocks, const double* __restrict__ dx,
+                                                            const double* __restrict__ dlam, const double* __restrict__ delta,
+                                                            const double* __restrict__ x, double* __restrict__ x_out,
+                                                            const double* __restrict__ lam, double* __restrict__ lam_out) {
+  const int bi = blockIdx.y;
+  const bool is_x = int(blockIdx.x) < xblocks;
+  const int len = is_x ? n : m, blk = is_x ? int(blockIdx.x) : int(blockIdx.x) - xblocks;
+  const int i0 = (blk * int(blockDim.x) + int(threadIdx.x)) * 2;
+  if (i0 >= len) return;
+  const bool two = i0 + 1 < len;
+  const double* S = (is_x ? dx : dlam) + size_t(bi) * n_par * len + i0;
+  const double* in = (is_x ? x : lam) + size_t(bi) * len + i0;
+  double* out = (is_x ? x_out : lam_out) + size_t(bi) * len + i0;
+  const double* dl = delta + size_t(bi) * n_par;
+  double a0 = in[0], a1 = two ? in[1] : 0.0;
+  for (int k = 0; k < n_par; ++k) {
+    const double* row = S + size_t(k) * len;
+    const double d = dl[k];
+    if (two && (reinterpret_cast<uintptr_t>(row) & 15) == 0) {
+      const double2 s2 = *reinterpret_cast<const double2*>(row);
+      a0 = a0 + s2.x * d;
+      a1 = a1 + s2.y * d;
+    } else {
+      a0 = a0 + row[0] * d;
+      if (two) a1 = a1 + row[1] * d;
+    }
+  }
+  out[0] = a0;
+  if (two) out[1] = a1;
+}
+
+}  // namespace rpm
+
+namespace {
+
+int refuse(rpm_ipm* h, int code, const std::string& who, const std::string& why) {
+  h->err = who + ": " + why;
+  return code;
+}
+
+template <class T>
+int sens_room(rpm_ipm* h, T** p, size_t* cap, size_t count) {   // grown only; what growing replaces is freed (the stream is idle between calls)
+  if (*p && count <= *cap) return RPM_OK;
+  if (*p) {
+    IPM_TRY(h, hipFree(*p));
+    *p = nullptr;
+    *cap = 0;
+  }
+  IPM_TRY(h, hipMalloc(reinterpret_cast<void**>(p), (count ? count : 1) * sizeof(T)));
+  *cap = count;
+  return RPM_OK;
+}
+
+// every refusal of rpm_ipm_sensitivities[_dev] / rpm_ipm_debug_sensitivity_rhs, on the host, before anything is queued; *table: the
+// source table of the list (NULL: only checked)
+int sens_check(rpm_ipm* h, const std::string& who, int n_par, const int* var_index, bool need_state, IpmSensTable* table) {
+  const Engine& e = h->eng->e;
+  std::string why;
+  if (int rc = ipm_sens_table(h->plan, h->lbfgs ? 0 : e.nnz_h, e.hes_i.data(), e.hes_j.data(), n_par, var_index, table, &why))
+    return refuse(h, rc, who, why);
+  if (h->lbfgs) return refuse(h, RPM_E_UNSUPPORTED, who, "hessian-approximation = limited-memory: a quasi-Newton Hessian gives no sensitivities");
+  if (h->D.scal_on) return refuse(h, RPM_E_UNSUPPORTED, who, "not with nlp_scaling = 1");
+  if (need_state && !h->state_held)
+    return refuse(h, RPM_E_INVALID, who, "valid after a finished solve, or directly after rpm_ipm_debug_start / rpm_ipm_debug_pass on this solver");
+  return RPM_OK;
+}
+
+// the source table of the list on the device (kept while the list stays the same), the fixed pattern, the work space
+int sens_upload(rpm_ipm* h, int n_par, const int* var_index, const IpmSensTable& t) {
+  rpm_ipm::Sens& s = h->sens;
+  const IpmPlan& p = h->plan;
+  int rc;
+  if (!s.fixed) {
+    size_t cap = 0;
+    if ((rc = sens_room(h, &s.fixed, &cap, size_t(p.n)))) return rc;
+    IPM_TRY(h, hipMemcpy(s.fixed, p.fixed.data(), size_t(p.n) * sizeof(int), hipMemcpyHostToDevice));
+  }
+  const std::vector<int> list(var_index, var_index + n_par);
+  if (list != s.var_index || !s.table) {
+    const size_t G = size_t(t.n_groups());
+    std::vector<int> flat;   // ptr (G + 1), par (G), dst (G), src
+    flat.reserve(3 * G + 1 + t.src.size());
+    flat.insert(flat.end(), t.ptr.begin(), t.ptr.end());
+    flat.insert(flat.end(), t.par.begin(), t.par.end());
+    flat.insert(flat.end(), t.dst.begin(), t.dst.end());
+    flat.insert(flat.end(), t.src.begin(), t.src.end());
+    s.var_index.clear();
+    if ((rc = sens_room(h, &s.table, &s.table_cap, flat.size()))) return rc;
+    IPM_TRY(h, hipMemcpy(s.table, flat.data(), flat.size() * sizeof(int), hipMemcpyHostToDevice));
+    s.n_groups = int(G);
+    s.var_index = list;
+  }
+  return sens_room(h, &s.ws, &s.ws_cap, size_t(h->D.B) * size_t(n_par) * size_t(p.Nt_alloc));
+}
+
+// steps 1 and 3: g, the Jacobian and the exact Hessian at the state, then the n_par right-hand sides of every instance into the
+// (zeroed) work space
+int sens_evaluate_and_gather(rpm_ipm* h, const IpmLoop& L, int n_par) {
+  Engine& e = L.e;
+  IpmDev& D = L.D;
+  const rpm_ipm::Sens& s = h->sens;
+  int rc;
+  dev_forget_persistent(e);   // this evaluation writes all of D.jac, the constant block included (as the first one of a solve does)
+  ipm_launch_pack_x(D, L.st);
+  if ((rc = dev_eval_cons(e, D.xe, D.g, D.jac, 3 | 4 | 16, L.st))) return L.eng_fail(rc);
+  if ((rc = L.exact_hessian())) return rc;
+  IPM_TRY(h, hipMemsetAsync(s.ws, 0, size_t(D.B) * size_t(n_par) * size_t(D.Nt) * sizeof(double), L.st));
+  const int G = s.n_groups;
+  if (G > 0) {
+    const int *ptr = s.table, *par = ptr + G + 1, *dst = par + G, *src = dst + G;
+    hipLaunchKernelGGL(ipm_sens_rhs_kernel, dim3(unsigned((G + 255) / 256), unsigned(D.B)), dim3(256), 0, L.st, D, ptr, par, dst, src, G, s.ws);
+  }
+  return launch_check(h, "ipm_sens_rhs_kernel");
+}
+
+SensPars pars_of(int n_par, const int* var_index) {
+  SensPars P{};
+  P.n_par = n_par;
+  for (int k = 0; k < n_par; ++k) P.idx[k] = var_index[k];
+  return P;
+}
+
+// The whole of rpm_ipm_sensitivities_dev after its checks.  The solver's stream is idle on return, the instance records, the
+// counters and the statistics of the last solve are what they were.
+int sens_run(rpm_ipm* h, int n_par, const int* var_index, double* d_dx, double* d_dlambda, double* delta_w, int* info, void* stream) {
+  Engine& e = h->eng->e;
+  IpmDev& D = h->D;
+  hipStream_t st = static_cast<hipStream_t>(dev_stream(e));
+  const size_t B = size_t(D.B);
+  // ordering contract of rpm_ipm_solve_dev: after what the caller queued on `stream`, drained on return
+  IPM_TRY(h, hipEventRecord(h->ev[0], static_cast<hipStream_t>(stream)));
+  IPM_TRY(h, hipStreamWaitEvent(st, h->ev[0], 0));
+  // the records of the last solve (or of the hooks) are saved; live ones take their place around the factorisation: mode 0,
+  // delta_w = 0, asking for a factorisation — and status 5 kept, so that an instance with a non-finite state is left out
+  std::vector<IpmInst> saved(B), live(B, IpmInst{});
+  IPM_TRY(h, hipMemcpyAsync(saved.data(), D.inst, B * sizeof(IpmInst), hipMemcpyDeviceToHost, st));
+  IPM_TRY(h, hipStreamSynchronize(st));
+  for (size_t bi = 0; bi < B; ++bi) {
+    live[bi].mu = saved[bi].mu;
+    live[bi].refactor = 1;
+    live[bi].status = saved[bi].status == 5 ? 5 : 0;
+  }
+  const int keep_fact = h->total_factorizations, keep_cnt[4] = {h->h_cnt[0], h->h_cnt[1], h->h_cnt[2], h->h_cnt[3]};
+  const double keep_ms = h->factor_ms;
+  h->debug_ls = 0;   // (a direction rpm_ipm_debug_pass(3) left does not survive: D.K and D.rhs are rewritten)
+  const IpmLoop L{h, e, D, st, false};
+  auto body = [&]() -> int {
+    int rc;
+    IPM_TRY(h, hipMemcpyAsync(D.inst, live.data(), B * sizeof(IpmInst), hipMemcpyHostToDevice, st));
+    if ((rc = sens_evaluate_and_gather(h, L, n_par))) return rc;
+    if ((rc = L.factor_with_inertia_correction())) return rc;
+    IpmDev Ds = D;   // the substitution kernels on the work space: n_par right-hand sides per instance, same factors
+    Ds.rhs = h->sens.ws;
+    Ds.rhs_mult = n_par;
+    kkt_launch_solve(Ds, 1, st);
+    hipLaunchKernelGGL(ipm_sens_unpack_kernel, dim3(unsigned((D.n + D.m + 255) / 256), unsigned(D.B), unsigned(n_par)), dim3(256), 0, st, D,
+                       pars_of(n_par, var_index), h->sens.fixed, h->sens.ws, d_dx, d_dlambda);
+    if ((rc = launch_check(h, "sensitivity substitution"))) return rc;
+    IPM_TRY(h, hipMemcpyAsync(live.data(), D.inst, B * sizeof(IpmInst), hipMemcpyDeviceToHost, st));
+    return RPM_OK;
+  };
+  const int rc = body();
+  // put back, whatever happened
+  const std::string err = h->err;
+  hipError_t s1 = hipMemcpyAsync(D.inst, saved.data(), B * sizeof(IpmInst), hipMemcpyHostToDevice, st);
+  hipError_t s2 = hipMemcpyAsync(D.cnt, keep_cnt, 4 * sizeof(int), hipMemcpyHostToDevice, st);
+  hipError_t s3 = hipStreamSynchronize(st);
+  for (int i = 0; i < 4; ++i) h->h_cnt[i] = keep_cnt[i];
+  h->total_factorizations = keep_fact;
+  h->factor_ms = keep_ms;
+  if (rc) { h->err = err; return rc; }
+  IPM_TRY(h, s1);
+  IPM_TRY(h, s2);
+  IPM_TRY(h, s3);
+  for (size_t bi = 0; bi < B; ++bi) {
+    const bool ok = live[bi].status == 0;
+    if (delta_w) delta_w[bi] = ok ? live[bi].delta_w : std::numeric_limits<double>::quiet_NaN();
+    if (info) info[bi] = ok ? (live[bi].delta_w > 0.0 ? 1 : 0) : 2;
+  }
+  return RPM_OK;
+}
+
+struct ApplyArrays {
+  const double *dx, *dlambda, *delta, *x;
+  double* x_out;
+  const double* lambda;
+  double* lambda_out;
+  bool with_lambda() const { return dlambda && lambda && lambda_out; }
+};
+
+int apply_check(rpm_ipm* h, const std::string& who, int n_par, const int* var_index, const ApplyArrays& a) {
+  if (int rc = sens_check(h, who, n_par, var_index, false, nullptr)) return rc;
+  if (!a.dx || !a.delta || !a.x || !a.x_out) return refuse(h, RPM_E_INVALID, who, "dx, delta, x or x_out is NULL");
+  const size_t B = size_t(h->D.B), d8 = sizeof(double), P = size_t(n_par), n = size_t(h->plan.n), m = size_t(h->plan.m);
+  const bool lam = a.with_lambda();
+  const ByteRange in[5] = {{"dx", a.dx, B * P * n * d8}, {"delta", a.delta, B * P * d8}, {"x", a.x, B * n * d8},
+                           {"dlambda", lam ? a.dlambda : nullptr, B * P * m * d8}, {"lambda", lam ? a.lambda : nullptr, B * m * d8}};
+  const ByteRange out[2] = {{"x_out", a.x_out, B * n * d8}, {"lambda_out", lam ? a.lambda_out : nullptr, B * m * d8}};
+  Engine& e = h->eng->e;
+  const int rc = step_overlap(e, who + ": ", out, 2, in, 5);   // every output against every input and the other output
+  if (rc) h->err = e.err;
+  return rc;
+}
+
+int apply_launch(rpm_ipm* h, int n_par, const ApplyArrays& a, hipStream_t stream) {
+  const IpmDev& D = h->D;
+  const bool lam = a.with_lambda() && D.m > 0;
+  const int xblocks = (D.n + 511) / 512, lblocks = lam ? (D.m + 511) / 512 : 0;   // two entries per thread
+  hipLaunchKernelGGL(ipm_sens_apply_kernel, dim3(unsigned(xblocks + lblocks), unsigned(D.B)), dim3(256), 0, stream, D.n, D.m, n_par, xblocks,
+                     a.dx, a.dlambda, a.delta, a.x, a.x_out, a.lambda, a.lambda_out);
+  return launch_check(h, "ipm_sens_apply_kernel");
+}
+
+}  // namespace
+
+extern "C" {
+
+int rpm_ipm_initial_state_variables(rpm_ipm* h, int phase, int* var_index) {
+  if (!h) return RPM_E_INVALID;
+  const Engine& e = h->eng->e;
+  const std::string who = "rpm_ipm_initial_state_variables";
+  if (phase < 0 || phase >= e.P) return refuse(h, RPM_E_INVALID, who, "phase " + std::to_string(phase) + " is out of range");
+  if (!var_index) return refuse(h, RPM_E_INVALID, who, "var_index is NULL");
+  const PhaseHost& p = e.ph[size_t(phase)];
+  for (int j = 0; j < p.nx; ++j) var_index[j] = p.var0 + j * (p.N + 1);
+  return RPM_OK;
+}
+
+int rpm_ipm_sensitivities_dev(rpm_ipm* h, int n_par, const int* var_index, double* d_dx, double* d_dlambda, double* delta_w, int* info,
+                              void* stream) {
+  if (!h) return RPM_E_INVALID;
+  const std::string who = "rpm_ipm_sensitivities";
+  if (!d_dx) return refuse(h, RPM_E_INVALID, who, var_index ? "dx is NULL" : "var_index is NULL");
+  IpmSensTable t;
+  int rc = sens_check(h, who, n_par, var_index, true, &t);
+  if (rc) return rc;
+  DeviceRestore restore;
+  if ((rc = dev_bind(h->eng->e))) { h->err = h->eng->e.err; return rc; }
+  if ((rc = sens_upload(h, n_par, var_index, t))) return rc;
+  return sens_run(h, n_par, var_index, d_dx, d_dlambda, delta_w, info, stream);
+}
+
+int rpm_ipm_sensitivities(rpm_ipm* h, int n_par, const int* var_index, double* dx, double* dlambda, double* delta_w, int* info) {
+  if (!h) return RPM_E_INVALID;
+  const std::string who = "rpm_ipm_sensitivities";
+  if (!dx) return refuse(h, RPM_E_INVALID, who, var_index ? "dx is NULL" : "var_index is NULL");
+  IpmSensTable t;
+  int rc = sens_check(h, who, n_par, var_index, true, &t);
+  if (rc) return rc;
+  DeviceRestore restore;
+  if ((rc = dev_bind(h->eng->e))) { h->err = h->eng->e.err; return rc; }
+  if ((rc = sens_upload(h, n_par, var_index, t))) return rc;
+  const size_t B = size_t(h->D.B), Pn = size_t(n_par) * h->plan.n, Pm = size_t(n_par) * h->plan.m;
+  if ((rc = sens_room(h, &h->sens.block, &h->sens.block_cap, B * (Pn + Pm)))) return rc;
+  double *d_dx = h->sens.block, *d_dl = dlambda ? d_dx + B * Pn : nullptr;
+  if ((rc = sens_run(h, n_par, var_index, d_dx, d_dl, delta_w, info, dev_stream(h->eng->e)))) return rc;
+  IPM_TRY(h, hipMemcpy(dx, d_dx, B * Pn * sizeof(double), hipMemcpyDeviceToHost));
+  if (dlambda && Pm) IPM_TRY(h, hipMemcpy(dlambda, d_dl, B * Pm * sizeof(double), hipMemcpyDeviceToHost));
+  return RPM_OK;
+}
+
+int rpm_ipm_debug_sensitivity_rhs(rpm_ipm* h, int n_par, const int* var_index, double* rhs) {
+  if (!h) return RPM_E_INVALID;
+  const std::string who = "rpm_ipm_debug_sensitivity_rhs";
+  if (!rhs) return refuse(h, RPM_E_INVALID, who, var_index ? "rhs is NULL" : "var_index is NULL");
+  IpmSensTable t;
+  int rc = sens_check(h, who, n_par, var_index, true, &t);
+  if (rc) return rc;
+  DeviceRestore restore;
+  Engine& e = h->eng->e;
+  if ((rc = dev_bind(e))) { h->err = e.err; return rc; }
+  if ((rc = sens_upload(h, n_par, var_index, t))) return rc;
+  IpmDev& D = h->D;
+  const IpmPlan& p = h->plan;
+  hipStream_t st = static_cast<hipStream_t>(dev_stream(e));
+  const IpmLoop L{h, e, D, st, false};
+  if ((rc = sens_evaluate_and_gather(h, L, n_par))) return rc;
+  const size_t B = size_t(D.B), P = size_t(n_par), Nt = size_t(p.Nt), Na = size_t(p.Nt_alloc);
+  std::vector<double> w(B * P * Na);
+  IPM_TRY(h, hipMemcpyAsync(w.data(), h->sens.ws, w.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+  IPM_TRY(h, hipStreamSynchronize(st));
+  for (size_t bi = 0; bi < B; ++bi)
+    for (size_t k = 0; k < P; ++k)
+      for (size_t a = 0; a < Nt; ++a) rhs[(bi * P + k) * Nt + a] = w[(k * B + bi) * Na + size_t(p.pos[a])];
+  return RPM_OK;
+}
+
+int rpm_ipm_apply_sensitivities_dev(rpm_ipm* h, int n_par, const int* var_index, const double* d_dx, const double* d_dlambda,
+                                    const double* d_delta, const double* d_x, double* d_x_out, const double* d_lambda, double* d_lambda_out,
+                                    void* stream) {
+  if (!h) return RPM_E_INVALID;
+  const ApplyArrays a{d_dx, d_dlambda, d_delta, d_x, d_x_out, d_lambda, d_lambda_out};
+  if (int rc = apply_check(h, "rpm_ipm_apply_sensitivities_dev", n_par, var_index, a)) return rc;
+  return apply_launch(h, n_par, a, static_cast<hipStream_t>(stream));
+}
+
+int rpm_ipm_apply_sensitivities(rpm_ipm* h, int n_par, const int* var_index, const double* dx, const double* dlambda, const double* delta,
+                                const double* x, double* x_out, const double* lambda, double* lambda_out) {
+  if (!h) return RPM_E_INVALID;
+  const ApplyArrays a{dx, dlambda, delta, x, x_out, lambda, lambda_out};
+  int rc = apply_check(h, "rpm_ipm_apply_sensitivities", n_par, var_index, a);
+  if (rc) return rc;
+  DeviceRestore restore;
+  Engine& e = h->eng->e;
+  if ((rc = dev_bind(e))) { h->err = e.err; return rc; }
+  hipStream_t st = static_cast<hipStream_t>(dev_stream(e));
+  const bool lam = a.with_lambda();
+  const size_t B = size_t(h->D.B), P = size_t(n_par), n = size_t(h->plan.n), m = size_t(h->plan.m), d8 = sizeof(double);
+  // the block: dx, delta, x, x_out, then dlambda, lambda, lambda_out (every piece an even number of doubles from the start,
+  // padded, so that each keeps the base's 16-byte alignment)
+  auto even = [](size_t c) { return (c + 1) & ~size_t(1); };
+  const size_t o_delta = even(B * P * n), o_x = o_delta + even(B * P), o_xo = o_x + even(B * n), o_dl = o_xo + even(B * n);
+  const size_t o_l = o_dl + even(B * P * m), o_lo = o_l + even(B * m), total = o_lo + even(B * m);
+  if ((rc = sens_room(h, &h->sens.block, &h->sens.block_cap, total))) return rc;
+  double* b = h->sens.block;
+  IPM_TRY(h, hipMemcpyAsync(b, dx, B * P * n * d8, hipMemcpyHostToDevice, st));
+  IPM_TRY(h, hipMemcpyAsync(b + o_delta, delta, B * P * d8, hipMemcpyHostToDevice, st));
+  IPM_TRY(h, hipMemcpyAsync(b + o_x, x, B * n * d8, hipMemcpyHostToDevice, st));
+  if (lam && m) {
+    IPM_TRY(h, hipMemcpyAsync(b + o_dl, dlambda, B * P * m * d8, hipMemcpyHostToDevice, st));
+    IPM_TRY(h, hipMemcpyAsync(b + o_l, lambda, B * m * d8, hipMemcpyHostToDevice, st));
+  }
+  const ApplyArrays dv{b, lam ? b + o_dl : nullptr, b + o_delta, b + o_x, b + o_xo, lam ? b + o_l : nullptr, lam ? b + o_lo : nullptr};
+  if ((rc = apply_launch(h, n_par, dv, st))) return rc;
+  IPM_TRY(h, hipMemcpyAsync(x_out, b + o_xo, B * n * d8, hipMemcpyDeviceToHost, st));
+  if (lam && m) IPM_TRY(h, hipMemcpyAsync(lambda_out, b + o_lo, B * m * d8, hipMemcpyDeviceToHost, st));
+  IPM_TRY(h, hipStreamSynchronize(st));
+  return RPM_OK;
+}
+
+}  // extern "C"

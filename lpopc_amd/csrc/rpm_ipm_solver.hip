@@ -528,6 +528,7 @@ int ipm_solve_dev(rpm_ipm* h, bool warm, double* d_x, double* d_lambda, double* 
   hipStream_t st = static_cast<hipStream_t>(dev_stream(e));
   h->lb_iterations = 0;
   h->debug_started = false;
+  h->state_held = false;
   h->debug_ls = 0;
   h->total_factorizations = h->total_iterations = h->total_trials = h->total_soc = 0;
   h->factor_ms = h->solve_ms = 0.0;

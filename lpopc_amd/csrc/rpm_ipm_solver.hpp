@@ -1,5 +1,5 @@
-// rpm_ipm_solver.hpp — private to rpm_ipm_solver.hip (create, options, the loop, the solve entry points) and rpm_ipm_debug.hip
-// (the test hooks): the solver object behind the rpm_ipm handle, the few helpers both units use and the steps of the solve loop
+// rpm_ipm_solver.hpp — private to rpm_ipm_solver.hip (create, options, the loop, the solve entry points), rpm_ipm_debug.hip
+// (the test hooks) and rpm_ipm_sens.hip (solution sensitivities): the solver object behind the rpm_ipm handle, the few helpers both units use and the steps of the solve loop
 // (IpmLoop), which the hooks rpm_ipm_debug_pass, rpm_ipm_debug_line_search and rpm_ipm_debug_update run one pass of.
 #pragma once
 #include <algorithm>
@@ -34,9 +34,22 @@ struct rpm_ipm {
   int debug_ls = 0;              // 1: rpm_ipm_debug_pass(stage 3) left instances running, rpm_ipm_debug_line_search may follow; 2: it has run
                                  // (it may run again, or rpm_ipm_debug_update); 0: neither
   double* d_host_form = nullptr; // the host-pointer entry points' device copies of x, lambda, z_L, z_U (B x (3 n + m)), on first use
+  bool state_held = false;       // D.v, D.lam, D.zL, D.zU, D.vl, D.vu hold a state sensitivities may be taken at: a solve has finished, or
+                                 // rpm_ipm_debug_start / rpm_ipm_debug_pass was the last call to touch it
+  // rpm_ipm_sens.hip: its work space (B x n_par x Nt_alloc right-hand sides), the source table of the last parameter list, the
+  // plan's fixed pattern and the host-pointer forms' device block; each on first use, kept, grown only
+  struct Sens {
+    double *ws = nullptr, *block = nullptr;
+    int *table = nullptr, *fixed = nullptr;
+    size_t ws_cap = 0, block_cap = 0, table_cap = 0;
+    int n_groups = 0;
+    std::vector<int> var_index;    // the list `table` was built for
+  } sens;
   ~rpm_ipm() {
     if (attached && eng && eng->e.ipm_attached > 0) eng->e.ipm_attached -= 1;
     for (void* p : allocs) (void)hipFree(p);
+    for (void* p : {static_cast<void*>(sens.ws), static_cast<void*>(sens.block), static_cast<void*>(sens.table), static_cast<void*>(sens.fixed)})
+      if (p) (void)hipFree(p);
     if (h_cnt) (void)hipHostFree(h_cnt);
     for (hipEvent_t e2 : ev)
       if (e2) (void)hipEventDestroy(e2);
@@ -244,6 +257,7 @@ struct IpmLoop {
       if (kkt_error) kkt_error[bi] = S.err0;
     }
     h->solved = true;
+    h->state_held = true;
     return RPM_OK;
   }
 };

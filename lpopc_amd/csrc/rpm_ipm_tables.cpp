@@ -1,6 +1,7 @@
 // rpm_ipm_tables.cpp — the index tables rpm_ipm_create uploads beside the plan (host side of row f-2, see rpm_ipm.hpp): the
 // factorisation's sub-problems, the long Jacobian columns, the ascending list of every structural slot (one-pass fill) and the
-// per-interval-block tables of the fill fused into kkt_factor_dense_kernel.  Pure functions of the plan: no engine, no device.
+// per-interval-block tables of the fill fused into kkt_factor_dense_kernel; and the source table of the sensitivity right-hand sides
+// (rpm_ipm_sens.hip), with the check of its parameter list.  Pure functions of the plan: no engine, no device.
 #include <algorithm>
 #include <unordered_map>
 
@@ -118,6 +119,50 @@ IpmFusedFill ipm_fused_fill(const IpmSubList& s, const IpmFillList& fill) {
     if (!skip[size_t(c)]) t.live.push_back(c);
   t.built = true;
   return t;
+}
+
+int ipm_sens_table(const IpmPlan& p, int nnz_h, const int* hes_i, const int* hes_j, int n_par, const int* var_index, IpmSensTable* t,
+                   std::string* why) {
+  auto refuse = [&](const std::string& msg) { if (why) *why = msg; return int(RPM_E_INVALID); };
+  if (!var_index) return refuse("var_index is NULL");
+  if (n_par < 1 || n_par > IPM_SENS_MAX_PAR)
+    return refuse("n_par = " + std::to_string(n_par) + " is outside 1 .. " + std::to_string(IPM_SENS_MAX_PAR));
+  std::vector<int> par_of(size_t(p.n), -1);
+  for (int k = 0; k < n_par; ++k) {
+    const int j = var_index[k];
+    if (j < 0 || j >= p.n) return refuse("var_index[" + std::to_string(k) + "] = " + std::to_string(j) + " is outside the " + std::to_string(p.n) + " variables");
+    if (par_of[size_t(j)] >= 0) return refuse("variable " + std::to_string(j) + " is listed twice (var_index[" + std::to_string(par_of[size_t(j)]) + "] and [" + std::to_string(k) + "])");
+    if (!p.fixed[size_t(j)]) return refuse("variable " + std::to_string(j) + " (var_index[" + std::to_string(k) + "]) is free in the solver's plan: sensitivities are taken to fixed variables");
+    par_of[size_t(j)] = k;
+  }
+  if (!t) return RPM_OK;   // the list alone was to be checked (the predictor's entry points)
+  struct Ent { int par, dst, src; };
+  std::vector<Ent> ents;
+  // Hessian triplets {i, j_k} with i free, each once per parameter it touches (two fixed ends: nothing, for either)
+  for (int e = 0; e < nnz_h; ++e) {
+    const int a = hes_i[e], c = hes_j[e];
+    if (par_of[size_t(a)] >= 0 && !p.fixed[size_t(c)]) ents.push_back(Ent{par_of[size_t(a)], p.pos[size_t(c)], (0 << 28) | e});
+    if (par_of[size_t(c)] >= 0 && !p.fixed[size_t(a)]) ents.push_back(Ent{par_of[size_t(c)], p.pos[size_t(a)], (0 << 28) | e});
+  }
+  // the Jacobian column of every parameter (jt_*: entries of a column in triplet order)
+  for (int k = 0; k < n_par; ++k)
+    for (int q = p.jt_ptr[size_t(var_index[k])]; q < p.jt_ptr[size_t(var_index[k]) + 1]; ++q)
+      ents.push_back(Ent{k, p.pos[size_t(p.nv + p.jt_row[size_t(q)])], (1 << 28) | p.jt_ent[size_t(q)]});
+  std::sort(ents.begin(), ents.end(), [](const Ent& x, const Ent& y) {
+    return x.par != y.par ? x.par < y.par : (x.dst != y.dst ? x.dst < y.dst : x.src < y.src);
+  });
+  IpmSensTable out;
+  for (size_t i = 0; i < ents.size(); ++i) {
+    if (i == 0 || ents[i].par != ents[i - 1].par || ents[i].dst != ents[i - 1].dst) {
+      out.ptr.push_back(int(i));
+      out.par.push_back(ents[i].par);
+      out.dst.push_back(ents[i].dst);
+    }
+    out.src.push_back(ents[i].src);
+  }
+  out.ptr.push_back(int(ents.size()));
+  *t = std::move(out);
+  return RPM_OK;
 }
 
 }  // namespace rpm

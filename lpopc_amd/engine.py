@@ -49,6 +49,8 @@ ABI_SYMBOLS = [
     "rpm_ipm_get_stats", "rpm_ipm_get_subproblems", "rpm_ipm_get_trace", "rpm_ipm_get_restorations", "rpm_ipm_get_kernel_times", "rpm_ipm_solve", "rpm_ipm_solve_dev", "rpm_ipm_get_permutation", "rpm_ipm_debug_solve", "rpm_ipm_debug_solve_dense", "rpm_ipm_debug_slot",
     "rpm_ipm_debug_lbfgs_step", "rpm_ipm_debug_lbfgs_state", "rpm_ipm_debug_lbfgs_solve", "rpm_ipm_debug_pass",
     "rpm_ipm_debug_line_search", "rpm_ipm_debug_update",
+    "rpm_ipm_initial_state_variables", "rpm_ipm_sensitivities_dev", "rpm_ipm_sensitivities", "rpm_ipm_apply_sensitivities_dev",
+    "rpm_ipm_apply_sensitivities", "rpm_ipm_debug_sensitivity_rhs", "rpm_sweep_sensitivities",
 ]
 
 
@@ -216,6 +218,13 @@ def lib(path=None):
     L.rpm_sweep_get_stats.argtypes = [vp, ip, ip, ip]
     L.rpm_sweep_solve_warm.argtypes = [vp, dp, dp, dp, dp, dp, ip, ip, dp]
     L.rpm_sweep_get_bound_multipliers.argtypes = [vp, dp, dp]
+    L.rpm_ipm_initial_state_variables.argtypes = [vp, C.c_int, ip]
+    L.rpm_ipm_sensitivities_dev.argtypes = [vp, C.c_int, ip, vp, vp, dp, ip, vp]
+    L.rpm_ipm_sensitivities.argtypes = [vp, C.c_int, ip, dp, dp, dp, ip]
+    L.rpm_ipm_apply_sensitivities_dev.argtypes = [vp, C.c_int, ip] + [vp] * 8
+    L.rpm_ipm_apply_sensitivities.argtypes = [vp, C.c_int, ip] + [dp] * 7
+    L.rpm_ipm_debug_sensitivity_rhs.argtypes = [vp, C.c_int, ip, dp]
+    L.rpm_sweep_sensitivities.argtypes = [vp, C.c_int, ip, dp, dp, dp, ip]
     _LIBS[so] = L
     if so == _SO:
         _LIB = L
@@ -1062,6 +1071,74 @@ class BatchedIPM:
     def bound_multipliers_dev(self, d_z_L, d_z_U, stream=None):
         self._chk(self._L.rpm_ipm_get_bound_multipliers_dev(self._h, C.c_void_p(d_z_L.data_ptr()), C.c_void_p(d_z_U.data_ptr()),
                                                             NLPEngine._stream(stream)))
+
+    # ---- solution sensitivities to fixed variables (rpm_ipm_sensitivities, include/rpm_hip.h) --------------------------
+
+    def initial_state_variables(self, phase):
+        """The variables set_initial_states writes: x_state0 + j (N + 1), j < nx of `phase`."""
+        if not 0 <= int(phase) < self._e.n_phases:
+            raise RpmError(RPM_E_INVALID, "phase %d is out of range" % int(phase))
+        out = np.zeros(self._e._desc.phases[int(phase)].nx, dtype=np.int32)
+        self._chk(self._L.rpm_ipm_initial_state_variables(self._h, int(phase), _ip(out)))
+        return out
+
+    @staticmethod
+    def _var_index(var_index):
+        return None if var_index is None else np.ascontiguousarray(var_index, dtype=np.int32).ravel()
+
+    def sensitivities(self, var_index, want_lambda=True):
+        """First-order sensitivities of the solution the solver holds to the fixed variables `var_index` (P of them):
+        dict(dx (B, P, n), dlambda (B, P, m) or None, delta_w (B), info (B): 0 computed, 1 computed with a regularised matrix,
+        2 left out (NaN blocks))."""
+        B, n, m = self._e.n_instances, self._e.n, self._e.m
+        vi = self._var_index(var_index)
+        P = 0 if vi is None else vi.size
+        out = {"dx": np.zeros((B, P, n)), "dlambda": np.zeros((B, P, m)) if want_lambda else None, "delta_w": np.zeros(B),
+               "info": np.zeros(B, dtype=np.int32)}
+        self._chk(self._L.rpm_ipm_sensitivities(self._h, P, None if vi is None else _ip(vi), _dp(out["dx"]),
+                                                _dp(out["dlambda"]) if want_lambda else None, _dp(out["delta_w"]), _ip(out["info"])))
+        return out
+
+    def sensitivities_dev(self, var_index, d_dx, d_dlambda=None, stream=None):
+        """The device-resident form on torch CUDA tensors (float64): d_dx (B, P, n), d_dlambda (B, P, m) or None, written when
+        the call returns -> dict(delta_w, info)."""
+        B = self._e.n_instances
+        vi = self._var_index(var_index)
+        out = {"delta_w": np.zeros(B), "info": np.zeros(B, dtype=np.int32)}
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        self._chk(self._L.rpm_ipm_sensitivities_dev(self._h, 0 if vi is None else vi.size, None if vi is None else _ip(vi), ptr(d_dx),
+                                                    ptr(d_dlambda), _dp(out["delta_w"]), _ip(out["info"]), NLPEngine._stream(stream)))
+        return out
+
+    def apply_sensitivities(self, var_index, dx, delta, x, dlambda=None, lam=None):
+        """The predictor x + sum_k dx[:, k] delta[:, k] (and lambda likewise when dlambda and lam are given), nothing clipped:
+        -> x_out (B, n), or (x_out, lambda_out)."""
+        B, n, m = self._e.n_instances, self._e.n, self._e.m
+        vi = self._var_index(var_index)
+        f = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float64)
+        dx, delta, x, dlambda, lam = f(dx), f(delta), f(x), f(dlambda), f(lam)
+        x_out = np.zeros((B, n))
+        lam_out = np.zeros((B, m)) if dlambda is not None and lam is not None else None
+        opt = lambda a: None if a is None else _dp(a)
+        self._chk(self._L.rpm_ipm_apply_sensitivities(self._h, 0 if vi is None else vi.size, None if vi is None else _ip(vi), opt(dx),
+                                                      opt(dlambda), opt(delta), opt(x), _dp(x_out), opt(lam), opt(lam_out)))
+        return x_out if lam_out is None else (x_out, lam_out)
+
+    def apply_sensitivities_dev(self, var_index, d_dx, d_delta, d_x, d_x_out, d_dlambda=None, d_lambda=None, d_lambda_out=None, stream=None):
+        """One launch on `stream` (torch's current one by default) over torch CUDA tensors; capturable into a graph."""
+        vi = self._var_index(var_index)
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        self._chk(self._L.rpm_ipm_apply_sensitivities_dev(self._h, 0 if vi is None else vi.size, None if vi is None else _ip(vi), ptr(d_dx),
+                                                          ptr(d_dlambda), ptr(d_delta), ptr(d_x), ptr(d_x_out), ptr(d_lambda),
+                                                          ptr(d_lambda_out), NLPEngine._stream(stream)))
+
+    def debug_sensitivity_rhs(self, var_index):
+        """Test hook: the right-hand sides of sensitivities() -> (B, P, kkt_order), unknown order (variables, slacks, multipliers)."""
+        vi = self._var_index(var_index)
+        P = 0 if vi is None else vi.size
+        rhs = np.zeros((self._e.n_instances, P, self.info()["kkt_order"]))
+        self._chk(self._L.rpm_ipm_debug_sensitivity_rhs(self._h, P, None if vi is None else _ip(vi), _dp(rhs)))
+        return rhs
 
     def debug_start(self, x0, lam0=None, z0=None, warm=True):
         """The state the iteration loop starts from (rpm_ipm_debug_start; no step is taken): dict(v (B, nv): x then the slacks,
