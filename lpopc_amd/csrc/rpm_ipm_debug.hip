@@ -15,48 +15,45 @@ namespace {
 // otherwise the plain factor + solve of every instance, then the pivot signs summed into the records.
 int debug_factor_solve(rpm_ipm* h, const double* store, double* rhs, size_t rhs_len, bool limited_memory, std::vector<IpmInst>& inst) {
   IpmDev& D = h->D;
-  hipStream_t st = static_cast<hipStream_t>(dev_stream(h->eng->e));
+  hipStream_t st = ipm_stream(h);
   const size_t B = size_t(D.B);
-  h->debug_started = false;
-  h->state_held = false;
-  h->debug_ls = 0;
+  h->hold.overwritten();
   inst.assign(B, IpmInst{});
   for (IpmInst& s : inst) s.refactor = 1;
-  IPM_TRY(h, hipMemcpyAsync(D.inst, inst.data(), B * sizeof(IpmInst), hipMemcpyHostToDevice, st));
+  int rc = ipm_upload_records(h, inst);
+  if (rc) return rc;
   IPM_TRY(h, hipMemcpyAsync(D.K, store, B * size_t(h->plan.storage()) * sizeof(double), hipMemcpyHostToDevice, st));
   IPM_TRY(h, hipMemcpyAsync(D.rhs, rhs, B * rhs_len * sizeof(double), hipMemcpyHostToDevice, st));
-  const int df_keep = D.df_on;
-  D.df_on = 0;
-  int rc;
-  if (limited_memory) {
-    kkt_launch_factor(D, h->factor_mt, h->factor_lds, st);
-    lb_launch_columns_and_solve(D, st);
-    lb_launch_small(D, st);
-    kkt_launch_solve(D, 1, st);
-    lb_launch_correct(D, 1, st);
-    rc = launch_check(h, "limited-memory solve");
-  } else {
-    rc = factor_and_solve_launch(h, st, true, true, 0);
-    if (!rc) ipm_launch_inertia(D, st);
+  {
+    const IpmFusedFillOff on_the_storage(D);
+    if (limited_memory) {
+      kkt_launch_factor(D, h->factor_mt, h->factor_lds, st);
+      lb_launch_columns_and_solve(D, st);
+      lb_launch_small(D, st);
+      kkt_launch_solve(D, 1, st);
+      lb_launch_correct(D, 1, st);
+      rc = launch_check(h, "limited-memory solve");
+    } else {
+      rc = factor_and_solve_launch(h, st, true, true, 0);
+      if (!rc) ipm_launch_inertia(D, st);
+    }
   }
-  D.df_on = df_keep;
   if (rc) return rc;
-  IPM_TRY(h, hipStreamSynchronize(st));
-  IPM_TRY(h, hipMemcpy(rhs, D.rhs, B * rhs_len * sizeof(double), hipMemcpyDeviceToHost));
-  IPM_TRY(h, hipMemcpy(inst.data(), D.inst, B * sizeof(IpmInst), hipMemcpyDeviceToHost));
-  return RPM_OK;
+  IPM_TRY(h, hipMemcpyAsync(rhs, D.rhs, B * rhs_len * sizeof(double), hipMemcpyDeviceToHost, st));
+  return ipm_download_records(h, inst);
 }
 
-// right-hand sides in unknown order (B x Nt) <-> vectors in KKT order (B x Nt_alloc)
-std::vector<double> to_kkt_order(const IpmPlan& p, size_t B, const double* rhs) {
+// the same for right-hand sides (B x Nt) and solutions in unknown order: into KKT order (B x Nt_alloc) and back
+int debug_factor_solve_unknown_order(rpm_ipm* h, const std::vector<double>& store, const double* rhs, double* sol, bool limited_memory,
+                                     std::vector<IpmInst>& inst) {
+  const IpmPlan& p = h->plan;
+  const size_t B = size_t(h->D.B);
   std::vector<double> r(B * size_t(p.Nt_alloc), 0.0);
   for (size_t bi = 0; bi < B; ++bi)
     for (size_t a = 0; a < size_t(p.Nt); ++a) r[bi * p.Nt_alloc + p.pos[a]] = rhs[bi * p.Nt + a];
-  return r;
-}
-void from_kkt_order(const IpmPlan& p, size_t B, const std::vector<double>& r, double* sol) {
-  for (size_t bi = 0; bi < B; ++bi)
-    for (size_t a = 0; a < size_t(p.Nt); ++a) sol[bi * p.Nt + a] = r[bi * p.Nt_alloc + p.pos[a]];
+  if (int rc = debug_factor_solve(h, store.data(), r.data(), size_t(p.Nt_alloc), limited_memory, inst)) return rc;
+  ipm_from_kkt_order(p, B, 1, r.data(), sol);
+  return RPM_OK;
 }
 void pivot_signs(const std::vector<IpmInst>& inst, int* n_pos, int* n_neg) {
   for (size_t bi = 0; bi < inst.size(); ++bi) {
@@ -79,9 +76,14 @@ void flat_record(const IpmInst& S, double* r) {
   static_assert(sizeof(v) / sizeof(v[0]) == RPM_IPM_RECORD_DOUBLES, "RPM_IPM_RECORD_DOUBLES");
   std::memcpy(r, v, sizeof(v));
 }
+// the instance records down into `inst` and, flattened, into `record` (NULL: not wanted)
+int download_flat_records(rpm_ipm* h, std::vector<IpmInst>& inst, double* record) {
+  if (int rc = ipm_download_records(h, inst)) return rc;
+  for (size_t bi = 0; record && bi < inst.size(); ++bi) flat_record(inst[bi], record + bi * RPM_IPM_RECORD_DOUBLES);
+  return RPM_OK;
+}
 int no_slot(rpm_ipm* h, const char* who, long long a, long long c) {
-  h->err = std::string(who) + ": entry (" + std::to_string(a) + ", " + std::to_string(c) + ") has no slot in the layout";
-  return RPM_E_INVALID;
+  return ipm_refuse(h, RPM_E_INVALID, who, "entry (" + std::to_string(a) + ", " + std::to_string(c) + ") has no slot in the layout");
 }
 }  // namespace
 
@@ -92,7 +94,7 @@ extern "C" {
 int rpm_ipm_debug_solve(rpm_ipm* h, const double* k_storage, const double* rhs, double* sol, int* n_pos, int* n_neg) {
   if (!h || !k_storage || !rhs || !sol) return RPM_E_INVALID;
   const IpmPlan& p = h->plan;
-  if (p.nd) { h->err = "rpm_ipm_debug_solve takes the band + border storage; with nested dissection use rpm_ipm_debug_solve_dense"; return RPM_E_UNSUPPORTED; }
+  if (p.nd) return ipm_refuse(h, RPM_E_UNSUPPORTED, "", "rpm_ipm_debug_solve takes the band + border storage; with nested dissection use rpm_ipm_debug_solve_dense");
   std::vector<IpmInst> inst;
   std::memcpy(sol, rhs, size_t(h->D.B) * p.Nt * sizeof(double));
   int rc = debug_factor_solve(h, k_storage, sol, size_t(p.Nt), false, inst);
@@ -122,9 +124,8 @@ int rpm_ipm_debug_solve_dense(rpm_ipm* h, const double* k_dense, const double* r
         if (o < 0) return no_slot(h, "rpm_ipm_debug_solve_dense", (long long)a, (long long)c);
         store[bi * size_t(p.storage()) + size_t(o)] = v;
       }
-  std::vector<double> r = to_kkt_order(p, B, rhs);
   std::vector<IpmInst> inst;
-  int rc = debug_factor_solve(h, store.data(), r.data(), size_t(p.Nt_alloc), false, inst);
+  int rc = debug_factor_solve_unknown_order(h, store, rhs, sol, false, inst);
   if (rc) return rc;
 #ifdef IPM_TIMING
   // kkt_factor_dense_kernel (build with -DIPM_TIMING_SUB=<out of range>): tile wave 0 and the diagonal wave of interval block 0
@@ -134,7 +135,6 @@ int rpm_ipm_debug_solve_dense(rpm_ipm* h, const double* k_dense, const double* r
   fprintf(stderr, "left-looking phases of instance 0 [100 MHz ticks]: T %lld  k-loop %lld  diag %lld  panel %lld  corner %lld  tail %lld\n",
           inst[0].dbg[0], inst[0].dbg[1], inst[0].dbg[2], inst[0].dbg[3], inst[0].dbg[4], inst[0].dbg[5]);
 #endif
-  from_kkt_order(p, B, r, sol);
   pivot_signs(inst, n_pos, n_neg);
   return RPM_OK;
 }
@@ -162,14 +162,12 @@ int rpm_ipm_get_permutation(rpm_ipm* h, int* pos, int capacity) {
 int rpm_ipm_debug_lbfgs_step(rpm_ipm* h, int reset, const double* x, const double* glag_new, const double* glag_old, const int* mode,
                              const int* status) {
   if (!h || !x || !glag_new || !glag_old) return RPM_E_INVALID;
-  if (!h->lbfgs) { h->err = "rpm_ipm_debug_lbfgs_step: the solver was created with the exact Hessian"; return RPM_E_UNSUPPORTED; }
+  if (!h->lbfgs) return ipm_refuse(h, RPM_E_UNSUPPORTED, "rpm_ipm_debug_lbfgs_step", "the solver was created with the exact Hessian");
   const IpmPlan& p = h->plan;
   IpmDev& D = h->D;
-  hipStream_t st = static_cast<hipStream_t>(dev_stream(h->eng->e));
+  hipStream_t st = ipm_stream(h);
   const size_t B = size_t(D.B), row = size_t(p.n) * sizeof(double), pitch = size_t(p.nv) * sizeof(double);
-  h->debug_started = false;
-  h->state_held = false;
-  h->debug_ls = 0;
+  h->hold.overwritten();
   IPM_TRY(h, hipMemcpyAsync(D.xt, x, B * row, hipMemcpyHostToDevice, st));
   if (reset) {
     ipm_launch_init(D, D.xt, st);
@@ -178,17 +176,14 @@ int rpm_ipm_debug_lbfgs_step(rpm_ipm* h, int reset, const double* x, const doubl
   IPM_TRY(h, hipMemcpy2DAsync(D.v, pitch, x, row, row, B, hipMemcpyHostToDevice, st));
   IPM_TRY(h, hipMemcpy2DAsync(D.glag, pitch, glag_new, row, row, B, hipMemcpyHostToDevice, st));
   IPM_TRY(h, hipMemcpy2DAsync(D.lb_gold, pitch, glag_old, row, row, B, hipMemcpyHostToDevice, st));
-  std::vector<IpmInst> inst(B);
-  IPM_TRY(h, hipMemcpyAsync(inst.data(), D.inst, B * sizeof(IpmInst), hipMemcpyDeviceToHost, st));
-  IPM_TRY(h, hipStreamSynchronize(st));
-  for (size_t bi = 0; bi < B; ++bi) {
-    inst[bi].mode = mode ? mode[bi] : 0;
-    inst[bi].status = status ? status[bi] : 0;
-  }
-  IPM_TRY(h, hipMemcpyAsync(D.inst, inst.data(), B * sizeof(IpmInst), hipMemcpyHostToDevice, st));
-  lb_launch_update(D, st);
-  int rc = launch_check(h, "limited-memory update");
+  std::vector<IpmInst> inst;
+  int rc = ipm_edit_records(h, inst, [&](size_t bi, IpmInst& s) {
+    s.mode = mode ? mode[bi] : 0;
+    s.status = status ? status[bi] : 0;
+  });
   if (rc) return rc;
+  lb_launch_update(D, st);
+  if ((rc = launch_check(h, "limited-memory update"))) return rc;
   IPM_TRY(h, hipStreamSynchronize(st));
   return RPM_OK;
 }
@@ -197,11 +192,10 @@ int rpm_ipm_debug_lbfgs_step(rpm_ipm* h, int reset, const double* x, const doubl
  * valid, updates, skips, the two decision words), M (B x 12 x 12) and the pair columns S, Y (B x 6 x n, oldest first); NULL = skip */
 int rpm_ipm_debug_lbfgs_state(rpm_ipm* h, double* record, double* M, double* S, double* Y) {
   if (!h) return RPM_E_INVALID;
-  if (!h->lbfgs) { h->err = "rpm_ipm_debug_lbfgs_state: the solver was created with the exact Hessian"; return RPM_E_UNSUPPORTED; }
+  if (!h->lbfgs) return ipm_refuse(h, RPM_E_UNSUPPORTED, "rpm_ipm_debug_lbfgs_state", "the solver was created with the exact Hessian");
   IpmDev& D = h->D;
-  hipStream_t st = static_cast<hipStream_t>(dev_stream(h->eng->e));
   const size_t B = size_t(D.B), th2 = size_t(2 * IPM_LB_H) * size_t(2 * IPM_LB_H), cols = B * IPM_LB_H * size_t(D.n);
-  IPM_TRY(h, hipStreamSynchronize(st));
+  IPM_TRY(h, hipStreamSynchronize(ipm_stream(h)));
   std::vector<double> small(B * IPM_LB_SMALL);
   IPM_TRY(h, hipMemcpy(small.data(), D.lb_small, small.size() * sizeof(double), hipMemcpyDeviceToHost));
   for (size_t bi = 0; bi < B; ++bi) {
@@ -219,7 +213,7 @@ int rpm_ipm_debug_lbfgs_state(rpm_ipm* h, double* record, double* M, double* S, 
  * Every instance is made live first.  An entry the layout has no slot for: RPM_E_INVALID. */
 int rpm_ipm_debug_lbfgs_solve(rpm_ipm* h, int nnz, const int* rows, const int* cols, const double* vals, const double* rhs, double* sol) {
   if (!h || nnz < 0 || (nnz && (!rows || !cols || !vals)) || !rhs || !sol) return RPM_E_INVALID;
-  if (!h->lbfgs) { h->err = "rpm_ipm_debug_lbfgs_solve: the solver was created with the exact Hessian"; return RPM_E_UNSUPPORTED; }
+  if (!h->lbfgs) return ipm_refuse(h, RPM_E_UNSUPPORTED, "rpm_ipm_debug_lbfgs_solve", "the solver was created with the exact Hessian");
   const IpmPlan& p = h->plan;
   const size_t B = size_t(h->D.B);
   std::vector<double> store(B * size_t(p.storage()), 0.0);
@@ -229,12 +223,8 @@ int rpm_ipm_debug_lbfgs_solve(rpm_ipm* h, int nnz, const int* rows, const int* c
     if (o < 0) return no_slot(h, "rpm_ipm_debug_lbfgs_solve", a, c);
     for (size_t bi = 0; bi < B; ++bi) store[bi * size_t(p.storage()) + size_t(o)] = vals[bi * size_t(nnz) + size_t(k)];
   }
-  std::vector<double> r = to_kkt_order(p, B, rhs);
   std::vector<IpmInst> inst;
-  int rc = debug_factor_solve(h, store.data(), r.data(), size_t(p.Nt_alloc), true, inst);
-  if (rc) return rc;
-  from_kkt_order(p, B, r, sol);
-  return RPM_OK;
+  return debug_factor_solve_unknown_order(h, store, rhs, sol, true, inst);
 }
 
 /* test hook: exactly the launches that precede the iteration loop (warm = 0: the cold start, lambda / z_L / z_U ignored), then the
@@ -258,23 +248,20 @@ int rpm_ipm_debug_start(rpm_ipm* h, int warm, const double* x, const double* lam
     IPM_TRY(h, hipMemcpyAsync(d_zU, z_U, Bn * sizeof(double), hipMemcpyHostToDevice, st));
   }
   IPM_TRY(h, hipStreamSynchronize(st));
-  h->solved = false;   // D.v, D.zL, D.zU and D.lam are about to hold a start state, not a solve's result
-  h->state_held = false;
+  h->hold.start_begins();   // D.v, D.zL, D.zU and D.lam are about to hold a start state, not a solve's result
   if ((rc = ipm_start(h, warm != 0, d_x, d_l, warm && z_L ? d_zL : nullptr, warm && z_L ? d_zU : nullptr, st))) return rc;
   IPM_TRY(h, hipStreamSynchronize(st));
   if (v_out) IPM_TRY(h, hipMemcpy(v_out, D.v, Bv * sizeof(double), hipMemcpyDeviceToHost));
   if (zL_out) IPM_TRY(h, hipMemcpy(zL_out, D.zL, Bv * sizeof(double), hipMemcpyDeviceToHost));
   if (zU_out) IPM_TRY(h, hipMemcpy(zU_out, D.zU, Bv * sizeof(double), hipMemcpyDeviceToHost));
   if (lam_out) IPM_TRY(h, hipMemcpy(lam_out, D.lam, Bm * sizeof(double), hipMemcpyDeviceToHost));
-  std::vector<IpmInst> inst(B);
-  IPM_TRY(h, hipMemcpy(inst.data(), D.inst, B * sizeof(IpmInst), hipMemcpyDeviceToHost));
+  std::vector<IpmInst> inst;
+  if ((rc = ipm_download_records(h, inst))) return rc;
   for (size_t bi = 0; bi < B; ++bi) {
     if (mu_out) mu_out[bi] = inst[bi].mu;
     if (status_out) status_out[bi] = inst[bi].status;
   }
-  h->debug_started = true;
-  h->state_held = true;
-  h->debug_ls = 0;
+  h->hold.start_ends();
   return RPM_OK;
 }
 
@@ -286,68 +273,50 @@ int rpm_ipm_debug_start(rpm_ipm* h, int warm, const double* x, const double* lam
 int rpm_ipm_debug_pass(rpm_ipm* h, int stage, double* obj, double* grad, double* g, double* jac, double* c, double* glag, double* hess,
                        double* k_storage, double* rhs, double* dv, double* dlam, double* dzL, double* dzU, double* record) {
   if (!h) return RPM_E_INVALID;
-  if (stage < 1 || stage > 3) { h->err = "rpm_ipm_debug_pass: stage 1, 2 or 3"; return RPM_E_INVALID; }
-  if (!h->debug_started) { h->err = "rpm_ipm_debug_pass: valid only directly after rpm_ipm_debug_start on this solver"; return RPM_E_INVALID; }
-  h->debug_started = false;
-  h->debug_ls = 0;
-  Engine& e = h->eng->e;
-  IpmDev& D = h->D;
+  const char* who = "rpm_ipm_debug_pass";
+  if (stage < 1 || stage > 3) return ipm_refuse(h, RPM_E_INVALID, who, "stage 1, 2 or 3");
+  if (!h->hold.pass_allowed()) return ipm_refuse(h, RPM_E_INVALID, who, "valid only directly after rpm_ipm_debug_start on this solver");
+  h->hold.pass_begins();
+  h->stats = IpmStats{};
+  const IpmLoop L = ipm_loop(h);
+  const Engine& e = L.e;
+  IpmDev& D = L.D;
   const IpmPlan& p = h->plan;
-  hipStream_t st = static_cast<hipStream_t>(dev_stream(e));
-  h->lb_iterations = 0;
-  h->total_factorizations = h->total_iterations = h->total_trials = h->total_soc = 0;
-  h->factor_ms = h->solve_ms = 0.0;
-  h->solve_pending = false;
-  const IpmLoop L{h, e, D, st, D.scal_on != 0};
   int rc = L.evaluate_and_residual();
   if (!rc && stage >= 2 && h->h_cnt[0] > 0) {
     if (!h->lbfgs) rc = L.exact_hessian();
     if (!rc && stage == 2) {
-      const int df_keep = D.df_on;
-      D.df_on = 0;
-      ipm_launch_assemble(D, std::max(e.nnz_jac, e.nnz_h), st);
-      D.df_on = df_keep;
+      const IpmFusedFillOff by_the_fill_kernel(D);
+      ipm_launch_assemble(D, std::max(e.nnz_jac, e.nnz_h), L.st);
       rc = launch_check(h, "ipm_launch_assemble");
     }
     if (!rc && stage == 3) rc = L.factor_with_inertia_correction();
     if (!rc && stage == 3) rc = L.substitute();
     if (!rc && stage == 3) rc = L.direction();
   }
-  h->solve_pending = false;
+  h->stats.solve_pending = false;
   if (rc) return rc;
-  IPM_TRY(h, hipStreamSynchronize(st));
-  h->debug_ls = stage == 3 && h->h_cnt[0] > 0 ? 1 : 0;   // a direction stands: rpm_ipm_debug_line_search may follow
-  const size_t B = size_t(D.B), d8 = sizeof(double);
-  auto rows = [&](double* dst, const double* src, size_t width, size_t pitch) -> hipError_t {   // B rows of `width` doubles, `pitch` apart
-    if (!dst || !width) return hipSuccess;
-    return hipMemcpy2D(dst, width * d8, src, pitch * d8, width * d8, B, hipMemcpyDeviceToHost);
-  };
-  IPM_TRY(h, rows(obj, D.obj, 1, 1));
-  IPM_TRY(h, rows(grad, D.grad, size_t(p.n), size_t(p.n)));
-  IPM_TRY(h, rows(g, D.g, size_t(p.m), size_t(D.sg)));
-  IPM_TRY(h, rows(jac, D.jac, size_t(e.nnz_jac), size_t(D.sv)));
-  IPM_TRY(h, rows(c, D.c, size_t(p.m), size_t(p.m)));
-  IPM_TRY(h, rows(glag, D.glag, size_t(p.nv), size_t(p.nv)));
+  IPM_TRY(h, hipStreamSynchronize(L.st));
+  h->hold.pass_ends(stage == 3 && h->h_cnt[0] > 0);   // a direction stands: rpm_ipm_debug_line_search may follow
+  const size_t n = size_t(p.n), m = size_t(p.m), nv = size_t(p.nv);
+  IPM_TRY(h, ipm_rows(D, obj, D.obj, 1, 1));
+  IPM_TRY(h, ipm_rows(D, grad, D.grad, n, n));
+  IPM_TRY(h, ipm_rows(D, g, D.g, m, size_t(D.sg)));
+  IPM_TRY(h, ipm_rows(D, jac, D.jac, size_t(e.nnz_jac), size_t(D.sv)));
+  IPM_TRY(h, ipm_rows(D, c, D.c, m, m));
+  IPM_TRY(h, ipm_rows(D, glag, D.glag, nv, nv));
   // what the stage did not write is left alone in the caller's arrays, not filled from stale device memory
-  if (stage >= 2 && !h->lbfgs) IPM_TRY(h, rows(hess, D.hess, size_t(e.nnz_h), size_t(e.nnz_h)));   // (limited-memory: there is none)
-  if (stage >= 2) IPM_TRY(h, rows(k_storage, D.K, size_t(p.storage()), size_t(p.storage())));
+  if (stage >= 2 && !h->lbfgs) IPM_TRY(h, ipm_rows(D, hess, D.hess, size_t(e.nnz_h), size_t(e.nnz_h)));   // (limited-memory: there is none)
+  if (stage >= 2) IPM_TRY(h, ipm_rows(D, k_storage, D.K, size_t(p.storage()), size_t(p.storage())));
   if (stage >= 3) {
-    IPM_TRY(h, rows(dv, D.dv, size_t(p.nv), size_t(p.nv)));
-    IPM_TRY(h, rows(dlam, D.dlam, size_t(p.m), size_t(p.m)));
-    IPM_TRY(h, rows(dzL, D.dzL, size_t(p.nv), size_t(p.nv)));
-    IPM_TRY(h, rows(dzU, D.dzU, size_t(p.nv), size_t(p.nv)));
+    IPM_TRY(h, ipm_rows(D, dv, D.dv, nv, nv));
+    IPM_TRY(h, ipm_rows(D, dlam, D.dlam, m, m));
+    IPM_TRY(h, ipm_rows(D, dzL, D.dzL, nv, nv));
+    IPM_TRY(h, ipm_rows(D, dzU, D.dzU, nv, nv));
   }
-  if (rhs && stage >= 2) {
-    std::vector<double> r(B * size_t(p.Nt_alloc));
-    IPM_TRY(h, hipMemcpy(r.data(), D.rhs, r.size() * d8, hipMemcpyDeviceToHost));
-    from_kkt_order(p, B, r, rhs);
-  }
-  if (record) {
-    std::vector<IpmInst> inst(B);
-    IPM_TRY(h, hipMemcpy(inst.data(), D.inst, B * sizeof(IpmInst), hipMemcpyDeviceToHost));
-    for (size_t bi = 0; bi < B; ++bi) flat_record(inst[bi], record + bi * RPM_IPM_RECORD_DOUBLES);
-  }
-  return RPM_OK;
+  if (rhs && stage >= 2 && (rc = ipm_download_unknown_order(h, D.rhs, 1, rhs))) return rc;
+  std::vector<IpmInst> inst;
+  return record ? download_flat_records(h, inst, record) : RPM_OK;
 }
 
 /* test hook: rounds of the line search (IpmLoop::line_search_round, what IpmLoop::line_search repeats) on the direction that
@@ -358,67 +327,49 @@ int rpm_ipm_debug_line_search(rpm_ipm* h, int rounds, int n_filter, const double
                               double* rhs, double* record, int* counts) {
   if (!h) return RPM_E_INVALID;
   const char* who = "rpm_ipm_debug_line_search";
-  if (rounds < 1) { h->err = std::string(who) + ": rounds >= 1"; return RPM_E_INVALID; }
-  if (n_filter < 0 || n_filter > IPM_FMAX) { h->err = std::string(who) + ": at most " + std::to_string(IPM_FMAX) + " filter entries"; return RPM_E_INVALID; }
-  if (n_filter > 0 && (!filter || !filter_count)) { h->err = std::string(who) + ": filter entries need filter and filter_count"; return RPM_E_INVALID; }
-  if (h->debug_ls == 0) {
-    h->err = std::string(who) + ": valid only directly after rpm_ipm_debug_pass(stage 3) that left an instance running, or after itself";
-    return RPM_E_INVALID;
-  }
-  Engine& e = h->eng->e;
-  IpmDev& D = h->D;
+  if (rounds < 1) return ipm_refuse(h, RPM_E_INVALID, who, "rounds >= 1");
+  if (n_filter < 0 || n_filter > IPM_FMAX) return ipm_refuse(h, RPM_E_INVALID, who, "at most " + std::to_string(IPM_FMAX) + " filter entries");
+  if (n_filter > 0 && (!filter || !filter_count)) return ipm_refuse(h, RPM_E_INVALID, who, "filter entries need filter and filter_count");
+  if (!h->hold.line_search_allowed())
+    return ipm_refuse(h, RPM_E_INVALID, who, "valid only directly after rpm_ipm_debug_pass(stage 3) that left an instance running, or after itself");
+  const IpmLoop L = ipm_loop(h);
+  IpmDev& D = L.D;
   const IpmPlan& p = h->plan;
-  hipStream_t st = static_cast<hipStream_t>(dev_stream(e));
   const size_t B = size_t(D.B), d8 = sizeof(double);
-  std::vector<IpmInst> inst(B);
+  int rc;
   if (filter_count) {
     for (size_t bi = 0; bi < B; ++bi)
-      if (filter_count[bi] < 0 || filter_count[bi] > n_filter) { h->err = std::string(who) + ": filter_count outside 0 .. n_filter"; return RPM_E_INVALID; }
-    IPM_TRY(h, hipStreamSynchronize(st));
-    IPM_TRY(h, hipMemcpy(inst.data(), D.inst, B * sizeof(IpmInst), hipMemcpyDeviceToHost));
-    for (size_t bi = 0; bi < B; ++bi) inst[bi].nfilt = filter_count[bi];
-    IPM_TRY(h, hipMemcpy(D.inst, inst.data(), B * sizeof(IpmInst), hipMemcpyHostToDevice));
+      if (filter_count[bi] < 0 || filter_count[bi] > n_filter) return ipm_refuse(h, RPM_E_INVALID, who, "filter_count outside 0 .. n_filter");
+    std::vector<IpmInst> inst;
+    if ((rc = ipm_edit_records(h, inst, [&](size_t bi, IpmInst& s) { s.nfilt = filter_count[bi]; }))) return rc;
     if (n_filter > 0)
       IPM_TRY(h, hipMemcpy2D(D.filt, 2 * IPM_FMAX * d8, filter, 2 * size_t(n_filter) * d8, 2 * size_t(n_filter) * d8, B, hipMemcpyHostToDevice));
+    IPM_TRY(h, hipStreamSynchronize(L.st));   // (the records are up before `inst` goes)
   }
-  const bool first = h->debug_ls == 1;
-  h->debug_ls = 0;
-  h->state_held = false;   // trial points and, next, the update: no longer the state of a start or a pass
-  const IpmLoop L{h, e, D, st, D.scal_on != 0};
+  const bool first = h->hold.line_search_begins();   // trial points and, next, the update: no longer the state of a start or a pass
   std::vector<double> rk(soc_rhs ? B * size_t(p.Nt_alloc) : 0);
   bool corrected = false;
   for (int r = 0; r < rounds; ++r) {
     if (!(first && r == 0) && L.line_search_over()) break;      // (before the first round ever the counts are not on the host yet)
     corrected = h->h_cnt[3] > 0;
-    if (int rc = L.line_search_round(soc_rhs ? rk.data() : nullptr)) return rc;
+    if ((rc = L.line_search_round(soc_rhs ? rk.data() : nullptr))) return rc;
   }
-  if (soc_rhs && corrected) from_kkt_order(p, B, rk, soc_rhs);
-  h->debug_ls = 2;
-  auto rows = [&](double* dst, const double* src, size_t width, size_t pitch) -> hipError_t {
-    if (!dst || !width) return hipSuccess;
-    return hipMemcpy2D(dst, width * d8, src, pitch * d8, width * d8, B, hipMemcpyDeviceToHost);
-  };
+  if (soc_rhs && corrected) ipm_from_kkt_order(p, B, 1, rk.data(), soc_rhs);
+  h->hold.line_search_ends();
   const size_t n = size_t(p.n), m = size_t(p.m), nv = size_t(p.nv);
-  IPM_TRY(h, rows(xt, D.xt, n, n));
-  IPM_TRY(h, rows(objt, D.objt, 1, 1));
-  IPM_TRY(h, rows(gt, D.gt, m, size_t(D.sg)));
-  IPM_TRY(h, rows(ct, D.ct, m, m));
-  IPM_TRY(h, rows(csoc, D.csoc, m, m));
-  IPM_TRY(h, rows(dv2, D.dv2, nv, nv));
-  IPM_TRY(h, rows(dlam2, D.dlam2, m, m));
-  IPM_TRY(h, rows(dzL2, D.dzL2, nv, nv));
-  IPM_TRY(h, rows(dzU2, D.dzU2, nv, nv));
-  if (rhs) {
-    std::vector<double> r(B * size_t(p.Nt_alloc));
-    IPM_TRY(h, hipMemcpy(r.data(), D.rhs, r.size() * d8, hipMemcpyDeviceToHost));
-    from_kkt_order(p, B, r, rhs);
-  }
-  if (record) {
-    IPM_TRY(h, hipMemcpy(inst.data(), D.inst, B * sizeof(IpmInst), hipMemcpyDeviceToHost));
-    for (size_t bi = 0; bi < B; ++bi) flat_record(inst[bi], record + bi * RPM_IPM_RECORD_DOUBLES);
-  }
+  IPM_TRY(h, ipm_rows(D, xt, D.xt, n, n));
+  IPM_TRY(h, ipm_rows(D, objt, D.objt, 1, 1));
+  IPM_TRY(h, ipm_rows(D, gt, D.gt, m, size_t(D.sg)));
+  IPM_TRY(h, ipm_rows(D, ct, D.ct, m, m));
+  IPM_TRY(h, ipm_rows(D, csoc, D.csoc, m, m));
+  IPM_TRY(h, ipm_rows(D, dv2, D.dv2, nv, nv));
+  IPM_TRY(h, ipm_rows(D, dlam2, D.dlam2, m, m));
+  IPM_TRY(h, ipm_rows(D, dzL2, D.dzL2, nv, nv));
+  IPM_TRY(h, ipm_rows(D, dzU2, D.dzU2, nv, nv));
+  if (rhs && (rc = ipm_download_unknown_order(h, D.rhs, 1, rhs))) return rc;
   if (counts) { counts[0] = h->h_cnt[2]; counts[1] = h->h_cnt[3]; }
-  return RPM_OK;
+  std::vector<IpmInst> inst;
+  return record ? download_flat_records(h, inst, record) : RPM_OK;
 }
 
 /* test hook: IpmLoop::update on what rpm_ipm_debug_line_search has just left, and what it wrote.  filter: B x n_filter pairs, the
@@ -426,39 +377,30 @@ int rpm_ipm_debug_line_search(rpm_ipm* h, int rounds, int n_filter, const double
 int rpm_ipm_debug_update(rpm_ipm* h, double* v, double* zL, double* zU, double* lambda, int n_filter, double* filter, double* vR, double* dr2,
                          double* pp, double* nn, double* zp, double* zn, double* lb_gold, double* record) {
   if (!h) return RPM_E_INVALID;
-  if (n_filter < 0 || n_filter > IPM_FMAX || (n_filter > 0 && !filter)) { h->err = "rpm_ipm_debug_update: 0 .. " + std::to_string(IPM_FMAX) + " filter entries into filter"; return RPM_E_INVALID; }
-  if (h->debug_ls != 2) { h->err = "rpm_ipm_debug_update: valid only directly after rpm_ipm_debug_line_search on this solver"; return RPM_E_INVALID; }
-  h->debug_ls = 0;
-  Engine& e = h->eng->e;
-  IpmDev& D = h->D;
+  const char* who = "rpm_ipm_debug_update";
+  if (n_filter < 0 || n_filter > IPM_FMAX || (n_filter > 0 && !filter))
+    return ipm_refuse(h, RPM_E_INVALID, who, "0 .. " + std::to_string(IPM_FMAX) + " filter entries into filter");
+  if (!h->hold.update_allowed()) return ipm_refuse(h, RPM_E_INVALID, who, "valid only directly after rpm_ipm_debug_line_search on this solver");
+  h->hold.updated();
+  const IpmLoop L = ipm_loop(h);
+  IpmDev& D = L.D;
   const IpmPlan& p = h->plan;
-  hipStream_t st = static_cast<hipStream_t>(dev_stream(e));
-  const IpmLoop L{h, e, D, st, D.scal_on != 0};
   if (int rc = L.update()) return rc;
-  IPM_TRY(h, hipStreamSynchronize(st));
-  const size_t B = size_t(D.B), d8 = sizeof(double);
-  auto rows = [&](double* dst, const double* src, size_t width, size_t pitch) -> hipError_t {
-    if (!dst || !width) return hipSuccess;
-    return hipMemcpy2D(dst, width * d8, src, pitch * d8, width * d8, B, hipMemcpyDeviceToHost);
-  };
+  IPM_TRY(h, hipStreamSynchronize(L.st));
   const size_t n = size_t(p.n), m = size_t(p.m), nv = size_t(p.nv);
-  IPM_TRY(h, rows(v, D.v, nv, nv));
-  IPM_TRY(h, rows(zL, D.zL, nv, nv));
-  IPM_TRY(h, rows(zU, D.zU, nv, nv));
-  IPM_TRY(h, rows(lambda, D.lam, m, m));
-  IPM_TRY(h, rows(filter, D.filt, 2 * size_t(n_filter), 2 * size_t(IPM_FMAX)));
-  IPM_TRY(h, rows(vR, D.vR, nv, nv));
-  IPM_TRY(h, rows(dr2, D.dr2, nv, nv));
-  IPM_TRY(h, rows(pp, D.pp, m, m));
-  IPM_TRY(h, rows(nn, D.nn, m, m));
-  IPM_TRY(h, rows(zp, D.zp, m, m));
-  IPM_TRY(h, rows(zn, D.zn, m, m));
-  if (h->lbfgs) IPM_TRY(h, rows(lb_gold, D.lb_gold, n, nv));
-  h->h_inst.resize(B);                     // (rpm_ipm_get_trace reads the iteration counts from here)
-  IPM_TRY(h, hipMemcpy(h->h_inst.data(), D.inst, B * sizeof(IpmInst), hipMemcpyDeviceToHost));
-  if (record)
-    for (size_t bi = 0; bi < B; ++bi) flat_record(h->h_inst[bi], record + bi * RPM_IPM_RECORD_DOUBLES);
-  return RPM_OK;
+  IPM_TRY(h, ipm_rows(D, v, D.v, nv, nv));
+  IPM_TRY(h, ipm_rows(D, zL, D.zL, nv, nv));
+  IPM_TRY(h, ipm_rows(D, zU, D.zU, nv, nv));
+  IPM_TRY(h, ipm_rows(D, lambda, D.lam, m, m));
+  IPM_TRY(h, ipm_rows(D, filter, D.filt, 2 * size_t(n_filter), 2 * size_t(IPM_FMAX)));
+  IPM_TRY(h, ipm_rows(D, vR, D.vR, nv, nv));
+  IPM_TRY(h, ipm_rows(D, dr2, D.dr2, nv, nv));
+  IPM_TRY(h, ipm_rows(D, pp, D.pp, m, m));
+  IPM_TRY(h, ipm_rows(D, nn, D.nn, m, m));
+  IPM_TRY(h, ipm_rows(D, zp, D.zp, m, m));
+  IPM_TRY(h, ipm_rows(D, zn, D.zn, m, m));
+  if (h->lbfgs) IPM_TRY(h, ipm_rows(D, lb_gold, D.lb_gold, n, nv));
+  return download_flat_records(h, h->h_inst, record);   // (always: rpm_ipm_get_trace reads the iteration counts from h_inst)
 }
 
 }  // extern "C"

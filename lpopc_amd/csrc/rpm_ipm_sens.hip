@@ -94,11 +94,6 @@ __global__ __launch_bounds__(256) void ipm_sens_apply_kernel(int n, int m, int n
 
 namespace {
 
-int refuse(rpm_ipm* h, int code, const std::string& who, const std::string& why) {
-  h->err = who + ": " + why;
-  return code;
-}
-
 template <class T>
 int sens_room(rpm_ipm* h, T** p, size_t* cap, size_t count) {   // grown only; what growing replaces is freed (the stream is idle between calls)
   if (*p && count <= *cap) return RPM_OK;
@@ -118,11 +113,11 @@ int sens_check(rpm_ipm* h, const std::string& who, int n_par, const int* var_ind
   const Engine& e = h->eng->e;
   std::string why;
   if (int rc = ipm_sens_table(h->plan, h->lbfgs ? 0 : e.nnz_h, e.hes_i.data(), e.hes_j.data(), n_par, var_index, table, &why))
-    return refuse(h, rc, who, why);
-  if (h->lbfgs) return refuse(h, RPM_E_UNSUPPORTED, who, "hessian-approximation = limited-memory: a quasi-Newton Hessian gives no sensitivities");
-  if (h->D.scal_on) return refuse(h, RPM_E_UNSUPPORTED, who, "not with nlp_scaling = 1");
-  if (need_state && !h->state_held)
-    return refuse(h, RPM_E_INVALID, who, "valid after a finished solve, or directly after rpm_ipm_debug_start / rpm_ipm_debug_pass on this solver");
+    return ipm_refuse(h, rc, who, why);
+  if (h->lbfgs) return ipm_refuse(h, RPM_E_UNSUPPORTED, who, "hessian-approximation = limited-memory: a quasi-Newton Hessian gives no sensitivities");
+  if (h->D.scal_on) return ipm_refuse(h, RPM_E_UNSUPPORTED, who, "not with nlp_scaling = 1");
+  if (need_state && !h->hold.holds_state())
+    return ipm_refuse(h, RPM_E_INVALID, who, "valid after a finished solve, or directly after rpm_ipm_debug_start / rpm_ipm_debug_pass on this solver");
   return RPM_OK;
 }
 
@@ -154,6 +149,17 @@ int sens_upload(rpm_ipm* h, int n_par, const int* var_index, const IpmSensTable&
   return sens_room(h, &s.ws, &s.ws_cap, size_t(h->D.B) * size_t(n_par) * size_t(p.Nt_alloc));
 }
 
+// What rpm_ipm_sensitivities[_dev] and rpm_ipm_debug_sensitivity_rhs begin with, under the caller's DeviceRestore: every refusal
+// (out_ptr: the output that must not be NULL, named out_name), the engine's device bound, table and work space on the device.
+int sens_enter(rpm_ipm* h, const std::string& who, int n_par, const int* var_index, const void* out_ptr, const char* out_name) {
+  if (!out_ptr) return ipm_refuse(h, RPM_E_INVALID, who, var_index ? std::string(out_name) + " is NULL" : "var_index is NULL");
+  IpmSensTable t;
+  int rc = sens_check(h, who, n_par, var_index, true, &t);
+  if (rc) return rc;
+  if ((rc = dev_bind(h->eng->e))) return ipm_eng_fail(h, rc);
+  return sens_upload(h, n_par, var_index, t);
+}
+
 // steps 1 and 3: g, the Jacobian and the exact Hessian at the state, then the n_par right-hand sides of every instance into the
 // (zeroed) work space
 int sens_evaluate_and_gather(rpm_ipm* h, const IpmLoop& L, int n_par) {
@@ -163,7 +169,7 @@ int sens_evaluate_and_gather(rpm_ipm* h, const IpmLoop& L, int n_par) {
   int rc;
   dev_forget_persistent(e);   // this evaluation writes all of D.jac, the constant block included (as the first one of a solve does)
   ipm_launch_pack_x(D, L.st);
-  if ((rc = dev_eval_cons(e, D.xe, D.g, D.jac, 3 | 4 | 16, L.st))) return L.eng_fail(rc);
+  if ((rc = dev_eval_cons(e, D.xe, D.g, D.jac, 3 | 4 | 16, L.st))) return ipm_eng_fail(h, rc);
   if ((rc = L.exact_hessian())) return rc;
   IPM_TRY(h, hipMemsetAsync(s.ws, 0, size_t(D.B) * size_t(n_par) * size_t(D.Nt) * sizeof(double), L.st));
   const int G = s.n_groups;
@@ -184,30 +190,28 @@ SensPars pars_of(int n_par, const int* var_index) {
 // The whole of rpm_ipm_sensitivities_dev after its checks.  The solver's stream is idle on return, the instance records, the
 // counters and the statistics of the last solve are what they were.
 int sens_run(rpm_ipm* h, int n_par, const int* var_index, double* d_dx, double* d_dlambda, double* delta_w, int* info, void* stream) {
-  Engine& e = h->eng->e;
-  IpmDev& D = h->D;
-  hipStream_t st = static_cast<hipStream_t>(dev_stream(e));
+  const IpmLoop L = ipm_loop(h);   // (nlp_scaling is off: sens_check)
+  IpmDev& D = L.D;
+  hipStream_t st = L.st;
   const size_t B = size_t(D.B);
   // ordering contract of rpm_ipm_solve_dev: after what the caller queued on `stream`, drained on return
   IPM_TRY(h, hipEventRecord(h->ev[0], static_cast<hipStream_t>(stream)));
   IPM_TRY(h, hipStreamWaitEvent(st, h->ev[0], 0));
   // the records of the last solve (or of the hooks) are saved; live ones take their place around the factorisation: mode 0,
   // delta_w = 0, asking for a factorisation — and status 5 kept, so that an instance with a non-finite state is left out
-  std::vector<IpmInst> saved(B), live(B, IpmInst{});
-  IPM_TRY(h, hipMemcpyAsync(saved.data(), D.inst, B * sizeof(IpmInst), hipMemcpyDeviceToHost, st));
-  IPM_TRY(h, hipStreamSynchronize(st));
+  std::vector<IpmInst> saved, live(B, IpmInst{});
+  if (int rc = ipm_download_records(h, saved)) return rc;
   for (size_t bi = 0; bi < B; ++bi) {
     live[bi].mu = saved[bi].mu;
     live[bi].refactor = 1;
     live[bi].status = saved[bi].status == 5 ? 5 : 0;
   }
-  const int keep_fact = h->total_factorizations, keep_cnt[4] = {h->h_cnt[0], h->h_cnt[1], h->h_cnt[2], h->h_cnt[3]};
-  const double keep_ms = h->factor_ms;
-  h->debug_ls = 0;   // (a direction rpm_ipm_debug_pass(3) left does not survive: D.K and D.rhs are rewritten)
-  const IpmLoop L{h, e, D, st, false};
+  const IpmStats keep_stats = h->stats;
+  const int keep_cnt[4] = {h->h_cnt[0], h->h_cnt[1], h->h_cnt[2], h->h_cnt[3]};
+  h->hold.sensitivities_taken();   // (a direction rpm_ipm_debug_pass(3) left does not survive: D.K and D.rhs are rewritten)
   auto body = [&]() -> int {
     int rc;
-    IPM_TRY(h, hipMemcpyAsync(D.inst, live.data(), B * sizeof(IpmInst), hipMemcpyHostToDevice, st));
+    if ((rc = ipm_upload_records(h, live))) return rc;
     if ((rc = sens_evaluate_and_gather(h, L, n_par))) return rc;
     if ((rc = L.factor_with_inertia_correction())) return rc;
     IpmDev Ds = D;   // the substitution kernels on the work space: n_par right-hand sides per instance, same factors
@@ -221,15 +225,13 @@ int sens_run(rpm_ipm* h, int n_par, const int* var_index, double* d_dx, double* 
     return RPM_OK;
   };
   const int rc = body();
-  // put back, whatever happened
-  const std::string err = h->err;
+  // put back, whatever happened (plain runtime calls: a failure's text in h->err stays)
   hipError_t s1 = hipMemcpyAsync(D.inst, saved.data(), B * sizeof(IpmInst), hipMemcpyHostToDevice, st);
   hipError_t s2 = hipMemcpyAsync(D.cnt, keep_cnt, 4 * sizeof(int), hipMemcpyHostToDevice, st);
   hipError_t s3 = hipStreamSynchronize(st);
   for (int i = 0; i < 4; ++i) h->h_cnt[i] = keep_cnt[i];
-  h->total_factorizations = keep_fact;
-  h->factor_ms = keep_ms;
-  if (rc) { h->err = err; return rc; }
+  h->stats = keep_stats;
+  if (rc) return rc;
   IPM_TRY(h, s1);
   IPM_TRY(h, s2);
   IPM_TRY(h, s3);
@@ -251,16 +253,14 @@ struct ApplyArrays {
 
 int apply_check(rpm_ipm* h, const std::string& who, int n_par, const int* var_index, const ApplyArrays& a) {
   if (int rc = sens_check(h, who, n_par, var_index, false, nullptr)) return rc;
-  if (!a.dx || !a.delta || !a.x || !a.x_out) return refuse(h, RPM_E_INVALID, who, "dx, delta, x or x_out is NULL");
+  if (!a.dx || !a.delta || !a.x || !a.x_out) return ipm_refuse(h, RPM_E_INVALID, who, "dx, delta, x or x_out is NULL");
   const size_t B = size_t(h->D.B), d8 = sizeof(double), P = size_t(n_par), n = size_t(h->plan.n), m = size_t(h->plan.m);
   const bool lam = a.with_lambda();
   const ByteRange in[5] = {{"dx", a.dx, B * P * n * d8}, {"delta", a.delta, B * P * d8}, {"x", a.x, B * n * d8},
                            {"dlambda", lam ? a.dlambda : nullptr, B * P * m * d8}, {"lambda", lam ? a.lambda : nullptr, B * m * d8}};
   const ByteRange out[2] = {{"x_out", a.x_out, B * n * d8}, {"lambda_out", lam ? a.lambda_out : nullptr, B * m * d8}};
   Engine& e = h->eng->e;
-  const int rc = step_overlap(e, who + ": ", out, 2, in, 5);   // every output against every input and the other output
-  if (rc) h->err = e.err;
-  return rc;
+  return ipm_eng_fail(h, step_overlap(e, who + ": ", out, 2, in, 5));   // every output against every input and the other output
 }
 
 int apply_launch(rpm_ipm* h, int n_par, const ApplyArrays& a, hipStream_t stream) {
@@ -280,8 +280,8 @@ int rpm_ipm_initial_state_variables(rpm_ipm* h, int phase, int* var_index) {
   if (!h) return RPM_E_INVALID;
   const Engine& e = h->eng->e;
   const std::string who = "rpm_ipm_initial_state_variables";
-  if (phase < 0 || phase >= e.P) return refuse(h, RPM_E_INVALID, who, "phase " + std::to_string(phase) + " is out of range");
-  if (!var_index) return refuse(h, RPM_E_INVALID, who, "var_index is NULL");
+  if (phase < 0 || phase >= e.P) return ipm_refuse(h, RPM_E_INVALID, who, "phase " + std::to_string(phase) + " is out of range");
+  if (!var_index) return ipm_refuse(h, RPM_E_INVALID, who, "var_index is NULL");
   const PhaseHost& p = e.ph[size_t(phase)];
   for (int j = 0; j < p.nx; ++j) var_index[j] = p.var0 + j * (p.N + 1);
   return RPM_OK;
@@ -290,27 +290,16 @@ int rpm_ipm_initial_state_variables(rpm_ipm* h, int phase, int* var_index) {
 int rpm_ipm_sensitivities_dev(rpm_ipm* h, int n_par, const int* var_index, double* d_dx, double* d_dlambda, double* delta_w, int* info,
                               void* stream) {
   if (!h) return RPM_E_INVALID;
-  const std::string who = "rpm_ipm_sensitivities";
-  if (!d_dx) return refuse(h, RPM_E_INVALID, who, var_index ? "dx is NULL" : "var_index is NULL");
-  IpmSensTable t;
-  int rc = sens_check(h, who, n_par, var_index, true, &t);
-  if (rc) return rc;
   DeviceRestore restore;
-  if ((rc = dev_bind(h->eng->e))) { h->err = h->eng->e.err; return rc; }
-  if ((rc = sens_upload(h, n_par, var_index, t))) return rc;
+  if (int rc = sens_enter(h, "rpm_ipm_sensitivities", n_par, var_index, d_dx, "dx")) return rc;
   return sens_run(h, n_par, var_index, d_dx, d_dlambda, delta_w, info, stream);
 }
 
 int rpm_ipm_sensitivities(rpm_ipm* h, int n_par, const int* var_index, double* dx, double* dlambda, double* delta_w, int* info) {
   if (!h) return RPM_E_INVALID;
-  const std::string who = "rpm_ipm_sensitivities";
-  if (!dx) return refuse(h, RPM_E_INVALID, who, var_index ? "dx is NULL" : "var_index is NULL");
-  IpmSensTable t;
-  int rc = sens_check(h, who, n_par, var_index, true, &t);
-  if (rc) return rc;
   DeviceRestore restore;
-  if ((rc = dev_bind(h->eng->e))) { h->err = h->eng->e.err; return rc; }
-  if ((rc = sens_upload(h, n_par, var_index, t))) return rc;
+  int rc = sens_enter(h, "rpm_ipm_sensitivities", n_par, var_index, dx, "dx");
+  if (rc) return rc;
   const size_t B = size_t(h->D.B), Pn = size_t(n_par) * h->plan.n, Pm = size_t(n_par) * h->plan.m;
   if ((rc = sens_room(h, &h->sens.block, &h->sens.block_cap, B * (Pn + Pm)))) return rc;
   double *d_dx = h->sens.block, *d_dl = dlambda ? d_dx + B * Pn : nullptr;
@@ -322,28 +311,11 @@ int rpm_ipm_sensitivities(rpm_ipm* h, int n_par, const int* var_index, double* d
 
 int rpm_ipm_debug_sensitivity_rhs(rpm_ipm* h, int n_par, const int* var_index, double* rhs) {
   if (!h) return RPM_E_INVALID;
-  const std::string who = "rpm_ipm_debug_sensitivity_rhs";
-  if (!rhs) return refuse(h, RPM_E_INVALID, who, var_index ? "rhs is NULL" : "var_index is NULL");
-  IpmSensTable t;
-  int rc = sens_check(h, who, n_par, var_index, true, &t);
-  if (rc) return rc;
   DeviceRestore restore;
-  Engine& e = h->eng->e;
-  if ((rc = dev_bind(e))) { h->err = e.err; return rc; }
-  if ((rc = sens_upload(h, n_par, var_index, t))) return rc;
-  IpmDev& D = h->D;
-  const IpmPlan& p = h->plan;
-  hipStream_t st = static_cast<hipStream_t>(dev_stream(e));
-  const IpmLoop L{h, e, D, st, false};
-  if ((rc = sens_evaluate_and_gather(h, L, n_par))) return rc;
-  const size_t B = size_t(D.B), P = size_t(n_par), Nt = size_t(p.Nt), Na = size_t(p.Nt_alloc);
-  std::vector<double> w(B * P * Na);
-  IPM_TRY(h, hipMemcpyAsync(w.data(), h->sens.ws, w.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-  IPM_TRY(h, hipStreamSynchronize(st));
-  for (size_t bi = 0; bi < B; ++bi)
-    for (size_t k = 0; k < P; ++k)
-      for (size_t a = 0; a < Nt; ++a) rhs[(bi * P + k) * Nt + a] = w[(k * B + bi) * Na + size_t(p.pos[a])];
-  return RPM_OK;
+  int rc = sens_enter(h, "rpm_ipm_debug_sensitivity_rhs", n_par, var_index, rhs, "rhs");
+  if (rc) return rc;
+  if ((rc = sens_evaluate_and_gather(h, ipm_loop(h), n_par))) return rc;
+  return ipm_download_unknown_order(h, h->sens.ws, size_t(n_par), rhs);
 }
 
 int rpm_ipm_apply_sensitivities_dev(rpm_ipm* h, int n_par, const int* var_index, const double* d_dx, const double* d_dlambda,
@@ -363,7 +335,7 @@ int rpm_ipm_apply_sensitivities(rpm_ipm* h, int n_par, const int* var_index, con
   if (rc) return rc;
   DeviceRestore restore;
   Engine& e = h->eng->e;
-  if ((rc = dev_bind(e))) { h->err = e.err; return rc; }
+  if ((rc = dev_bind(e))) return ipm_eng_fail(h, rc);
   hipStream_t st = static_cast<hipStream_t>(dev_stream(e));
   const bool lam = a.with_lambda();
   const size_t B = size_t(h->D.B), P = size_t(n_par), n = size_t(h->plan.n), m = size_t(h->plan.m), d8 = sizeof(double);

@@ -31,8 +31,6 @@ bool env_is_zero(const char* name) {   // the "set and equal to 0" switches of r
   return v && std::atoi(v) == 0;
 }
 
-int device_failed(rpm_ipm* h, const char* what) { h->err = what; return RPM_E_DEVICE; }
-
 // the plan's scatter maps and the fill list, resident
 int upload_plan_tables(rpm_ipm* h, const IpmFillList& fill, bool one_pass) {
   const Engine& e = h->eng->e;
@@ -121,15 +119,24 @@ int alloc_state(rpm_ipm* h) {
   a.room(&D.part, B * IPM_VEC_BLOCKS * IPM_VEC_PART); a.room(&D.tick, B);
   if (a.rc) return a.rc;
   // on the engine's (non-blocking) stream, where the kernels that take tickets run: a null-stream fill is not ordered against it
-  if (hipMemsetAsync(D.tick, 0, B * sizeof(int), static_cast<hipStream_t>(dev_stream(e))) != hipSuccess) return device_failed(h, "hipMemset");
-  if (hipHostMalloc(reinterpret_cast<void**>(&h->h_cnt), 4 * sizeof(int)) != hipSuccess) return device_failed(h, "hipHostMalloc");
+  if (hipMemsetAsync(D.tick, 0, B * sizeof(int), static_cast<hipStream_t>(dev_stream(e))) != hipSuccess) return ipm_refuse(h, RPM_E_DEVICE, "", "hipMemset");
+  if (hipHostMalloc(reinterpret_cast<void**>(&h->h_cnt), 4 * sizeof(int)) != hipSuccess) return ipm_refuse(h, RPM_E_DEVICE, "", "hipHostMalloc");
   std::vector<double> l(B * p.nv, 0.0), u(B * p.nv, 0.0);
   for (size_t bi = 0; bi < B; ++bi)
     for (int i = 0; i < p.n; ++i) { l[bi * p.nv + i] = e.xl[i]; u[bi * p.nv + i] = e.xu[i]; }
   if (hipMemcpy(D.vl0, l.data(), l.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(D.vu0, u.data(), u.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) return device_failed(h, "hipMemcpy");
+      hipMemcpy(D.vu0, u.data(), u.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) return ipm_refuse(h, RPM_E_DEVICE, "", "hipMemcpy");
   h->h_inst.resize(B);
   return RPM_OK;
+}
+
+// why kkt_factor_kernel cannot hold the plan's sub-problems — rows per block column, LDS —; empty: it can
+std::string factor_kernel_refusal(const IpmPlan& p) {
+  if (p.max_rows > 4 * IPM_MT * 16)
+    return "band + border of " + std::to_string(p.max_rows - IPM_W) + " rows exceeds the factorisation's 512 rows per block column";
+  if (kkt_factor_lds_bytes(p) > 150 * 1024)
+    return "band of " + std::to_string(p.b) + " and border of " + std::to_string(p.nb) + " rows do not fit the factorisation's LDS";
+  return "";
 }
 
 // which factorisation kernel runs each level, with how much LDS and how many tiles per wave; refuses what no kernel holds
@@ -153,7 +160,7 @@ int choose_kernels(rpm_ipm* h, const IpmSubList& s) {
     // 1024 quadrotor instances 0.12 against 0.30 ms)
     if (B > 256) h->last_dense_lds = 0;
     const size_t most = std::max(h->l1_dense_lds, std::max(h->l2_dense_lds, h->last_dense_lds));
-    if (most && kkt_factor_dense_prepare(most) != hipSuccess) return device_failed(h, "hipFuncSetAttribute");
+    if (most && kkt_factor_dense_prepare(most) != hipSuccess) return ipm_refuse(h, RPM_E_DEVICE, "", "hipFuncSetAttribute");
     if (!env_is_zero("RPM_IPM_DENSE")) D.l1_dense_lds = h->l1_dense_lds;   // option "level1_dense"
     if (!env_is_zero("RPM_IPM_UPPER_DENSE")) {                             // option "upper_dense"
       D.l2_dense_lds = h->l2_dense_lds;
@@ -164,16 +171,9 @@ int choose_kernels(rpm_ipm* h, const IpmSubList& s) {
   // a few large instances: fewer sub-problems than two per CU -> 8 waves per workgroup, 3 tiles each (code 38: <3, 8>)
   if (p.nd && p.max_rows > 256 && p.max_rows <= 384 && B * p.subs.size() <= 512) h->factor_mt = 38;
   if (const char* fm = std::getenv("RPM_IPM_FACTOR_VARIANT")) h->factor_mt = std::atoi(fm);   // experiments: 4, 6, 8, 28 (<2,8>), 38 (<3,8>)
-  if (p.max_rows > 4 * IPM_MT * 16) {
-    h->err = "band + border of " + std::to_string(p.max_rows - IPM_W) + " rows exceeds the factorisation's 512 rows per block column";
-    return RPM_E_UNSUPPORTED;
-  }
+  if (const std::string why = factor_kernel_refusal(p); !why.empty()) return ipm_refuse(h, RPM_E_UNSUPPORTED, "", why);
   h->factor_lds = kkt_factor_lds_bytes(p);
-  if (h->factor_lds > 150 * 1024) {
-    h->err = "band of " + std::to_string(p.b) + " and border of " + std::to_string(p.nb) + " rows do not fit the factorisation's LDS";
-    return RPM_E_UNSUPPORTED;
-  }
-  if (kkt_factor_prepare(h->factor_mt, h->factor_lds) != hipSuccess) return device_failed(h, "hipFuncSetAttribute");
+  if (kkt_factor_prepare(h->factor_mt, h->factor_lds) != hipSuccess) return ipm_refuse(h, RPM_E_DEVICE, "", "hipFuncSetAttribute");
   return RPM_OK;
 }
 }  // namespace
@@ -210,7 +210,7 @@ int rpm_ipm_create(rpm_engine* eng, rpm_ipm** out) {
   rc = build_ipm_plan(e, h->plan, &why, e.opt_ipm_nested != 0);
   // automatic: no interval structure to dissect, or sub-problems the factorisation kernel cannot hold (rows per block column, LDS:
   // e.g. a border grown by promoted unknowns on top of the intervals' separators) -> one band
-  if (e.opt_ipm_nested == -1 && (rc || h->plan.max_rows > 4 * IPM_MT * 16 || kkt_factor_lds_bytes(h->plan) > 150 * 1024))
+  if (e.opt_ipm_nested == -1 && (rc || !factor_kernel_refusal(h->plan).empty()))
     rc = build_ipm_plan(e, h->plan, &why, 0);
   if (rc) return fail(rc, why);
   const IpmPlan& p = h->plan;
@@ -263,21 +263,21 @@ int rpm_ipm_set_option(rpm_ipm* h, const char* key, double value) {
   else if (k == "acceptable_tol") o.acceptable_tol = value;
   else if (k == "acceptable_iter") o.acceptable_iter = int(value);
   else if (k == "restoration_max_iter") o.resto_max = int(value);
-  else if (k == "bound_relax_factor") { if (!(value >= 0.0)) { h->err = "bound_relax_factor must be >= 0"; return RPM_E_INVALID; } o.bound_relax = value; }
+  else if (k == "bound_relax_factor") { if (!(value >= 0.0)) return ipm_refuse(h, RPM_E_INVALID, "", "bound_relax_factor must be >= 0"); o.bound_relax = value; }
   else if (k == "max_soc") o.max_soc = std::max(0, int(value));
   else if (k == "sigma_cap") o.sigma_cap = value;      // experiment
   else if (k == "init_ls_multipliers") o.init_ls_mult = value != 0.0;
   else if (k == "nlp_scaling") { o.nlp_scaling = value != 0.0; h->D.scal_on = o.nlp_scaling; }
-  else if (k == "nlp_scaling_max_gradient") { if (!(value > 0.0)) { h->err = "nlp_scaling_max_gradient must be > 0"; return RPM_E_INVALID; } o.scal_gmax = value; }
+  else if (k == "nlp_scaling_max_gradient") { if (!(value > 0.0)) return ipm_refuse(h, RPM_E_INVALID, "", "nlp_scaling_max_gradient must be > 0"); o.scal_gmax = value; }
   else if (k == "ic_hot_start") o.ic_hot = value != 0.0;
   else if (k == "ic_hot_min") o.ic_hot_min = value;
   else if (k == "mu_strategy") {       // 0 monotone (default), 1 adaptive: LOQO oracle + kkt-error globalisation
-    if (value != 0.0 && value != 1.0) { h->err = "mu_strategy: 0 (monotone) or 1 (adaptive)"; return RPM_E_INVALID; }
+    if (value != 0.0 && value != 1.0) return ipm_refuse(h, RPM_E_INVALID, "", "mu_strategy: 0 (monotone) or 1 (adaptive)");
     o.mu_adaptive = int(value);
   }
   else if (k == "restoration_penalty") o.resto_rho = value;
   else if (k == "level1_dense") {   // level 1 of the nested dissection on kkt_factor_dense_kernel (default where the interval blocks fit it)
-    if (value != 0.0 && !h->l1_dense_lds) { h->err = "level1_dense: no nested dissection, or an interval block of more than 21 block rows"; return RPM_E_UNSUPPORTED; }
+    if (value != 0.0 && !h->l1_dense_lds) return ipm_refuse(h, RPM_E_UNSUPPORTED, "", "level1_dense: no nested dissection, or an interval block of more than 21 block rows");
     h->D.l1_dense_lds = value != 0.0 ? h->l1_dense_lds : 0;
   }
   else if (k == "upper_dense") {    // the levels above the interval blocks on kkt_factor_dense_kernel too (default where their sub-problems fit it)
@@ -286,12 +286,12 @@ int rpm_ipm_set_option(rpm_ipm* h, const char* key, double value) {
     h->D.last_dense_corner = value == 2.0 ? 0 : 1;   // 2: the last level's corner by kkt_factor_kernel's unblocked elimination
   }
   else if (k == "fused_fill") {     // level-1 blocks assembled inside kkt_factor_dense_kernel (default where that kernel runs and the tables exist)
-    if (value != 0.0 && !h->D.df_map) { h->err = "fused_fill: level 1 does not run on kkt_factor_dense_kernel"; return RPM_E_UNSUPPORTED; }
+    if (value != 0.0 && !h->D.df_map) return ipm_refuse(h, RPM_E_UNSUPPORTED, "", "fused_fill: level 1 does not run on kkt_factor_dense_kernel");
     h->D.df_on = value != 0.0;
   }
   else if (k == "trace") {          // keep the first `value` iterations of every instance (rpm_ipm_get_trace)
     const int cap = int(value);
-    if (cap < 0 || cap > 100000) { h->err = "trace: 0 ... 100000 records"; return RPM_E_INVALID; }
+    if (cap < 0 || cap > 100000) return ipm_refuse(h, RPM_E_INVALID, "", "trace: 0 ... 100000 records");
     h->D.trace = nullptr;
     h->D.trace_cap = 0;
     if (cap > 0) {
@@ -300,7 +300,7 @@ int rpm_ipm_set_option(rpm_ipm* h, const char* key, double value) {
       h->D.trace_cap = cap;
     }
   }
-  else { h->err = "unknown option " + k; return RPM_E_INVALID; }
+  else return ipm_refuse(h, RPM_E_INVALID, "", "unknown option " + k);
   return RPM_OK;
 }
 
@@ -335,16 +335,16 @@ int rpm_ipm_get_subproblems(rpm_ipm* h, int capacity, int* geom, int* n_sub) {
 
 int rpm_ipm_get_stats(rpm_ipm* h, int* iterations, int* factorizations, int* trial_points) {
   if (!h) return RPM_E_INVALID;
-  if (iterations) *iterations = h->total_iterations;
-  if (factorizations) *factorizations = h->total_factorizations;
-  if (trial_points) *trial_points = h->total_trials;
+  if (iterations) *iterations = h->stats.total_iterations;
+  if (factorizations) *factorizations = h->stats.total_factorizations;
+  if (trial_points) *trial_points = h->stats.total_trials;
   return RPM_OK;
 }
 
 int rpm_ipm_get_kernel_times(rpm_ipm* h, double* factor_ms, double* substitution_ms) {
   if (!h) return RPM_E_INVALID;
-  if (factor_ms) *factor_ms = h->factor_ms;
-  if (substitution_ms) *substitution_ms = h->solve_ms;
+  if (factor_ms) *factor_ms = h->stats.factor_ms;
+  if (substitution_ms) *substitution_ms = h->stats.solve_ms;
   return RPM_OK;
 }
 
@@ -366,6 +366,7 @@ int rpm_ipm_get_trace(rpm_ipm* h, int instance, int capacity, double* records, i
 
 // the KKT layout is shared by all instances: the first variable of x_l / x_u (one instance, n) that is fixed where the plan has it
 // free or the other way round, -1 if none
+static const char* const FIXED_FREE_CHANGE = " changes between fixed and free (the KKT layout is shared by all instances)";
 static int fixed_free_change(const IpmPlan& p, const double* x_l, const double* x_u) {
   for (int i = 0; i < p.n; ++i)
     if ((x_l[i] == x_u[i]) != (p.fixed[i] != 0)) return i;
@@ -375,17 +376,14 @@ static int fixed_free_change(const IpmPlan& p, const double* x_l, const double* 
 int rpm_ipm_set_bounds(rpm_ipm* h, int instance, const double* x_l, const double* x_u) {
   if (!h || !x_l || !x_u || instance < 0 || instance >= h->D.B) return RPM_E_INVALID;
   const IpmPlan& p = h->plan;
-  if (const int i = fixed_free_change(p, x_l, x_u); i >= 0) {
-    h->err = "rpm_ipm_set_bounds: variable " + std::to_string(i) + " changes between fixed and free (the KKT layout is shared by all instances)";
-    return RPM_E_INVALID;
-  }
+  if (const int i = fixed_free_change(p, x_l, x_u); i >= 0)
+    return ipm_refuse(h, RPM_E_INVALID, "rpm_ipm_set_bounds", "variable " + std::to_string(i) + FIXED_FREE_CHANGE);
   // caller arrays go through the engine's staging slots (rpm_device.hip), not the runtime's pageable-copy path
   Engine& e = h->eng->e;
   int rc = dev_upload(e, h->D.vl0 + size_t(instance) * p.nv, x_l, size_t(p.n), STAGE_X);
   if (!rc) rc = dev_upload(e, h->D.vu0 + size_t(instance) * p.nv, x_u, size_t(p.n), STAGE_G);
   if (!rc) rc = dev_sync(e);
-  if (rc) h->err = e.err;
-  return rc;
+  return ipm_eng_fail(h, rc);
 }
 
 /* variable bounds of all instances at once: x_l, x_u are n_instances x n (host), e.g. the measured initial states of a
@@ -395,17 +393,15 @@ int rpm_ipm_set_all_bounds(rpm_ipm* h, const double* x_l, const double* x_u) {
   const IpmPlan& p = h->plan;
   const size_t B = size_t(h->D.B);
   for (size_t bi = 0; bi < B; ++bi)
-    if (const int i = fixed_free_change(p, x_l + bi * p.n, x_u + bi * p.n); i >= 0) {
-      h->err = "rpm_ipm_set_all_bounds: instance " + std::to_string(bi) + ", variable " + std::to_string(i) +
-               " changes between fixed and free (the KKT layout is shared by all instances)";
-      return RPM_E_INVALID;
-    }
+    if (const int i = fixed_free_change(p, x_l + bi * p.n, x_u + bi * p.n); i >= 0)
+      return ipm_refuse(h, RPM_E_INVALID, "rpm_ipm_set_all_bounds",
+                        "instance " + std::to_string(bi) + ", variable " + std::to_string(i) + FIXED_FREE_CHANGE);
   Engine& e = h->eng->e;
   hipStream_t st = static_cast<hipStream_t>(dev_stream(e));
   double *sl = nullptr, *su = nullptr;
   int rc = dev_stage_reserve(e, STAGE_X, B * p.n, &sl, nullptr);
   if (!rc) rc = dev_stage_reserve(e, STAGE_G, B * p.n, &su, nullptr);
-  if (rc) { h->err = e.err; return rc; }
+  if (rc) return ipm_eng_fail(h, rc);
   std::memcpy(sl, x_l, B * p.n * sizeof(double));
   std::memcpy(su, x_u, B * p.n * sizeof(double));
   IPM_TRY(h, hipMemcpy2DAsync(h->D.vl0, size_t(p.nv) * sizeof(double), sl, size_t(p.n) * sizeof(double), size_t(p.n) * sizeof(double), B,
@@ -423,16 +419,14 @@ namespace {
 // plan, because the KKT layout is shared by all instances.
 int initial_states_check(rpm_ipm* h, const char* who, int phase, const void* state0) {
   const Engine& e = h->eng->e;
-  if (phase < 0 || phase >= e.P) { h->err = std::string(who) + ": phase " + std::to_string(phase) + " is out of range"; return RPM_E_INVALID; }
-  if (!state0) { h->err = std::string(who) + ": state0 is NULL"; return RPM_E_INVALID; }
+  if (phase < 0 || phase >= e.P) return ipm_refuse(h, RPM_E_INVALID, who, "phase " + std::to_string(phase) + " is out of range");
+  if (!state0) return ipm_refuse(h, RPM_E_INVALID, who, "state0 is NULL");
   const PhaseHost& p = e.ph[size_t(phase)];
   for (int j = 0; j < p.nx; ++j) {
     const int i = p.var0 + j * (p.N + 1);
-    if (!h->plan.fixed[size_t(i)]) {
-      h->err = std::string(who) + ": variable " + std::to_string(i) + " (initial state " + std::to_string(j) +
-               ") is free in the solver's plan (the KKT layout is shared by all instances)";
-      return RPM_E_INVALID;
-    }
+    if (!h->plan.fixed[size_t(i)])
+      return ipm_refuse(h, RPM_E_INVALID, who, "variable " + std::to_string(i) + " (initial state " + std::to_string(j) +
+                                                   ") is free in the solver's plan (the KKT layout is shared by all instances)");
   }
   return RPM_OK;
 }
@@ -460,12 +454,10 @@ int rpm_ipm_set_initial_states(rpm_ipm* h, int phase, const double* state0) {
   const PhaseHost& p = e.ph[size_t(phase)];
   double *d_x, *d_l, *d_zL, *d_zU;
   if ((rc = host_form(h, &d_x, &d_l, &d_zL, &d_zU))) return rc;
-  rc = dev_upload(e, d_x, state0, size_t(h->D.B) * p.nx, STAGE_X);
-  if (rc) { h->err = e.err; return rc; }
+  if ((rc = dev_upload(e, d_x, state0, size_t(h->D.B) * p.nx, STAGE_X))) return ipm_eng_fail(h, rc);
   ipm_launch_set_state0(h->D, p.var0, p.N + 1, p.nx, d_x, static_cast<hipStream_t>(dev_stream(e)));
   if ((rc = launch_check(h, "ipm_set_state0_kernel"))) return rc;
-  if ((rc = dev_sync(e))) h->err = e.err;
-  return rc;
+  return ipm_eng_fail(h, dev_sync(e));
 }
 
 }  // extern "C"
@@ -473,8 +465,8 @@ int rpm_ipm_set_initial_states(rpm_ipm* h, int phase, const double* state0) {
 namespace rpm {
 int ipm_check_start_args(rpm_ipm* h, const char* who, const char* need, bool warm, const void* x, const void* lambda, const void* z_L,
                          const void* z_U) {
-  if (!x || (warm && !lambda)) { h->err = std::string(who) + ": " + need; return RPM_E_INVALID; }
-  if (warm && (!z_L != !z_U)) { h->err = std::string(who) + ": z_L and z_U are given together or both NULL"; return RPM_E_INVALID; }
+  if (!x || (warm && !lambda)) return ipm_refuse(h, RPM_E_INVALID, who, need);
+  if (warm && (!z_L != !z_U)) return ipm_refuse(h, RPM_E_INVALID, who, "z_L and z_U are given together or both NULL");
   return RPM_OK;
 }
 
@@ -483,7 +475,6 @@ int ipm_start(rpm_ipm* h, bool warm, const double* d_x, const double* d_lambda, 
   IpmDev& D = h->D;
   const IpmPlan& p = h->plan;
   const unsigned B = unsigned(D.B);
-  auto eng_fail = [&](int rc) { h->err = e.err; return rc; };
   dev_forget_persistent(e);   // the first Jacobian evaluation of this solve writes the constant block of D.jac, the later ones skip it
   if (h->lbfgs) lb_launch_reset(D, st);
   IPM_TRY(h, hipMemcpyAsync(D.xt, d_x, size_t(B) * p.n * sizeof(double), hipMemcpyDeviceToDevice, st));
@@ -491,15 +482,15 @@ int ipm_start(rpm_ipm* h, bool warm, const double* d_x, const double* d_lambda, 
   int rc;
   const bool scal = D.scal_on != 0;
   if (scal) {   // Ipopt's gradient-based scaling: factors from the gradients at the caller's starting point (before it is pushed inside its bounds)
-    if ((rc = dev_eval_obj(e, D.xt, D.objt, D.grad, st))) return eng_fail(rc);
-    if ((rc = dev_eval_cons(e, D.xt, D.gt, D.jac, 3 | 4 | 16, st))) return eng_fail(rc);
+    if ((rc = dev_eval_obj(e, D.xt, D.objt, D.grad, st))) return ipm_eng_fail(h, rc);
+    if ((rc = dev_eval_cons(e, D.xt, D.gt, D.jac, 3 | 4 | 16, st))) return ipm_eng_fail(h, rc);
     ipm_launch_scaling_factors(D, st);
     // this evaluation has written D.jac's constant block, which the later ones leave alone: it is scaled here, once
     if (e.nnz_jac > D.nnz_var) ipm_launch_scale(D, nullptr, D.jac, D.nnz_var, e.nnz_jac, nullptr, nullptr, st);
   }
   ipm_launch_pack_x(D, st);
   rc = dev_eval_cons(e, D.xe, D.g, nullptr, 1 | 4, st);
-  if (rc) return eng_fail(rc);
+  if (rc) return ipm_eng_fail(h, rc);
   if (scal) ipm_launch_scale(D, D.g, nullptr, 0, 0, nullptr, nullptr, st);
   ipm_launch_init_slack(D, st, warm ? 1 : 0);
   if (warm) ipm_launch_warm_duals(D, D.xt, d_lambda, d_zL, d_zU, st);   // (D.xt: the caller's x as it came)
@@ -526,17 +517,10 @@ int ipm_solve_dev(rpm_ipm* h, bool warm, double* d_x, double* d_lambda, double* 
   Engine& e = h->eng->e;
   IpmDev& D = h->D;
   hipStream_t st = static_cast<hipStream_t>(dev_stream(e));
-  h->lb_iterations = 0;
-  h->debug_started = false;
-  h->state_held = false;
-  h->debug_ls = 0;
-  h->total_factorizations = h->total_iterations = h->total_trials = h->total_soc = 0;
-  h->factor_ms = h->solve_ms = 0.0;
-  h->solve_pending = false;
-  if (D.sg != e.stride_g() || D.sv != e.stride_values()) {   // rpm_set_option refuses this while a solver is attached; belt and braces
-    h->err = "rpm_ipm_solve_dev: the engine's instance strides changed after rpm_ipm_create";
-    return RPM_E_INVALID;
-  }
+  h->hold.solve_begins();
+  h->stats = IpmStats{};
+  if (D.sg != e.stride_g() || D.sv != e.stride_values())   // rpm_set_option refuses this while a solver is attached; belt and braces
+    return ipm_refuse(h, RPM_E_INVALID, "rpm_ipm_solve_dev", "the engine's instance strides changed after rpm_ipm_create");
   // Ordering contract (rpm_hip.h): the loop runs on the engine's private stream.  Its first read of d_x / its first write of
   // d_lambda wait for everything the caller queued on `stream` before this call; the call returns after the solver's stream
   // has drained, so the results are complete for every stream and for the host.
@@ -545,11 +529,11 @@ int ipm_solve_dev(rpm_ipm* h, bool warm, double* d_x, double* d_lambda, double* 
 
   int rc = ipm_start(h, warm, d_x, d_lambda, d_zL, d_zU, st);
   if (rc) return rc;
-  const IpmLoop L{h, e, D, st, D.scal_on != 0};
+  const IpmLoop L = ipm_loop(h);
   for (;;) {
     if ((rc = L.evaluate_and_residual())) return rc;
     if (h->h_cnt[0] == 0) break;
-    h->total_iterations += 1;
+    h->stats.total_iterations += 1;
     if (!h->lbfgs && (rc = L.exact_hessian())) return rc;
     if ((rc = L.factor_with_inertia_correction())) return rc;
     if ((rc = L.substitute())) return rc;
@@ -574,20 +558,19 @@ int solve_from_host(rpm_ipm* h, bool warm, double* x, double* lambda, double* z_
   if (!rc && with_z) rc = dev_upload(e, d_zL, z_L, Bn, STAGE_G);
   if (!rc && with_z) rc = dev_upload(e, d_zU, z_U, Bn, STAGE_GRAD);
   if (!rc) rc = dev_sync(e);                                                                   // nothing in flight when the solve starts
-  if (rc) { h->err = e.err; return rc; }
+  if (rc) return ipm_eng_fail(h, rc);
   rc = ipm_solve_dev(h, warm, d_x, d_l, with_z ? d_zL : nullptr, with_z ? d_zU : nullptr, obj, status, iterations, kkt_error, nullptr);
   if (rc) return rc;
   rc = dev_download(e, x, d_x, Bn, STAGE_X);
   if (!rc && lambda) rc = dev_download(e, lambda, d_l, Bm, STAGE_LAMBDA);
   if (!rc && with_z) rc = dev_download(e, z_L, d_zL, Bn, STAGE_G);
   if (!rc && with_z) rc = dev_download(e, z_U, d_zU, Bn, STAGE_GRAD);
-  if (rc) h->err = e.err;
-  return rc;
+  return ipm_eng_fail(h, rc);
 }
 
 int bound_multipliers_ready(rpm_ipm* h, const double* z_L, const double* z_U) {
-  if (!z_L || !z_U) { h->err = "rpm_ipm_get_bound_multipliers: z_L or z_U is NULL"; return RPM_E_INVALID; }
-  if (!h->solved) { h->err = "rpm_ipm_get_bound_multipliers: no solve has finished"; return RPM_E_INVALID; }
+  if (!z_L || !z_U) return ipm_refuse(h, RPM_E_INVALID, "rpm_ipm_get_bound_multipliers", "z_L or z_U is NULL");
+  if (!h->hold.multipliers_ready()) return ipm_refuse(h, RPM_E_INVALID, "rpm_ipm_get_bound_multipliers", "no solve has finished");
   return RPM_OK;
 }
 }  // namespace
@@ -629,8 +612,7 @@ int rpm_ipm_get_bound_multipliers(rpm_ipm* h, double* z_L, double* z_U) {
   if ((rc = launch_check(h, "ipm_bound_mult_kernel"))) return rc;
   rc = dev_download(e, z_L, d_zL, Bn, STAGE_X);
   if (!rc) rc = dev_download(e, z_U, d_zU, Bn, STAGE_G);
-  if (rc) h->err = e.err;
-  return rc;
+  return ipm_eng_fail(h, rc);
 }
 
 int rpm_ipm_solve(rpm_ipm* h, double* x, double* lambda, double* obj, int* status, int* iterations, double* kkt_error) {

@@ -9,6 +9,18 @@
 
 #include "rpm_device_internal.hpp"
 #include "rpm_ipm_device.hpp"
+#include "rpm_ipm_hold.hpp"
+
+namespace rpm {
+// what a solve counts (rpm_ipm_get_stats, rpm_ipm_get_kernel_times) and what its loop carries from one step to the next; a solve
+// and rpm_ipm_debug_pass start from IpmStats{}, the sensitivities keep a copy and put it back
+struct IpmStats {
+  int total_iterations = 0, total_factorizations = 0, total_trials = 0, total_soc = 0;
+  double factor_ms = 0.0, solve_ms = 0.0;   // inside the factorisation / the substitution kernels (HIP events)
+  bool solve_pending = false;    // a substitution's time is read once the line search's first fetch_counts has waited for it
+  int lb_iterations = 0;         // iterations of the running solve: an upper bound of the pairs any instance holds
+};
+}  // namespace rpm
 
 struct rpm_ipm {
   rpm_engine* eng = nullptr;
@@ -22,20 +34,12 @@ struct rpm_ipm {
   int factor_mt = rpm::IPM_MT;
   std::string err;
   std::vector<rpm::IpmInst> h_inst;
-  int total_factorizations = 0, total_iterations = 0, total_trials = 0, total_soc = 0;
+  rpm::IpmStats stats;
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};   // around the factorisation and the substitution of an iteration
-  double factor_ms = 0.0, solve_ms = 0.0;
-  bool solve_pending = false;
   bool attached = false;
   bool lbfgs = false;            // hessian-approximation = limited-memory (rpm_ipm_lbfgs.hip)
-  int lb_iterations = 0;         // iterations of the running solve: an upper bound of the pairs any instance holds
-  bool solved = false;           // a solve has finished: D.zL / D.zU hold its bound multipliers (rpm_ipm_get_bound_multipliers)
-  bool debug_started = false;    // rpm_ipm_debug_start was the last call to touch the state: rpm_ipm_debug_pass may run on it
-  int debug_ls = 0;              // 1: rpm_ipm_debug_pass(stage 3) left instances running, rpm_ipm_debug_line_search may follow; 2: it has run
-                                 // (it may run again, or rpm_ipm_debug_update); 0: neither
+  rpm::IpmHold hold;             // what the arrays of D hold between two calls: what may be called after what (rpm_ipm_hold.hpp)
   double* d_host_form = nullptr; // the host-pointer entry points' device copies of x, lambda, z_L, z_U (B x (3 n + m)), on first use
-  bool state_held = false;       // D.v, D.lam, D.zL, D.zU, D.vl, D.vu hold a state sensitivities may be taken at: a solve has finished, or
-                                 // rpm_ipm_debug_start / rpm_ipm_debug_pass was the last call to touch it
   // rpm_ipm_sens.hip: its work space (B x n_par x Nt_alloc right-hand sides), the source table of the last parameter list, the
   // plan's fixed pattern and the host-pointer forms' device block; each on first use, kept, grown only
   struct Sens {
@@ -56,16 +60,24 @@ struct rpm_ipm {
   }
 };
 
-#define IPM_TRY(h, call)                                                      \
-  do {                                                                        \
-    hipError_t _s = (call);                                                   \
-    if (_s != hipSuccess) {                                                   \
-      (h)->err = std::string(#call) + ": " + hipGetErrorString(_s);          \
-      return RPM_E_DEVICE;                                                    \
-    }                                                                         \
+#define IPM_TRY(h, call)                                                                             \
+  do {                                                                                               \
+    hipError_t _s = (call);                                                                          \
+    if (_s != hipSuccess) return rpm::ipm_refuse((h), RPM_E_DEVICE, #call, hipGetErrorString(_s)); \
   } while (0)
 
 namespace rpm {
+
+// every refusal and every failure: `code` with h->err = "<who>: <why>" (who empty: the bare <why>)
+inline int ipm_refuse(rpm_ipm* h, int code, const std::string& who, const std::string& why) {
+  h->err = who.empty() ? why : who + ": " + why;
+  return code;
+}
+// what a call into the engine returned, passed on: its text goes with a failure
+inline int ipm_eng_fail(rpm_ipm* h, int rc) {
+  if (rc) h->err = h->eng->e.err;
+  return rc;
+}
 
 template <class T>
 int ipm_alloc(rpm_ipm* h, T** dst, size_t count, const T* src = nullptr) {
@@ -78,12 +90,8 @@ int ipm_alloc(rpm_ipm* h, T** dst, size_t count, const T* src = nullptr) {
 }
 
 inline int launch_check(rpm_ipm* h, const char* what) {
-  hipError_t s = hipGetLastError();
-  if (s != hipSuccess) {
-    h->err = std::string(what) + ": " + hipGetErrorString(s);
-    return RPM_E_DEVICE;
-  }
-  return RPM_OK;
+  const hipError_t s = hipGetLastError();
+  return s == hipSuccess ? RPM_OK : ipm_refuse(h, RPM_E_DEVICE, what, hipGetErrorString(s));
 }
 inline int factor_and_solve_launch(rpm_ipm* h, hipStream_t st, bool factor, bool solve, int check_status, int forward_done = 0) {
   if (factor) kkt_launch_factor(h->D, h->factor_mt, h->factor_lds, st);
@@ -106,6 +114,57 @@ inline int ipm_abi_status(int device_status) {   // IpmInst::status -> rpm_hip.h
   return device_status == 1 ? 0 : (device_status == 6 ? 1 : device_status);
 }
 
+// ---- reading state back to the host and editing it there (the test hooks, the sensitivities).  Pageable copies on the solver's
+// stream, which the caller or the helper synchronises; not the solve's path.
+inline hipStream_t ipm_stream(rpm_ipm* h) { return static_cast<hipStream_t>(dev_stream(h->eng->e)); }
+
+// B rows of `width` doubles, `pitch` apart on the device, packed into dst; a NULL dst or an empty row is skipped.  Blocking.
+inline hipError_t ipm_rows(const IpmDev& D, double* dst, const double* src, size_t width, size_t pitch) {
+  if (!dst || !width) return hipSuccess;
+  return hipMemcpy2D(dst, width * sizeof(double), src, pitch * sizeof(double), width * sizeof(double), size_t(D.B), hipMemcpyDeviceToHost);
+}
+
+// KKT order -> unknown order through the plan's permutation: out is B x P x Nt, its row (bi, k) is row k B + bi of kkt (rows of
+// Nt_alloc) — the layout of the sensitivities' work space; with P = 1 that of D.rhs
+inline void ipm_from_kkt_order(const IpmPlan& p, size_t B, size_t P, const double* kkt, double* out) {
+  for (size_t r = 0; r < B * P; ++r)
+    for (size_t a = 0; a < size_t(p.Nt); ++a) out[r * p.Nt + a] = kkt[((r % P) * B + r / P) * p.Nt_alloc + size_t(p.pos[a])];
+}
+// the same from the device: d_kkt down on the solver's stream, synchronised, then permuted
+inline int ipm_download_unknown_order(rpm_ipm* h, const double* d_kkt, size_t P, double* out) {
+  std::vector<double> w(size_t(h->D.B) * P * size_t(h->plan.Nt_alloc));
+  IPM_TRY(h, hipMemcpyAsync(w.data(), d_kkt, w.size() * sizeof(double), hipMemcpyDeviceToHost, ipm_stream(h)));
+  IPM_TRY(h, hipStreamSynchronize(ipm_stream(h)));
+  ipm_from_kkt_order(h->plan, size_t(h->D.B), P, w.data(), out);
+  return RPM_OK;
+}
+
+// the instance records: down (synchronised), up (queued: `inst` outlives the caller's next synchronise), both around edit(bi, record)
+inline int ipm_download_records(rpm_ipm* h, std::vector<IpmInst>& inst) {
+  inst.resize(size_t(h->D.B));
+  IPM_TRY(h, hipMemcpyAsync(inst.data(), h->D.inst, inst.size() * sizeof(IpmInst), hipMemcpyDeviceToHost, ipm_stream(h)));
+  IPM_TRY(h, hipStreamSynchronize(ipm_stream(h)));
+  return RPM_OK;
+}
+inline int ipm_upload_records(rpm_ipm* h, const std::vector<IpmInst>& inst) {
+  IPM_TRY(h, hipMemcpyAsync(h->D.inst, inst.data(), inst.size() * sizeof(IpmInst), hipMemcpyHostToDevice, ipm_stream(h)));
+  return RPM_OK;
+}
+template <class F>
+int ipm_edit_records(rpm_ipm* h, std::vector<IpmInst>& inst, F edit) {
+  if (int rc = ipm_download_records(h, inst)) return rc;
+  for (size_t bi = 0; bi < inst.size(); ++bi) edit(bi, inst[bi]);
+  return ipm_upload_records(h, inst);
+}
+
+// level 1 left to the fill kernel while this lives (IpmDev::df_on off): the launches in its scope work on what is in the storage
+struct IpmFusedFillOff {
+  IpmDev& D;
+  const int keep;
+  explicit IpmFusedFillOff(IpmDev& d) : D(d), keep(d.df_on) { D.df_on = 0; }
+  ~IpmFusedFillOff() { D.df_on = keep; }
+};
+
 // ---- one solve: the steps of an iteration, in the order ipm_solve_dev takes them (rpm_ipm_debug_pass runs the first of them on an
 // injected state: the same members, no launch sequence of its own)
 struct IpmLoop {
@@ -114,7 +173,6 @@ struct IpmLoop {
   IpmDev& D;
   hipStream_t st;
   bool scal;     // nlp_scaling is on
-  int eng_fail(int rc) const { h->err = e.err; return rc; }
 
   int fetch_counts() const {
     IPM_TRY(h, hipMemcpyAsync(h->h_cnt, D.cnt, 4 * sizeof(int), hipMemcpyDeviceToHost, st));
@@ -125,10 +183,10 @@ struct IpmLoop {
   int evaluate_and_residual() const {
     int rc;
     ipm_launch_pack_x(D, st);
-    if ((rc = dev_eval_obj(e, D.xe, D.obj, D.grad, st))) return eng_fail(rc);
+    if ((rc = dev_eval_obj(e, D.xe, D.obj, D.grad, st))) return ipm_eng_fail(h, rc);
     // D.jac is this solver's own array, written by the tile kernel only: its constant Doffdiag block (55 % of the metric
     // problem's Jacobian) is written by the first evaluation of a solve and left alone afterwards (flag 16)
-    if ((rc = dev_eval_cons(e, D.xe, D.g, D.jac, 3 | 4 | 16, st))) return eng_fail(rc);
+    if ((rc = dev_eval_cons(e, D.xe, D.g, D.jac, 3 | 4 | 16, st))) return ipm_eng_fail(h, rc);
     // (without the scaling's own evaluation the first pass of a solve writes the constant block too: then all of D.jac is scaled)
     if (scal) ipm_launch_scale(D, D.g, D.jac, 0, D.nnz_var, D.obj, D.grad, st);
     IPM_TRY(h, hipMemsetAsync(D.cnt, 0, 4 * sizeof(int), st));
@@ -138,7 +196,7 @@ struct IpmLoop {
   }
   int exact_hessian() const {
     if (scal) ipm_launch_scale_lambda(D, st);            // sf (H_f + sum (lambda_i sc_i / sf) H_ci)
-    if (int rc = dev_eval_h(e, D.xe, 1.0, scal ? D.lam_h : D.lam, D.hess, st)) return eng_fail(rc);
+    if (int rc = dev_eval_h(e, D.xe, 1.0, scal ? D.lam_h : D.lam, D.hess, st)) return ipm_eng_fail(h, rc);
     if (scal) ipm_launch_scale_hessian(D, st);
     return RPM_OK;
   }
@@ -152,17 +210,17 @@ struct IpmLoop {
       if ((rc = factor_and_solve_launch(h, st, true, false, 1))) return rc;
       IPM_TRY(h, hipEventRecord(h->ev[1], st));
       ipm_launch_inertia(D, st);
-      h->total_factorizations += 1;
+      h->stats.total_factorizations += 1;
       if ((rc = fetch_counts())) return rc;
       float ms = 0.f;
-      if (hipEventElapsedTime(&ms, h->ev[0], h->ev[1]) == hipSuccess) h->factor_ms += ms;
+      if (hipEventElapsedTime(&ms, h->ev[0], h->ev[1]) == hipSuccess) h->stats.factor_ms += ms;
       if (h->h_cnt[1] == 0) break;
     }
     return RPM_OK;
   }
   int substitute() const {
     IPM_TRY(h, hipEventRecord(h->ev[2], st));
-    if (h->lbfgs && h->lb_iterations > 0) {
+    if (h->lbfgs && h->stats.lb_iterations > 0) {
       // Z = K0^-1 E with the factors in place (all columns of all instances in one pass), then C = M - E'Z
       lb_launch_columns_and_solve(D, st);
       lb_launch_small(D, st);
@@ -170,7 +228,7 @@ struct IpmLoop {
     if (int rc = factor_and_solve_launch(h, st, false, true, 1, 1)) return rc;   // (the right-hand side the factorisation was given)
     if (h->lbfgs) lb_launch_correct(D, 1, st);
     IPM_TRY(h, hipEventRecord(h->ev[3], st));
-    h->solve_pending = true;   // its time is read once the line search's first fetch_counts has waited for it
+    h->stats.solve_pending = true;   // its time is read once the line search's first fetch_counts has waited for it
     return RPM_OK;
   }
   // the step, then rounds: every pending instance evaluates one trial point per round — its next backtracking step, or the next
@@ -193,20 +251,20 @@ struct IpmLoop {
       if ((rc = factor_and_solve_launch(h, st, false, true, 2))) return rc;
       if (h->lbfgs) lb_launch_correct(D, 2, st);
       ipm_launch_soc_direction(D, st);
-      h->total_soc += 1;
+      h->stats.total_soc += 1;
     }
     ipm_launch_trial(D, st);
-    if ((rc = dev_eval_obj(e, D.xt, D.objt, nullptr, st))) return eng_fail(rc);
-    if ((rc = dev_eval_cons(e, D.xt, D.gt, nullptr, 1 | 4, st))) return eng_fail(rc);
+    if ((rc = dev_eval_obj(e, D.xt, D.objt, nullptr, st))) return ipm_eng_fail(h, rc);
+    if ((rc = dev_eval_cons(e, D.xt, D.gt, nullptr, 1 | 4, st))) return ipm_eng_fail(h, rc);
     if (scal) ipm_launch_scale(D, D.gt, nullptr, 0, 0, D.objt, nullptr, st);
     IPM_TRY(h, hipMemsetAsync(D.cnt + 2, 0, 2 * sizeof(int), st));
     ipm_launch_accept(D, st);
-    h->total_trials += 1;
+    h->stats.total_trials += 1;
     if ((rc = fetch_counts())) return rc;
-    if (h->solve_pending) {
+    if (h->stats.solve_pending) {
       float ms = 0.f;
-      if (hipEventElapsedTime(&ms, h->ev[2], h->ev[3]) == hipSuccess) h->solve_ms += ms;
-      h->solve_pending = false;
+      if (hipEventElapsedTime(&ms, h->ev[2], h->ev[3]) == hipSuccess) h->stats.solve_ms += ms;
+      h->stats.solve_pending = false;
     }
     return RPM_OK;
   }
@@ -224,7 +282,7 @@ struct IpmLoop {
     ipm_launch_update(D, st);
     if (h->lbfgs) {
       ipm_launch_jt_lambda_into(D, D.lb_gold, st);   // grad_x L(x_old, lambda_new): D.grad / D.jac still belong to the old iterate
-      h->lb_iterations += 1;
+      h->stats.lb_iterations += 1;
     }
     return launch_check(h, "ipm iteration");
   }
@@ -256,10 +314,10 @@ struct IpmLoop {
       if (iterations) iterations[bi] = S.iter;
       if (kkt_error) kkt_error[bi] = S.err0;
     }
-    h->solved = true;
-    h->state_held = true;
+    h->hold.solve_ends();
     return RPM_OK;
   }
 };
+inline IpmLoop ipm_loop(rpm_ipm* h) { return IpmLoop{h, h->eng->e, h->D, ipm_stream(h), h->D.scal_on != 0}; }
 
 }  // namespace rpm

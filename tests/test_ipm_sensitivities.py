@@ -184,6 +184,7 @@ def test_every_instance_as_if_alone_and_nothing_disturbed(built):
     z2 = ipm.bound_multipliers()
     assert np.array_equal(z[0], z2[0]) and np.array_equal(z[1], z2[1])
     warm_after = ipm.solve(sol["x"], sol["lambda"], z)
+    warm_after_stats = ipm.stats()
     again = ipm.solve(x0)
     for k in ("x", "lambda", "obj", "status", "iterations", "kkt_error"):
         assert np.array_equal(again[k], sol[k]), k
@@ -191,6 +192,7 @@ def test_every_instance_as_if_alone_and_nothing_disturbed(built):
     warm_plain = ipm.solve(again["x"], again["lambda"], z3)
     for k in ("x", "lambda", "z_L", "z_U", "obj", "status", "iterations", "kkt_error"):
         assert np.array_equal(warm_after[k], warm_plain[k]), k
+    assert ipm.stats() == warm_after_stats
     # a B = 1 solver on every instance
     e1 = NLPEngine(problems.quadrotor(2, 4), ws._exact(), n_instances=1, device=0)
     s1 = BatchedIPM(e1)
