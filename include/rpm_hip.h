@@ -53,7 +53,8 @@ enum {
   RPM_PROBLEM_MIN_TIME_CLIMB = 5,  /* authored here (BASELINE config 2) */
   RPM_PROBLEM_QUADROTOR = 6,       /* authored here (BASELINE config 5) */
   RPM_PROBLEM_PARAM_SLED = 7,      /* authored here: minimum-time sled with one static parameter (nq = 1), known optimum 2.5 */
-  RPM_PROBLEM_PARAM_OSC = 8,       /* authored here: two linked phases, two static parameters each (nq = 2), path + events + links on them */
+  RPM_PROBLEM_PARAM_OSC = 8,       /* authored here: two linked phases, two static parameters each (nq = 2), path + events + links on them
+                                      (both: limited-memory or RPM_HESSIAN_EXACT_PARAMETERS, never plain RPM_HESSIAN_EXACT) */
   RPM_PROBLEM_USER = 100           /* the functor `rpm::UserProblem` of a user's header, in a library built from that header
                                       (lpopc_amd/userproblem.py, INTEGRATION.md "your own problem"): the stand-in for
                                       subclassing FunctionWrapper (Core/LpFunctionWrapper.h:50-69) */
@@ -62,7 +63,14 @@ enum {
 /* first-derive option, Core/LpOptDerive.hpp:29-32 */
 enum { RPM_DERIVE_FINITE_DIFFERENCE = 0, RPM_DERIVE_ANALYTIC = 1 };
 /* hessian-approximation option, Core/LpNLPWrapper.hpp:71-72 */
-enum { RPM_HESSIAN_LIMITED_MEMORY = 0, RPM_HESSIAN_EXACT = 1 };
+enum {
+  RPM_HESSIAN_LIMITED_MEMORY = 0,
+  RPM_HESSIAN_EXACT = 1,             /* lpopc's own second differences; refused for problems with static parameters (nq > 0) */
+  RPM_HESSIAN_EXACT_PARAMETERS = 2   /* "exact-parameters": the same Hessian with the rows of the static parameters by the corrected
+                                        formulas (DESIGN.md section 3 lists every departure from Core/LpHessian.cpp); with nq = 0 in
+                                        every phase it is RPM_HESSIAN_EXACT bit for bit.  rpm_create turns it into RPM_HESSIAN_EXACT
+                                        plus an engine flag: everything downstream sees an exact-Hessian engine */
+};
 /* how work is split when shard_world > 1 */
 enum { RPM_SHARD_NONE = 0, RPM_SHARD_INTERVALS = 1 };
 
@@ -426,8 +434,9 @@ int rpm_hpliu_refine(rpm_hpliu* h, rpm_engine* e, const double* x, const double*
  * stands for the Hessian of the Lagrangian: RPM_HESSIAN_EXACT = lpopc's finite-difference Hessian (rpm_eval_h);
  * RPM_HESSIAN_LIMITED_MEMORY — lpopc's default, Core/LpNLPWrapper.hpp:71 — = Ipopt's limited-memory BFGS (history 6, scaling
  * s'y / s's, its skipping rule; csrc/rpm_ipm_lbfgs.hip): the KKT matrix of a diagonal Hessian is factored and the low-rank
- * part enters every solve through the Sherman-Morrison-Woodbury formula (12 more substitutions per iteration); also the only
- * mode for problems with static parameters (nq > 0).  Set the engine's "instance_align" before rpm_ipm_create.
+ * part enters every solve through the Sherman-Morrison-Woodbury formula (12 more substitutions per iteration).  Problems with
+ * static parameters (nq > 0) have the limited-memory mode and RPM_HESSIAN_EXACT_PARAMETERS (the parameters sit in the border of
+ * the KKT layouts); plain RPM_HESSIAN_EXACT refuses them.  Set the engine's "instance_align" before rpm_ipm_create.
  *   rpm_ipm_set_option: "tol" (1e-8), "max_iter" (3000), "mu_init" (0.1), "bound_push", "bound_frac" (1e-2),
  *                       "delta_c" (1e-9, constraint regularisation that makes the pivot-free LDL^T well defined; keep it
  *                       well below bound_relax_factor),
@@ -564,11 +573,24 @@ int rpm_ipm_get_bound_multipliers_dev(rpm_ipm* s, double* d_z_L, double* d_z_U, 
  * allocated on first use, kept, and grows only for a larger n_par.  The iterate, the multipliers, the instance records,
  * rpm_ipm_get_bound_multipliers and the statistics of the last solve are what they were before the call: a following
  * rpm_ipm_solve[_warm] is bit for bit what it is without the call in between.  The calling thread's current device is restored.
+ * Solver option "sens_refine" (-1 = automatic, the default: 2 rounds on an engine created with RPM_HESSIAN_EXACT_PARAMETERS whose
+ * phases have static parameters, none on every other engine; 0 = none; 1 .. 8 = that many rounds of iterative refinement of every column, sol += K^-1 (rhs - K sol) with
+ * the same factors and the residual formed from the matrix's sources — the Hessian and Jacobian triplets, the slacks' -1, the
+ * diagonal terms — in a fixed order, so the result is deterministic; the work space triples).  A refined call factors with
+ * delta_w starting at 1e-8 instead of 0 (the pivot-free LDL^T is stable on a quasi-definite matrix) and takes the residual against
+ * the matrix without it, so the rounds remove what it adds; info is 1 only when the inertia correction went beyond that floor, and
+ * delta_w reports where the factorisation ended (1e-8 at info 0).  Where W + Sigma is nearly singular at delta_w = 0 (a bang-bang
+ * plan with a fixed static parameter: no curvature in the states, their bounds inactive) the plain columns keep about three digits;
+ * two rounds agree with a dense solve to 4e-11 — hence the automatic rounds exactly where sensitivities to a
+ * fixed static parameter can be asked for.  Without rounds every bit is what it was.
  * Refusals, all decided on the host before anything is queued — RPM_E_INVALID with a message: NULL var_index or dx, n_par outside
  * 1 .. 32, an index out of range, a duplicate, a free variable (named), no state to take them at; RPM_E_UNSUPPORTED:
  * hessian-approximation = limited-memory (a quasi-Newton W gives no sensitivities), nlp_scaling = 1.
- * rpm_ipm_initial_state_variables (host only): the nx variables rpm_ipm_set_initial_states writes, x_state0 + j (N + 1). */
+ * rpm_ipm_initial_state_variables (host only): the nx variables rpm_ipm_set_initial_states writes, x_state0 + j (N + 1).
+ * rpm_ipm_parameter_variables (host only): the nq static parameters of the phase, x_t0 + 2 + j — with parameter_min ==
+ * parameter_max they are fixed variables of the plan, and the columns above are d(plan) / d(parameter). */
 int rpm_ipm_initial_state_variables(rpm_ipm* s, int phase, int* var_index /* nx */);
+int rpm_ipm_parameter_variables(rpm_ipm* s, int phase, int* var_index /* nq */);
 int rpm_ipm_sensitivities_dev(rpm_ipm* s, int n_par, const int* var_index, double* d_dx, double* d_dlambda, double* delta_w, int* info,
                               void* stream);
 int rpm_ipm_sensitivities(rpm_ipm* s, int n_par, const int* var_index, double* dx, double* dlambda, double* delta_w, int* info);
@@ -701,7 +723,12 @@ int rpm_eval_h_dev(rpm_engine* e, const double* d_x, double obj_factor, const do
  * rpm_eval_h only ever gives that kernel zeros to add.  tmp (HOST): n_instances x tmp_len doubles, tmp_len = 3 * (sum of
  * the phases' N); phase p starts at 3 * (nodes of the phases before it) and holds N per-node terms of the t0t0 entry,
  * then N of tftf, then N of tft0.  out (HOST): [(instance * n_phases + p) * 3 + i], i = 0 t0t0, 1 tft0, 2 tftf, read back
- * from where rpm_eval_h stores them. */
+ * from where rpm_eval_h stores them.  An engine with static parameters (nq > 0) reduces more rows than these three and a
+ * non-autonomous parameter functor exercises them through rpm_eval_h itself: RPM_E_UNSUPPORTED there.
+ * rpm_debug_hess_structure (HOST only, no device): the structure build_hessian_tables gives for a caller-given dependency pattern
+ * instead of the device probe's — dep: per phase (nx + nc) x (nx + nu) zeros and ones, column-major, phases concatenated; iRow / jCol
+ * (capacity entries, may be NULL to ask for *nnz_h alone).  The engine is left as it was. */
+int rpm_debug_hess_structure(rpm_engine* e, const int* dep, int dep_len, int capacity, int* iRow, int* jCol, int* nnz_h);
 int rpm_debug_hess_tt(rpm_engine* e, const double* tmp, int tmp_len, double* out);
 /* Test hook of the pipelined kernel's tile orders (host arithmetic only): the slot in [0, nh * nb) of a round of tiles that
  * half `half` of workgroup b takes in a launch of nb workgroups of nh halves under "tile_order" = order; -1: bad argument. */

@@ -184,7 +184,7 @@ def lower(problem, options=None, n_instances=1, shard_mode=0, shard_rank=0, shar
     desc.consts = _darr(fun.consts, keep)
     desc.fd_tol = float(options.GetNumericValue("finite-difference-tol"))
     desc.first_derive = 1 if options.GetStringValue("first-derive") == "analytic" else 0
-    desc.hessian_approximation = 1 if options.GetStringValue("hessian-approximation") == "exact" else 0
+    desc.hessian_approximation = {"limited-memory": 0, "exact": 1, "exact-parameters": 2}[options.GetStringValue("hessian-approximation")]   # RPM_HESSIAN_*
     desc.n_instances = int(n_instances)
     desc.shard_mode = int(shard_mode)
     desc.shard_rank = int(shard_rank)

@@ -678,11 +678,41 @@ int rpm_debug_tile_slot(int order, int nh, int nb, int b, int half) {
   if (order < 0 || order >= rpm::PL_TILE_ORDERS || nh < 1 || nb < 1 || b < 0 || b >= nb || half < 0 || half >= nh) return -1;
   return rpm::dev_pl_tile_slot(order, nh, nb, b, half);
 }
+int rpm_debug_hess_structure(rpm_engine* h, const int* dep, int dep_len, int capacity, int* iRow, int* jCol, int* nnz_h) {
+  if (!h) return RPM_E_INVALID;
+  RPM_GUARD_BEGIN
+  Engine& e = h->e;
+  if (e.hessian_mode != RPM_HESSIAN_EXACT) return fail(e, RPM_E_UNSUPPORTED, "debug_hess_structure: the engine was created with hessian-approximation=limited-memory");
+  int want = 0;
+  for (const rpm::PhaseHost& p : e.ph) want += (p.nx + p.nc) * (p.nx + p.nu);
+  if (!dep || dep_len != want || !nnz_h) return fail(e, RPM_E_INVALID, "debug_hess_structure: dep holds (nx + nc) x (nx + nu) flags per phase");
+  // on a copy of the host description: the engine's own tables, built from the device probe, stay what they are
+  Engine c;
+  c.P = e.P; c.L = e.L; c.ph = e.ph; c.links = e.links;
+  c.hess_dep.assign(e.P, {});
+  int off = 0;
+  for (int i = 0; i < e.P; ++i) {
+    const int len = (e.ph[i].nx + e.ph[i].nc) * (e.ph[i].nx + e.ph[i].nu);
+    c.hess_dep[i].assign(dep + off, dep + off + len);
+    off += len;
+  }
+  rpm::build_hessian_tables(c);
+  *nnz_h = c.nnz_h;
+  if (iRow || jCol) {
+    if (!iRow || !jCol || capacity < c.nnz_h) return fail(e, RPM_E_INVALID, "debug_hess_structure: iRow / jCol are too short");
+    std::memcpy(iRow, c.hes_i.data(), sizeof(int) * c.nnz_h);
+    std::memcpy(jCol, c.hes_j.data(), sizeof(int) * c.nnz_h);
+  }
+  return RPM_OK;
+  RPM_GUARD_END(h->e)
+}
 int rpm_debug_hess_tt(rpm_engine* h, const double* tmp, int tmp_len, double* out) {
   if (!h) return RPM_E_INVALID;
   RPM_GUARD_BEGIN
   Engine& e = h->e;
   if (e.hessian_mode != RPM_HESSIAN_EXACT) return fail(e, RPM_E_UNSUPPORTED, "debug_hess_tt: the engine was created with hessian-approximation=limited-memory");
+  for (const rpm::PhaseHost& p : e.ph)
+    if (p.nq > 0) return fail(e, RPM_E_UNSUPPORTED, "debug_hess_tt: the engine has parameter rows (nq > 0); eval_h of a non-autonomous functor exercises the reduction there");
   int rc = rpm::ensure_hessian(e);
   if (rc) return rc;
   if (!tmp || !out || tmp_len != e.hess_tmp_len) return fail(e, RPM_E_INVALID, "debug_hess_tt: tmp holds three rows of N terms per phase");

@@ -208,7 +208,7 @@ void device_destroy(Engine& e) {
   void* ptrs[] = {d->d_phases, d->d_tiles, d->d_tasks, d->d_nodes, d->d_points, d->d_weights, d->d_diag,
                   d->d_dvals, d->d_doff, d->d_consts, d->d_inst_consts, d->d_alin_v, d->d_links, d->d_alin_j, d->d_x, d->d_g,
                   d->d_values, d->d_grad, d->d_obj, d->d_lambda, d->d_hess, d->d_partial, d->d_hpairs, d->d_hphases,
-                  d->d_hends, d->d_hlinks, d->d_htiles, d->d_htmp};
+                  d->d_hends, d->d_hlinks, d->d_htiles, d->d_hred, d->d_htmp};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   if (d->d_flag) (void)hipFree(d->d_flag);

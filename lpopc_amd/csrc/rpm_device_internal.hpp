@@ -78,6 +78,7 @@ struct HParams {
   const HessEndDev* ends;
   const HessLinkDev* links;
   const int* tiles;     // per workgroup: phase, k0, cnt
+  const int* red_dst;   // I-part offsets of the parameter scalars (HessPhaseDev::red0)
   int n_tiles, th, n_ends, n_links, nnz_h, tmp_len;
 };
 
@@ -119,6 +120,7 @@ struct Device {
   HessEndDev* d_hends = nullptr;
   HessLinkDev* d_hlinks = nullptr;
   int* d_htiles = nullptr;
+  int* d_hred = nullptr;
   double* d_htmp = nullptr;
   HParams hp{};
   size_t hess_lds = 0;

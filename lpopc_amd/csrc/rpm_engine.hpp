@@ -50,11 +50,13 @@ struct TileDev {
 };
 
 // ---- exact-Hessian mode (hessian-approximation=exact), LpHessian.cpp ------------------------------
-// One record per perturbation pair (a >= b over the node variables [x.., u.., t]) of a phase.
+// One record per perturbation pair (a >= b over the node variables [x.., u.., t, p..]) of a phase.
 struct HessPairDev {
   int a, b;
-  int kind;        // 0: not stored (pattern H(a,b) = 0), 1: N-long block, 2: (t, v) pair -> t0 and tf row blocks, 3: (t, t)
-  int dst0, dst1;  // offsets inside the phase's I-part (kind 1: dst0; kind 2: t0 block, tf block)
+  int kind;        // 0: not stored (pattern H(a,b) = 0), 1: N-long block, 2: (t, v) pair -> t0 and tf row blocks, 3: (t, t),
+                   // 4: (p, t) -> per-node terms of the (p, t0) and (p, tf) scalars, 5: (p, p') -> per-node terms of that scalar
+  int dst0, dst1;  // offsets inside the phase's I-part (kind 1: dst0; kind 2: t0 block, tf block); kinds 4 and 5: rows of the
+                   // phase's scratch block (kind 4: the t0 row, the tf row; kind 5: dst0)
 };
 struct HessPhaseDev {
   int pair0;             // first HessPairDev of the phase
@@ -62,13 +64,15 @@ struct HessPhaseDev {
   int nI, nE;
   int tt_dst[3];         // I-part offsets of the t0t0, tft0, tftf scalars
   int end0, n_end;       // endpoint entries (HessEndDev) of the phase
-  int tt_tmp;            // offset of the phase's per-node tt terms in the scratch array (3 x N)
+  int tt_tmp;            // offset of the phase's per-node terms in the scratch array ((3 + n_red) x N)
+  int red0, n_red;       // parameter rows of the scratch block beyond the first three: 2 nq + nq (nq + 1) / 2 of them, row 3 + r
+                         // sums into I-part offset HParams::red_dst[red0 + r]
 };
 // One E-part (events + Mayer) entry: second difference w.r.t. endpoint variables a then b of
-// W = [x0.., xf.., t0, tf]; the denominator is pert(da)*pert(db) exactly as the reference writes it
-// (including its pertxf(istate) quirk, LpHessian.cpp:1588,1612,1826,1850).
+// W = [x0.., xf.., t0, tf, p..]; the denominator is pert(da)*pert(db) exactly as the reference writes it
+// (including its pertxf(istate) quirk, LpHessian.cpp:1588,1612,1826,1850); pairs with a parameter have da = a, db = b.
 struct HessEndDev { int phase, a, b, da, db, dst; };
-// One linkage entry: variables a then b of [xf_left.., x0_right..]
+// One linkage entry: variables a then b of [xf_left.., x0_right.., p_left.., p_right..]
 struct HessLinkDev { int pair, a, b, dst; };
 
 // endpoint work items, one workgroup each: 0 = linear rows, 1 = events of phase idx, 2 = linkage pair idx
@@ -132,6 +136,7 @@ struct Engine {
   std::vector<double> inst_consts;   // n_instances x consts.size() once rpm_set_instance_constants was used, else empty (shared)
   double fd_tol = 1e-6;
   int first_derive = 0, hessian_mode = 0;
+  bool hess_parameters = false;      // created with RPM_HESSIAN_EXACT_PARAMETERS (hessian_mode is RPM_HESSIAN_EXACT then)
   int n_instances = 1;
   int shard_mode = 0, shard_rank = 0, shard_world = 1;
   // per-mesh data
@@ -151,6 +156,7 @@ struct Engine {
   std::vector<HessPhaseDev> hess_phases;
   std::vector<HessEndDev> hess_ends;
   std::vector<HessLinkDev> hess_links;
+  std::vector<int> hess_red_dst;                   // HessPhaseDev::red0
   int hess_tmp_len = 0;
   // device tables (host copies)
   std::vector<PhaseDev> phd;

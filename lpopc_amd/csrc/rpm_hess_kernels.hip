@@ -8,8 +8,9 @@ namespace rpm {
 // Exact-Hessian mode (hessian-approximation=exact): forward SECOND differences of the user functions
 // (LpHessianCalculator::CalculatePhaseHessian, Core/LpHessian.cpp:1192-2161), lambda-weighted and assembled as in
 // GetPhaseHessian (:12-599).  Per node there are NR = (NV+1)(NV+2)/2 evaluation points (base, NV single and
-// NV(NV+1)/2 double perturbations of [x.., u.., t]); thread = (role, node): every point is evaluated concurrently,
-// published in LDS, then each pair role combines F_ab - F_a - F_b + F_0 and writes its N-long block.
+// NV(NV+1)/2 double perturbations of [x.., u.., t, p..]); thread = (role, node): every point is evaluated concurrently,
+// published in LDS, then each pair role combines F_ab - F_a - F_b + F_0 and writes its N-long block.  The static parameters
+// (hessian-approximation = exact-parameters) come last in the list, so a functor without them has the roles it always had.
 
 template <class Prob>
 __global__ void rpm_dep_probe_kernel(const KParams K, const double* __restrict__ xg, int* __restrict__ dep,
@@ -34,9 +35,9 @@ template <class Prob, bool AN>
 __global__ void rpm_hess_kernel(const KParams K, const HParams Hp, const double* __restrict__ xall, const double sigma,
                                 const double* __restrict__ lam_all, double* __restrict__ hv_all,
                                 double* __restrict__ tmp_all) {
-  constexpr int NX = Prob::NX, NU = Prob::NU, NC = Prob::NC;
-  constexpr int NV = NX + NU + 1, NF = NX + NC + 1, NR = (NV + 1) * (NV + 2) / 2;
-  constexpr int NXs = NX > 0 ? NX : 1, NUs = NU > 0 ? NU : 1, NCs = NC > 0 ? NC : 1;
+  constexpr int NX = Prob::NX, NU = Prob::NU, NC = Prob::NC, NQ = prob_nq<Prob>::value;
+  constexpr int NV = NX + NU + 1 + NQ, NF = NX + NC + 1, NR = (NV + 1) * (NV + 2) / 2;
+  constexpr int NXs = NX > 0 ? NX : 1, NUs = NU > 0 ? NU : 1, NCs = NC > 0 ? NC : 1, NQs = NQ > 0 ? NQ : 1;
   extern __shared__ double lds[];   // F values: [(role*NF + o)*TH + node]
   const int TH = Hp.th;
   const int tid = threadIdx.x;
@@ -89,8 +90,22 @@ __global__ void rpm_hess_kernel(const KParams K, const HParams Hp, const double*
     if (a == NX + NU) { ha = ht; tk += ht; }
     if (b == NX + NU) { hb = ht; tk += ht; }
   }
+  // static parameters: a private copy that carries the role's perturbation; without them the functor reads x as before
+  double ps[NQs];
+  const double* pq = x + ph.x_t0 + 2;
+  if constexpr (NQ > 0) {
+#pragma unroll
+    for (int j = 0; j < NQ; ++j) {
+      ps[j] = x[ph.x_t0 + 2 + j];
+      const double hj = K.tol * (1 + fabs(ps[j]));
+      if (a == NX + NU + 1 + j) { ha = hj; ps[j] += hj; }
+      if (b == NX + NU + 1 + j) { hb = hj; ps[j] += hj; }
+    }
+    pq = ps;
+  }
   double F[NF];
   if constexpr (has_stage<Prob>::value) {
+    static_assert(NQ == 0, "staged dynamics take no static parameters: stage() and dae_from2() would not see the perturbed copy");
     // functors with staged dynamics (problems.hpp): role 0 of a node leaves the sub-expressions of the unperturbed point in LDS,
     // every perturbed evaluation recomputes only what its one or two variables enter — same operations, same bits
     using Stage = typename stage_of<Prob>::type;
@@ -113,10 +128,10 @@ __global__ void rpm_hess_kernel(const KParams K, const HParams Hp, const double*
     F[NX + NC] = pf_lagrange<Prob>(ph.phase_num, tk, xs, us, x + ph.x_t0 + 2, c);
   } else {
     double cp[NCs];
-    pf_dae<Prob>(ph.phase_num, tk, xs, us, x + ph.x_t0 + 2, c, F, cp);
+    pf_dae<Prob>(ph.phase_num, tk, xs, us, pq, c, F, cp);
 #pragma unroll
     for (int j = 0; j < NC; ++j) F[NX + j] = cp[j];
-    F[NX + NC] = pf_lagrange<Prob>(ph.phase_num, tk, xs, us, x + ph.x_t0 + 2, c);
+    F[NX + NC] = pf_lagrange<Prob>(ph.phase_num, tk, xs, us, pq, c);
   }
   if (act) {
 #pragma unroll
@@ -147,6 +162,17 @@ __global__ void rpm_hess_kernel(const KParams K, const HParams Hp, const double*
   if (kind == 1) {
     hv[dst0 + k] = XI;
     return;
+  }
+  if constexpr (NQ > 0) {
+    if (kind == 5) {   // (p, p'): per-node terms of the scalar, reduced by rpm_hess_tt_kernel
+      tmp[dst0 * N + k] = XI;
+      return;
+    }
+    if (kind == 4) {   // (p, t): the variable of the first-derivative piece is a, the parameter; b is the time
+      b = a;
+      hb = ha;
+      Fb = Fa;
+    }
   }
   // ---- t0/tf rows: first-derivative pieces of variable b (:159-218).  Finite differences reuse the single
   //      perturbations already in LDS ((F_b - F_0)/h_b is exactly LpFDderive's formula) ----
@@ -180,6 +206,9 @@ __global__ void rpm_hess_kernel(const KParams K, const HParams Hp, const double*
   if (kind == 2) {
     hv[dst0 + k] = 0.5 * D1 + ta * XI;
     hv[dst1 + k] = -0.5 * D1 + tb * XI;
+  } else if (NQ > 0 && kind == 4) {   // per-node terms of (p, t0) and (p, tf)
+    tmp[dst0 * N + k] = 0.5 * D1 + ta * XI;
+    tmp[dst1 * N + k] = -0.5 * D1 + tb * XI;
   } else {   // (t,t): per-node terms of the three dot products, reduced by rpm_hess_tt_kernel
     tmp[k] = ta * (D1 + ta * XI);
     tmp[N + k] = tb * (-D1 + tb * XI);
@@ -188,7 +217,8 @@ __global__ void rpm_hess_kernel(const KParams K, const HParams Hp, const double*
 }
 
 // t0t0, tftf, tft0 scalars: fixed-shape tree sums of the per-node terms (deterministic; the reference sums in
-// Armadillo's dot order, so these three entries agree to rounding, not bit for bit)
+// Armadillo's dot order, so these three entries agree to rounding, not bit for bit).  The parameter scalars (p, t0), (p, tf),
+// (p, p') of a phase follow, one row after the other through the same strided loop and the same tree.
 __global__ void rpm_hess_tt_kernel(const KParams K, const HParams Hp, const double* __restrict__ tmp_all,
                                    double* __restrict__ hv_all) {
   __shared__ double red[3][256];
@@ -218,6 +248,18 @@ __global__ void rpm_hess_tt_kernel(const KParams K, const HParams Hp, const doub
     hv[hp.tt_dst[2]] = red[1][0];   // tftf
     hv[hp.tt_dst[1]] = red[2][0];   // tft0
   }
+  for (int r = 0; r < hp.n_red; ++r) {
+    __syncthreads();
+    double sr = 0.0;
+    for (int k = tid; k < N; k += 256) sr += tmp[(3 + r) * N + k];
+    red[0][tid] = sr;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+      if (tid < s) red[0][tid] += red[0][tid + s];
+      __syncthreads();
+    }
+    if (tid == 0) hv_all[size_t(inst) * Hp.nnz_h + hp.v0 + Hp.red_dst[hp.red0 + r]] = red[0][0];
+  }
 }
 
 // E-part (events + Mayer, LpHessian.cpp:1553-1983, assembled :290-330) and linkage entries (:1020-1190, :2163-2367):
@@ -225,7 +267,7 @@ __global__ void rpm_hess_tt_kernel(const KParams K, const HParams Hp, const doub
 template <class Prob>
 __global__ void rpm_hess_end_kernel(const KParams K, const HParams Hp, const double* __restrict__ xall, const double sigma,
                                     const double* __restrict__ lam_all, double* __restrict__ hv_all) {
-  constexpr int NX = Prob::NX;
+  constexpr int NX = Prob::NX, NQ = prob_nq<Prob>::value, NQs = NQ > 0 ? NQ : 1;
   constexpr int NE = Prob::NE_MAX > 0 ? Prob::NE_MAX : 1, NL = Prob::NLINK_MAX > 0 ? Prob::NLINK_MAX : 1;
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
   const int inst = blockIdx.y;
@@ -244,6 +286,9 @@ __global__ void rpm_hess_end_kernel(const KParams K, const HParams Hp, const dou
     const double t0 = x[ph.x_t0], tf = x[ph.x_t0 + 1];
     auto pert = [&](int v) -> double {
       double base = v < NX ? x0[v < NX ? v : 0] : (v < 2 * NX ? xf[v - NX] : (v == 2 * NX ? t0 : tf));
+      if constexpr (NQ > 0) {
+        if (v >= 2 * NX + 2) base = x[ph.x_t0 + 2 + (v - 2 * NX - 2)];
+      }
       return K.tol * (1 + fabs(base));
     };
     const double pa = pert(en.a), pb = pert(en.b), den = pert(en.da) * pert(en.db);
@@ -251,6 +296,12 @@ __global__ void rpm_hess_end_kernel(const KParams K, const HParams Hp, const dou
     for (int q = 0; q < 4; ++q) {   // 0: base, 1: a, 2: b, 3: a then b
       double y0[NX], yf[NX], s0 = t0, sf = tf;
       for (int j = 0; j < NX; ++j) { y0[j] = x0[j]; yf[j] = xf[j]; }
+      double yp[NQs];
+      const double* pq = x + ph.x_t0 + 2;
+      if constexpr (NQ > 0) {
+        for (int j = 0; j < NQ; ++j) yp[j] = x[ph.x_t0 + 2 + j];
+        pq = yp;
+      }
       for (int w = 0; w < 2; ++w) {
         const bool on = (w == 0) ? (q == 1 || q == 3) : (q == 2 || q == 3);
         if (!on) continue;
@@ -262,10 +313,14 @@ __global__ void rpm_hess_end_kernel(const KParams K, const HParams Hp, const dou
         }
         if (v == 2 * NX) s0 += hh;
         if (v == 2 * NX + 1) sf += hh;
+        if constexpr (NQ > 0) {
+          for (int j = 0; j < NQ; ++j)
+            if (v == 2 * NX + 2 + j) yp[j] += hh;
+        }
       }
       for (int i = 0; i < NE; ++i) ev[q][i] = 0.0;
-      if (ph.ne > 0) pf_event<Prob>(ph.phase_num, s0, y0, sf, yf, x + ph.x_t0 + 2, c, ev[q]);
-      my[q] = pf_mayer<Prob>(ph.phase_num, s0, y0, sf, yf, x + ph.x_t0 + 2, c);
+      if (ph.ne > 0) pf_event<Prob>(ph.phase_num, s0, y0, sf, yf, pq, c, ev[q]);
+      my[q] = pf_mayer<Prob>(ph.phase_num, s0, y0, sf, yf, pq, c);
     }
     const double hM = (my[3] - my[1] - my[2] + my[0]) / den;
     double v1 = 0.0, v2 = 0.0;   // accu(hEvents % event_lambda): two interleaved accumulators
@@ -282,20 +337,27 @@ __global__ void rpm_hess_end_kernel(const KParams K, const HParams Hp, const dou
     const LinkDev lk = K.links[le.pair];
     const PhaseDev pl = K.phases[lk.left];
     const PhaseDev pr = K.phases[lk.right];
-    double w0[2 * NX];
+    double w0[2 * NX + 2 * NQ];   // [xfL.., x0R.., pL.., pR..]
     for (int j = 0; j < NX; ++j) {
       w0[j] = x[pl.x_state0 + j * (pl.N + 1) + pl.N];
       w0[NX + j] = x[pr.x_state0 + j * (pr.N + 1)];
     }
+    for (int j = 0; j < NQ; ++j) {
+      w0[2 * NX + j] = x[pl.x_t0 + 2 + j];
+      w0[2 * NX + NQ + j] = x[pr.x_t0 + 2 + j];
+    }
     const double pa = K.tol * (1 + fabs(w0[le.a])), pb = K.tol * (1 + fabs(w0[le.b]));
     double lo[4][NL];
     for (int q = 0; q < 4; ++q) {
-      double w[2 * NX];
-      for (int j = 0; j < 2 * NX; ++j) w[j] = w0[j];
+      double w[2 * NX + 2 * NQ];
+      for (int j = 0; j < 2 * NX + 2 * NQ; ++j) w[j] = w0[j];
       if (q == 1 || q == 3) w[le.a] += pa;
       if (q == 2 || q == 3) w[le.b] += pb;
       for (int i = 0; i < NL; ++i) lo[q][i] = 0.0;
-      pf_link<Prob>(lk.left + 1, lk.right + 1, w, w + NX, x + K.phases[lk.left].x_t0 + 2, x + K.phases[lk.right].x_t0 + 2, c, lk.nlink, lo[q]);
+      if constexpr (NQ > 0)
+        pf_link<Prob>(lk.left + 1, lk.right + 1, w, w + NX, w + 2 * NX, w + 2 * NX + NQ, c, lk.nlink, lo[q]);
+      else
+        pf_link<Prob>(lk.left + 1, lk.right + 1, w, w + NX, x + K.phases[lk.left].x_t0 + 2, x + K.phases[lk.right].x_t0 + 2, c, lk.nlink, lo[q]);
     }
     // link multipliers: the reference reads the FIRST pair's rows for every pair (link_indices are built
     // without advancing the offset, Core/LpBoundsChecker.cpp:240-244) — kept
@@ -350,7 +412,7 @@ int ensure_hessian(Engine& e) {
     build_hessian_tables(e);
   }
   // tiles of the Hessian kernel: TH nodes x NR roles per workgroup
-  const int NV = nv + 1, NR = (NV + 1) * (NV + 2) / 2, NF = nout + 1;
+  const int NV = nv + 1 + pd.nq, NR = (NV + 1) * (NV + 2) / 2, NF = nout + 1;
   int TH = 64;
   while (TH > 1 && TH * NR > 1024) TH /= 2;
   if (TH * NR > 1024) {
@@ -369,6 +431,7 @@ int ensure_hessian(Engine& e) {
   HIP_TRY(e, upload(&d.d_hends, e.hess_ends));
   HIP_TRY(e, upload(&d.d_hlinks, e.hess_links));
   HIP_TRY(e, upload(&d.d_htiles, tiles));
+  HIP_TRY(e, upload(&d.d_hred, e.hess_red_dst));
   const size_t B = size_t(e.n_instances);
   HIP_TRY(e, hipMalloc(reinterpret_cast<void**>(&d.d_htmp), B * (e.hess_tmp_len ? e.hess_tmp_len : 1) * sizeof(double)));
   HIP_TRY(e, hipMalloc(reinterpret_cast<void**>(&d.d_hess), B * (e.nnz_h ? e.nnz_h : 1) * sizeof(double)));
@@ -377,6 +440,7 @@ int ensure_hessian(Engine& e) {
   d.hp.ends = d.d_hends;
   d.hp.links = d.d_hlinks;
   d.hp.tiles = d.d_htiles;
+  d.hp.red_dst = d.d_hred;
   d.hp.n_tiles = int(tiles.size() / 3);
   d.hp.th = TH;
   d.hp.n_ends = int(e.hess_ends.size());

@@ -14,6 +14,11 @@ using namespace rpm;
 
 namespace rpm {
 
+// Option "sens_refine": the factorisation starts at this delta_w instead of 0 — the pivot-free LDL^T is stable on a quasi-definite
+// matrix, and W + Sigma of a plan without curvature in some unknowns is only semi-definite to working precision —, and the
+// refinement's residual is taken against the matrix WITHOUT it, so the rounds remove what it adds.  sqrt(2^-52) rounded down.
+constexpr double SENS_REFINE_DELTA_W = 1e-8;
+
 struct SensPars {   // the parameter list, by value
   int n_par;
   int idx[IPM_SENS_MAX_PAR];
@@ -53,6 +58,50 @@ __global__ __launch_bounds__(256) void ipm_sens_unpack_kernel(IpmDev D, SensPars
     const int r = i - D.n;
     dlam[col * D.m + r] = left_out ? nan : w[D.pos[D.nv + r]];
   }
+}
+
+// Iterative refinement of the columns (option "sens_refine"): res = rhs0 - K sol, row by row from the SOURCES of the matrix —
+// the Hessian and Jacobian triplets, -1 at the slacks, the diagonal terms as ipm_assemble_kernel forms them — in the fixed order of
+// the row table, one thread per row: deterministic, and independent of what the factorisation left in the storage.
+// rows: ptr (n_rows + 1), position of every row (n_rows), then per entry its code (kind << 28 | index: 0 Hessian triplet, 1 Jacobian
+// triplet, 2 the slack's -1, 3 diagonal of variable or slack i, 4 diagonal of constraint r) and the position of its column.
+__global__ __launch_bounds__(256) void ipm_sens_residual_kernel(IpmDev D, const int* __restrict__ rows, int n_rows, int n_ent,
+                                                               const double* __restrict__ rhs0, const double* __restrict__ sol,
+                                                               double* __restrict__ res, double dw_floor) {
+  const int bi = blockIdx.y, k = blockIdx.z, u = blockIdx.x * blockDim.x + threadIdx.x;
+  if (u >= n_rows) return;
+  const IpmInst& S = D.inst[bi];
+  const int *ptr = rows, *rpos = rows + n_rows + 1, *code = rpos + n_rows, *col = code + n_ent;
+  const size_t off = (size_t(k) * D.B + bi) * D.Nt;
+  const double *hess = D.hess + size_t(bi) * D.nnz_h, *jac = D.jac + size_t(bi) * D.sv;
+  const double *v = D.v + size_t(bi) * D.nv, *vl = D.vl + size_t(bi) * D.nv, *vu = D.vu + size_t(bi) * D.nv;
+  const double *zL = D.zL + size_t(bi) * D.nv, *zU = D.zU + size_t(bi) * D.nv;
+  double acc = rhs0[off + rpos[u]];
+  for (int j = ptr[u]; j < ptr[u + 1]; ++j) {
+    const int kind = code[j] >> 28, i = code[j] & 0x0fffffff;
+    double a;
+    if (kind == 0) a = hess[i];
+    else if (kind == 1) a = jac[i];
+    else if (kind == 2) a = -1.0;
+    else if (kind == 4) a = -D.o.delta_c;
+    else {
+      const double l = vl[i], up = vu[i];
+      a = 1.0;
+      if (l != up) {
+        a = S.delta_w > dw_floor ? S.delta_w : 0.0;   // (the floor the refined call factors with is not part of the matrix)
+        const double cap = D.o.sigma_cap > 0 ? D.o.sigma_cap : 1e300;
+        if (l > -IPM_INF) a += fmin(zL[i] / (v[i] - l), cap);
+        if (up < IPM_INF) a += fmin(zU[i] / (up - v[i]), cap);
+      }
+    }
+    acc -= a * sol[off + col[j]];
+  }
+  res[off + rpos[u]] = acc;
+}
+
+__global__ __launch_bounds__(256) void ipm_sens_correct_kernel(long long len, const double* __restrict__ d, double* __restrict__ sol) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < len) sol[i] += d[i];
 }
 
 // The predictor: out[b] = in[b], then for k ascending out[b] = out[b] + S[b][k] * delta[b][k] (product, then sum: the build keeps
@@ -180,6 +229,71 @@ int sens_evaluate_and_gather(rpm_ipm* h, const IpmLoop& L, int n_par) {
   return launch_check(h, "ipm_sens_rhs_kernel");
 }
 
+// rounds of refinement of a call: the option, or automatically 2 where the engine carries the exact Hessian of a problem with
+// static parameters (hessian-approximation = exact-parameters, nq > 0) — the plans whose sensitivities to a fixed parameter the
+// plain columns lose — and none elsewhere, where every bit stays what it was
+int sens_rounds(const rpm_ipm* h) {
+  if (h->sens.refine >= 0) return h->sens.refine;
+  const Engine& e = h->eng->e;
+  if (!e.hess_parameters) return 0;
+  for (const PhaseHost& p : e.ph)
+    if (p.nq > 0) return 2;
+  return 0;
+}
+
+// the row table of ipm_sens_residual_kernel (once per solver) and the two further work spaces
+int sens_refine_room(rpm_ipm* h, int n_par) {
+  rpm_ipm::Sens& s = h->sens;
+  const IpmPlan& p = h->plan;
+  const Engine& e = h->eng->e;
+  int rc;
+  if (!s.rows) {
+    const int nv = h->D.nv, n = p.n, m = p.m, NU = nv + m;
+    std::vector<std::vector<std::pair<int, int>>> R;
+    R.resize(size_t(NU));
+    for (int k = 0; k < e.nnz_h; ++k)
+      if (p.hes_dst[size_t(k)] >= 0) {
+        const int i = e.hes_i[size_t(k)], j = e.hes_j[size_t(k)];
+        R[size_t(i)].emplace_back(k, p.pos[size_t(j)]);
+        if (i != j) R[size_t(j)].emplace_back(k, p.pos[size_t(i)]);
+      }
+    for (int k = 0; k < e.nnz_jac; ++k)
+      if (p.jac_dst[size_t(k)] >= 0) {
+        const int r = nv + e.jac_i[size_t(k)], c = e.jac_j[size_t(k)];
+        R[size_t(r)].emplace_back((1 << 28) | k, p.pos[size_t(c)]);
+        R[size_t(c)].emplace_back((1 << 28) | k, p.pos[size_t(r)]);
+      }
+    for (int q = 0; q < int(p.slack_row.size()); ++q) {
+      const int r = nv + p.slack_row[size_t(q)], c = n + q;
+      R[size_t(r)].emplace_back(2 << 28, p.pos[size_t(c)]);
+      R[size_t(c)].emplace_back(2 << 28, p.pos[size_t(r)]);
+    }
+    for (int i = 0; i < nv; ++i) R[size_t(i)].emplace_back((3 << 28) | i, p.pos[size_t(i)]);
+    for (int r = 0; r < m; ++r) R[size_t(nv + r)].emplace_back((4 << 28) | r, p.pos[size_t(nv + r)]);
+    std::vector<int> ptr, rpos, code, col;
+    ptr.assign(size_t(NU) + 1, 0);
+    rpos.assign(size_t(NU), 0);
+    for (int u = 0; u < NU; ++u) {
+      rpos[size_t(u)] = p.pos[size_t(u)];
+      for (const auto& en : R[size_t(u)]) { code.push_back(en.first); col.push_back(en.second); }
+      ptr[size_t(u) + 1] = int(code.size());
+    }
+    std::vector<int> flat;
+    flat.insert(flat.end(), ptr.begin(), ptr.end());
+    flat.insert(flat.end(), rpos.begin(), rpos.end());
+    flat.insert(flat.end(), code.begin(), code.end());
+    flat.insert(flat.end(), col.begin(), col.end());
+    size_t cap = 0;
+    if ((rc = sens_room(h, &s.rows, &cap, flat.size()))) return rc;
+    IPM_TRY(h, hipMemcpy(s.rows, flat.data(), flat.size() * sizeof(int), hipMemcpyHostToDevice));
+    s.n_rows = NU;
+    s.n_ent = int(code.size());
+  }
+  const size_t len = size_t(h->D.B) * size_t(n_par) * size_t(p.Nt_alloc);
+  if ((rc = sens_room(h, &s.rhs0, &s.rhs0_cap, len))) return rc;
+  return sens_room(h, &s.res, &s.res_cap, len);
+}
+
 SensPars pars_of(int n_par, const int* var_index) {
   SensPars P{};
   P.n_par = n_par;
@@ -191,6 +305,7 @@ SensPars pars_of(int n_par, const int* var_index) {
 // counters and the statistics of the last solve are what they were.
 int sens_run(rpm_ipm* h, int n_par, const int* var_index, double* d_dx, double* d_dlambda, double* delta_w, int* info, void* stream) {
   const IpmLoop L = ipm_loop(h);   // (nlp_scaling is off: sens_check)
+  const int rounds = sens_rounds(h);
   IpmDev& D = L.D;
   hipStream_t st = L.st;
   const size_t B = size_t(D.B);
@@ -204,6 +319,7 @@ int sens_run(rpm_ipm* h, int n_par, const int* var_index, double* d_dx, double* 
   for (size_t bi = 0; bi < B; ++bi) {
     live[bi].mu = saved[bi].mu;
     live[bi].refactor = 1;
+    if (rounds > 0) live[bi].delta_w = SENS_REFINE_DELTA_W;
     live[bi].status = saved[bi].status == 5 ? 5 : 0;
   }
   const IpmStats keep_stats = h->stats;
@@ -217,7 +333,24 @@ int sens_run(rpm_ipm* h, int n_par, const int* var_index, double* d_dx, double* 
     IpmDev Ds = D;   // the substitution kernels on the work space: n_par right-hand sides per instance, same factors
     Ds.rhs = h->sens.ws;
     Ds.rhs_mult = n_par;
+    const rpm_ipm::Sens& sn = h->sens;
+    const size_t len = B * size_t(n_par) * size_t(D.Nt);
+    if (rounds > 0) {
+      if ((rc = sens_refine_room(h, n_par))) return rc;
+      IPM_TRY(h, hipMemcpyAsync(sn.rhs0, sn.ws, len * sizeof(double), hipMemcpyDeviceToDevice, st));
+    }
     kkt_launch_solve(Ds, 1, st);
+    // option "sens_refine": sol += K^-1 (rhs0 - K sol) with the same factors — what a pivot-free LDL^T needs where W + Sigma is
+    // nearly singular (a bang-bang plan: no curvature in the states, inactive bounds) and the columns lose digits
+    for (int round = 0; round < rounds; ++round) {
+      IPM_TRY(h, hipMemsetAsync(sn.res, 0, len * sizeof(double), st));
+      hipLaunchKernelGGL(ipm_sens_residual_kernel, dim3(unsigned((sn.n_rows + 255) / 256), unsigned(D.B), unsigned(n_par)), dim3(256), 0, st, D,
+                         sn.rows, sn.n_rows, sn.n_ent, sn.rhs0, sn.ws, sn.res, SENS_REFINE_DELTA_W);
+      IpmDev Dr = Ds;
+      Dr.rhs = sn.res;
+      kkt_launch_solve(Dr, 1, st);
+      hipLaunchKernelGGL(ipm_sens_correct_kernel, dim3(unsigned((len + 255) / 256)), dim3(256), 0, st, (long long)len, sn.res, sn.ws);
+    }
     hipLaunchKernelGGL(ipm_sens_unpack_kernel, dim3(unsigned((D.n + D.m + 255) / 256), unsigned(D.B), unsigned(n_par)), dim3(256), 0, st, D,
                        pars_of(n_par, var_index), h->sens.fixed, h->sens.ws, d_dx, d_dlambda);
     if ((rc = launch_check(h, "sensitivity substitution"))) return rc;
@@ -238,7 +371,7 @@ int sens_run(rpm_ipm* h, int n_par, const int* var_index, double* d_dx, double* 
   for (size_t bi = 0; bi < B; ++bi) {
     const bool ok = live[bi].status == 0;
     if (delta_w) delta_w[bi] = ok ? live[bi].delta_w : std::numeric_limits<double>::quiet_NaN();
-    if (info) info[bi] = ok ? (live[bi].delta_w > 0.0 ? 1 : 0) : 2;
+    if (info) info[bi] = ok ? (live[bi].delta_w > (rounds > 0 ? SENS_REFINE_DELTA_W : 0.0) ? 1 : 0) : 2;
   }
   return RPM_OK;
 }
@@ -284,6 +417,17 @@ int rpm_ipm_initial_state_variables(rpm_ipm* h, int phase, int* var_index) {
   if (!var_index) return ipm_refuse(h, RPM_E_INVALID, who, "var_index is NULL");
   const PhaseHost& p = e.ph[size_t(phase)];
   for (int j = 0; j < p.nx; ++j) var_index[j] = p.var0 + j * (p.N + 1);
+  return RPM_OK;
+}
+
+int rpm_ipm_parameter_variables(rpm_ipm* h, int phase, int* var_index) {
+  if (!h) return RPM_E_INVALID;
+  const Engine& e = h->eng->e;
+  const std::string who = "rpm_ipm_parameter_variables";
+  if (phase < 0 || phase >= e.P) return ipm_refuse(h, RPM_E_INVALID, who, "phase " + std::to_string(phase) + " is out of range");
+  if (!var_index) return ipm_refuse(h, RPM_E_INVALID, who, "var_index is NULL");
+  const PhaseHost& p = e.ph[size_t(phase)];
+  for (int j = 0; j < p.nq; ++j) var_index[j] = p.var0 + p.nx * (p.N + 1) + p.nu * p.N + 2 + j;
   return RPM_OK;
 }
 

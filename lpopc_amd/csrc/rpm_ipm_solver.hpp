@@ -48,11 +48,19 @@ struct rpm_ipm {
     size_t ws_cap = 0, block_cap = 0, table_cap = 0;
     int n_groups = 0;
     std::vector<int> var_index;    // the list `table` was built for
+    // option "sens_refine" (rounds of iterative refinement of the columns, 0 = none): the rows of the KKT matrix by source
+    // (ptr, position, then per entry a source code and the position of its column), a copy of the right-hand sides, the residuals
+    int refine = -1;               // -1 automatic: 2 rounds on an exact-parameters engine with static parameters, else none
+    int *rows = nullptr;
+    int n_rows = 0, n_ent = 0;
+    double *rhs0 = nullptr, *res = nullptr;
+    size_t rhs0_cap = 0, res_cap = 0;
   } sens;
   ~rpm_ipm() {
     if (attached && eng && eng->e.ipm_attached > 0) eng->e.ipm_attached -= 1;
     for (void* p : allocs) (void)hipFree(p);
-    for (void* p : {static_cast<void*>(sens.ws), static_cast<void*>(sens.block), static_cast<void*>(sens.table), static_cast<void*>(sens.fixed)})
+    for (void* p : {static_cast<void*>(sens.ws), static_cast<void*>(sens.block), static_cast<void*>(sens.table), static_cast<void*>(sens.fixed),
+                    static_cast<void*>(sens.rows), static_cast<void*>(sens.rhs0), static_cast<void*>(sens.res)})
       if (p) (void)hipFree(p);
     if (h_cnt) (void)hipHostFree(h_cnt);
     for (hipEvent_t e2 : ev)

@@ -2,7 +2,9 @@
 // goes with a diagonal slot, by destination: for ipm_fill_kernel (rpm_kkt_assemble.hip) and the assembling prologue of
 // kkt_factor_dense_kernel (rpm_kkt_factor.hip).  The rule is written out in two more places, whose results must agree with these
 // bit for bit — a change to it is made in all three: ipm_assemble_kernel (rpm_kkt_assemble.hip; by source, every term), and the
-// Hessian duplicate sum of the dense kernel's prologue.  (Sharing one copy through member functions changes the code generated
+// Hessian duplicate sum of the dense kernel's prologue.  A fourth reader restates the mode-0 matrix entries (no right-hand side):
+// ipm_sens_residual_kernel (rpm_ipm_sens.hip), whose refined columns tests/test_gpu_param_solver.py holds against a dense numpy solve
+// of the matrix built from independent sources — a rule that drifts apart there moves the refined columns.  (Sharing one copy through member functions changes the code generated
 // for ipm_fill_kernel and the dense factor kernels, which are tuned as they stand.)
 #pragma once
 #include "rpm_ipm_device.hpp"

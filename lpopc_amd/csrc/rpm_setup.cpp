@@ -306,7 +306,9 @@ int setup_engine(Engine& e, const rpm_problem_desc* d) {
   e.consts.assign(d->consts, d->consts + d->n_consts);
   e.fd_tol = d->fd_tol > 0 ? d->fd_tol : 1e-6;
   e.first_derive = d->first_derive;
-  e.hessian_mode = d->hessian_approximation;
+  // exact-parameters is exact plus a flag: every `== RPM_HESSIAN_EXACT` downstream keeps working
+  e.hess_parameters = d->hessian_approximation == RPM_HESSIAN_EXACT_PARAMETERS;
+  e.hessian_mode = e.hess_parameters ? RPM_HESSIAN_EXACT : d->hessian_approximation;
   e.n_instances = d->n_instances;
   e.shard_mode = d->shard_mode;
   e.shard_rank = d->shard_rank;
@@ -327,9 +329,10 @@ int setup_engine(Engine& e, const rpm_problem_desc* d) {
     // LpFiniteDifferenceDerive.cpp:299-317), values by the mathematically correct formulas where the reference's own
     // parameter path is inconsistent (DESIGN.md section 3 lists each departure)
     if (q.nq != pd.nq) return bad(e, RPM_E_INVALID, "the number of static parameters (nq) does not match the problem functor" + tag);
-    if (q.nq > 0 && e.hessian_mode == RPM_HESSIAN_EXACT)
+    if (q.nq > 0 && e.hessian_mode == RPM_HESSIAN_EXACT && !e.hess_parameters)
       return bad(e, RPM_E_UNSUPPORTED, "hessian-approximation=exact is not built for problems with static parameters (nq > 0): the reference's "
-                                       "parameter Hessian is inconsistent (SURVEY.md App. A.6 quirks); use limited-memory" + tag);
+                                       "parameter Hessian is inconsistent (SURVEY.md App. A.6 quirks); use limited-memory" + tag +
+                                       ", or exact-parameters for the corrected parameter Hessian");
     if (q.n_intervals < 1 || !q.mesh_points || !q.nodes_per_interval)
       return bad(e, RPM_E_INVALID, "MeshRefinement need at least two  meshPoints" + tag);
     if (q.mesh_points[0] != -1 || q.mesh_points[q.n_intervals] != 1)

@@ -25,7 +25,7 @@ ABI_SYMBOLS = [
     "rpm_create", "rpm_destroy", "rpm_last_error", "rpm_device_init", "rpm_get_nlp_info",
     "rpm_get_bounds_info", "rpm_get_starting_point", "rpm_eval_f", "rpm_eval_grad_f", "rpm_eval_g",
     "rpm_eval_jac_g", "rpm_eval_pair", "rpm_eval_h", "rpm_finalize_solution", "rpm_get_solution", "rpm_eval_g_dev",
-    "rpm_eval_jac_g_dev", "rpm_eval_pair_dev", "rpm_eval_f_dev", "rpm_eval_grad_f_dev", "rpm_eval_h_dev", "rpm_debug_hess_tt", "rpm_debug_tile_slot",
+    "rpm_eval_jac_g_dev", "rpm_eval_pair_dev", "rpm_eval_f_dev", "rpm_eval_grad_f_dev", "rpm_eval_h_dev", "rpm_debug_hess_tt", "rpm_debug_hess_structure", "rpm_debug_tile_slot",
     "rpm_synchronize", "rpm_set_option", "rpm_get_option", "rpm_set_instance_constants", "rpm_get_phase_sizes", "rpm_get_phase_tables",
     "rpm_shard_segments", "rpm_shard_pack_dev", "rpm_shard_unpack_dev", "rpm_shard_slot_len", "rpm_shard_pack_all_dev", "rpm_shard_unpack_all_dev", "rpm_nlp2op_control", "rpm_final_result_save",
     "rpm_solution_error", "rpm_ph_refine_mesh", "rpm_ph_refine_from_error",
@@ -49,7 +49,7 @@ ABI_SYMBOLS = [
     "rpm_ipm_get_stats", "rpm_ipm_get_subproblems", "rpm_ipm_get_trace", "rpm_ipm_get_restorations", "rpm_ipm_get_kernel_times", "rpm_ipm_solve", "rpm_ipm_solve_dev", "rpm_ipm_get_permutation", "rpm_ipm_debug_solve", "rpm_ipm_debug_solve_dense", "rpm_ipm_debug_slot",
     "rpm_ipm_debug_lbfgs_step", "rpm_ipm_debug_lbfgs_state", "rpm_ipm_debug_lbfgs_solve", "rpm_ipm_debug_pass",
     "rpm_ipm_debug_line_search", "rpm_ipm_debug_update",
-    "rpm_ipm_initial_state_variables", "rpm_ipm_sensitivities_dev", "rpm_ipm_sensitivities", "rpm_ipm_apply_sensitivities_dev",
+    "rpm_ipm_initial_state_variables", "rpm_ipm_parameter_variables", "rpm_ipm_sensitivities_dev", "rpm_ipm_sensitivities", "rpm_ipm_apply_sensitivities_dev",
     "rpm_ipm_apply_sensitivities", "rpm_ipm_debug_sensitivity_rhs", "rpm_sweep_sensitivities",
 ]
 
@@ -108,6 +108,7 @@ def lib(path=None):
     L.rpm_eval_grad_f_dev.argtypes = [vp, vp, vp, vp]
     L.rpm_eval_h_dev.argtypes = [vp, vp, C.c_double, vp, vp, vp]
     L.rpm_debug_hess_tt.argtypes = [vp, dp, C.c_int, dp]
+    L.rpm_debug_hess_structure.argtypes = [vp, ip, C.c_int, C.c_int, ip, ip, ip]
     L.rpm_debug_tile_slot.argtypes = [C.c_int] * 5
     L.rpm_synchronize.argtypes = [vp]
     L.rpm_set_option.argtypes = [vp, C.c_char_p, C.c_int]
@@ -219,6 +220,7 @@ def lib(path=None):
     L.rpm_sweep_solve_warm.argtypes = [vp, dp, dp, dp, dp, dp, ip, ip, dp]
     L.rpm_sweep_get_bound_multipliers.argtypes = [vp, dp, dp]
     L.rpm_ipm_initial_state_variables.argtypes = [vp, C.c_int, ip]
+    L.rpm_ipm_parameter_variables.argtypes = [vp, C.c_int, ip]
     L.rpm_ipm_sensitivities_dev.argtypes = [vp, C.c_int, ip, vp, vp, dp, ip, vp]
     L.rpm_ipm_sensitivities.argtypes = [vp, C.c_int, ip, dp, dp, dp, ip]
     L.rpm_ipm_apply_sensitivities_dev.argtypes = [vp, C.c_int, ip] + [vp] * 8
@@ -324,7 +326,9 @@ class NLPEngine:
     tensors (used only as HBM handles)."""
 
     def __init__(self, problem, options=None, n_instances=1, shard_mode=0, shard_rank=0, shard_world=1,
-                 tile_nodes=0, device=None, role_loop=None):
+                 tile_nodes=0, device=None, role_loop=None, probe_hessian=True):
+        """probe_hessian=False: an exact-Hessian engine is set up on the host only — the dependency probe, which needs the
+        device, is left to the first eval_h_structure / eval_h, and nnz_h is None until then."""
         self._L = lib(getattr(problem.GetOpimalProblemFuns(), "library", None))
         self._desc, self._keep = _abi.lower(problem, options, n_instances, shard_mode, shard_rank, shard_world)
         h = C.c_void_p()
@@ -340,8 +344,8 @@ class NLPEngine:
         # copies them through its own page-locked staging buffers.  A caller that reuses long-lived `out=` arrays (as
         # Ipopt does) may set_option("pin_host", 1) — then rpm_hip.h's lifetime contract for those arrays applies.
         n, m, nj, nh, st = (C.c_int() for _ in range(5))
-        self._check(self._L.rpm_get_nlp_info(h, C.byref(n), C.byref(m), C.byref(nj), C.byref(nh), C.byref(st)))
-        self.n, self.m, self.nnz_jac, self.nnz_h, self.index_style = n.value, m.value, nj.value, nh.value, st.value
+        self._check(self._L.rpm_get_nlp_info(h, C.byref(n), C.byref(m), C.byref(nj), C.byref(nh) if probe_hessian else None, C.byref(st)))
+        self.n, self.m, self.nnz_jac, self.nnz_h, self.index_style = n.value, m.value, nj.value, nh.value if probe_hessian else None, st.value
         self.n_instances = n_instances
         self.n_phases = problem.GetPhaseNum()
         if device is not None:
@@ -455,7 +459,16 @@ class NLPEngine:
         self._check(self._L.rpm_eval_pair(self._h, self.n, _dp(x), self.m, _dp(g), self.nnz_jac, _dp(v)))
         return (g.copy() if g_out is None else g_out), (v.copy() if values_out is None else values_out)
 
+    def _probed(self):
+        """nnz_h of an engine created with probe_hessian=False: asked for (the device probe runs) on first need."""
+        if self.nnz_h is None:
+            nh = C.c_int()
+            self._check(self._L.rpm_get_nlp_info(self._h, None, None, None, C.byref(nh), None))
+            self.nnz_h = nh.value
+        return self.nnz_h
+
     def eval_h_structure(self):
+        self._probed()
         i, j = np.zeros(self.nnz_h, dtype=np.int32), np.zeros(self.nnz_h, dtype=np.int32)
         self._check(self._L.rpm_eval_h(self._h, self.n, None, 0, 1.0, self.m, None, 0, self.nnz_h, _ip(i), _ip(j), None))
         return i, j
@@ -463,7 +476,7 @@ class NLPEngine:
     def eval_h(self, x, obj_factor, lam, new_x=True, new_lambda=True):
         x = self._x(x)
         lam = np.ascontiguousarray(lam, dtype=np.float64)
-        out = np.zeros(self.nnz_h * self.n_instances)
+        out = np.zeros(self._probed() * self.n_instances)
         self._check(self._L.rpm_eval_h(self._h, self.n, _dp(x), int(new_x), float(obj_factor), self.m, _dp(lam),
                                        int(new_lambda), self.nnz_h, None, None, _dp(out)))
         return out
@@ -510,6 +523,16 @@ class NLPEngine:
     def eval_h_dev(self, d_x, obj_factor, d_lambda, d_values, stream=None):
         self._check(self._L.rpm_eval_h_dev(self._h, self._ptr(d_x), float(obj_factor), self._ptr(d_lambda),
                                            self._ptr(d_values), self._stream(stream)))
+
+    def debug_hess_structure(self, dep):
+        """rpm_debug_hess_structure: (iRow, jCol) of the exact Hessian for a given dependency pattern (per phase (nx + nc) x
+        (nx + nu) flags, column-major, concatenated), host only — no device is touched."""
+        dep = np.ascontiguousarray(dep, dtype=np.int32).ravel()
+        nnz = np.zeros(1, dtype=np.int32)
+        self._check(self._L.rpm_debug_hess_structure(self._h, _ip(dep), int(dep.size), 0, None, None, _ip(nnz)))
+        hi, hj = np.zeros(int(nnz[0]), dtype=np.int32), np.zeros(int(nnz[0]), dtype=np.int32)
+        self._check(self._L.rpm_debug_hess_structure(self._h, _ip(dep), int(dep.size), int(nnz[0]), _ip(hi), _ip(hj), _ip(nnz)))
+        return hi, hj
 
     def debug_hess_tt(self, tmp):
         """rpm_debug_hess_tt: rpm_hess_tt_kernel alone on per-node terms (n_instances, 3 * sum N) -> (n_instances, n_phases, 3)
@@ -1082,6 +1105,15 @@ class BatchedIPM:
         self._chk(self._L.rpm_ipm_initial_state_variables(self._h, int(phase), _ip(out)))
         return out
 
+    def parameter_variables(self, phase):
+        """The static parameters of `phase`: x_t0 + 2 + j, j < nq.  Fixed in the plan (parameter_min == parameter_max) they are
+        what sensitivities() differentiates with respect to."""
+        if not 0 <= int(phase) < self._e.n_phases:
+            raise RpmError(RPM_E_INVALID, "phase %d is out of range" % int(phase))
+        out = np.zeros(self._e._desc.phases[int(phase)].nq, dtype=np.int32)
+        self._chk(self._L.rpm_ipm_parameter_variables(self._h, int(phase), _ip(out)))
+        return out
+
     @staticmethod
     def _var_index(var_index):
         return None if var_index is None else np.ascontiguousarray(var_index, dtype=np.int32).ravel()
@@ -1164,7 +1196,7 @@ class BatchedIPM:
         B, n, m = self._e.n_instances, self._e.n, self._e.m
         info = self.info()
         nv = n + info["n_slacks"]
-        width = {"obj": 1, "grad": n, "g": m, "jac": self._e.nnz_jac, "c": m, "glag": nv, "hess": self._e.nnz_h if self._e._desc.hessian_approximation == 1 else 0,   # (limited-memory: none)
+        width = {"obj": 1, "grad": n, "g": m, "jac": self._e.nnz_jac, "c": m, "glag": nv, "hess": self._e.nnz_h if self._e._desc.hessian_approximation in (1, 2) else 0,   # (limited-memory: none)
                  "K": info["storage_doubles"], "rhs": info["kkt_order"], "dv": nv,
                  "dlam": m, "dzL": nv, "dzU": nv, "record": _abi.RPM_IPM_RECORD_DOUBLES}
         out = {k: np.full((B, width[k]), np.nan) for k in _abi.IPM_PASS_OUTPUTS}

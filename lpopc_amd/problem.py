@@ -270,7 +270,7 @@ class Options:
         "first-derive": ("finite-difference", "analytic"),
         "analytic-derive-check": ("yes", "no"),
         "mesh-refine-methods": ("ph", "hp-Liu"),
-        "hessian-approximation": ("limited-memory", "exact"),
+        "hessian-approximation": ("limited-memory", "exact", "exact-parameters"),   # the last: include/rpm_hip.h, RPM_HESSIAN_EXACT_PARAMETERS
         "auto-scale": ("yes", "no"),
     }
 
