@@ -608,6 +608,40 @@ int rpm_ipm_apply_sensitivities(rpm_ipm* s, int n_par, const int* var_index, con
 /* test hook (host pointers, synchronous): the evaluation and the right-hand-side gather of rpm_ipm_sensitivities only; rhs:
  * n_instances x n_par x kkt_order in unknown order (variables, slacks, multipliers).  Same refusals. */
 int rpm_ipm_debug_sensitivity_rhs(rpm_ipm* s, int n_par, const int* var_index, double* rhs);
+/* Solution sensitivities to the instances' CONSTANTS (rpm_set_instance_constants; the shared constants where it was never used):
+ * a moved set-point, a mass, a weight.  The state, the matrix, its inertia correction, "sens_refine", info, delta_w, the ordering
+ * contract of the _dev form and everything that is left undisturbed are those of rpm_ipm_sensitivities; only the right-hand side
+ * and the unpacking differ.  Column k (k < n_par, 1 <= n_par <= 32, j = const_index[k] in 0 .. nconst - 1, no duplicate) of
+ * instance b: with c the instance's constants, h = rho (1 + |c_j|), rho the solver option "sens_constant_step" (default 1e-5,
+ * refused outside (0, 0.1]) and c+ / c- = c with entry j replaced by c_j + h / c_j - h, the objective gradient, g and the Jacobian
+ * values are evaluated at the held x at c+ and at c- by the engine's own batched launchers — the bits of a one-instance engine with
+ * those constants set.  The right-hand side, in unknown order: free variable i starts with acc = grad+[i] - grad-[i], then for the
+ * Jacobian triplets t of column i inside the state-dependent block, in ascending triplet index, acc = acc + (J+[t] - J-[t]) *
+ * lambda[row(t)] — product, then sum —, and the entry is -(acc / (h + h)); constraint row r -((g+[r] - g-[r]) / (h + h)); slacks and
+ * fixed variables 0.  Results: dx (n_instances x n_par x n) = dv on the free variables, 0 on every fixed one; dlambda (n_instances x
+ * n_par x m, or NULL) = dl; an instance that is left out gets NaN blocks.  The evaluation the matrix is assembled from comes after
+ * the perturbed ones.  The perturbed evaluations read a scratch copy of the constants: the engine's own constants — the values, the
+ * pointer the kernels read and its stride — are untouched on every exit path.  Cost: 2 n_par evaluations of grad f, g and the
+ * Jacobian on top of rpm_ipm_sensitivities' call; the scratch of one constant (two Jacobians, two gradient / g blocks) is allocated
+ * on first use, kept, grows only and serves every constant in turn.  These are barrier sensitivities at finite-difference accuracy
+ * and do not see a change of the active set.
+ * Refusals, all decided on the host before anything is queued — RPM_E_INVALID with a message: a functor without constants, NULL
+ * const_index or dx, n_par outside 1 .. 32, an index out of range, a duplicate, no state to take them at; RPM_E_UNSUPPORTED:
+ * hessian-approximation = limited-memory, nlp_scaling = 1.
+ * rpm_ipm_apply_constant_sensitivities[_dev]: the predictor above with delta (n_instances x n_par) the moves of the listed
+ * constants; the same launch, the same contract (the _dev form is one launch, capturable, allocates nothing), the list checked as
+ * a list of constants.
+ * rpm_ipm_debug_constant_sensitivity_rhs (test hook, host pointers, synchronous): the perturbed evaluations and the gather only;
+ * rhs: n_instances x n_par x kkt_order in unknown order.  Same refusals. */
+int rpm_ipm_constant_sensitivities_dev(rpm_ipm* s, int n_par, const int* const_index, double* d_dx, double* d_dlambda, double* delta_w,
+                                       int* info, void* stream);
+int rpm_ipm_constant_sensitivities(rpm_ipm* s, int n_par, const int* const_index, double* dx, double* dlambda, double* delta_w, int* info);
+int rpm_ipm_apply_constant_sensitivities_dev(rpm_ipm* s, int n_par, const int* const_index, const double* d_dx, const double* d_dlambda,
+                                             const double* d_delta, const double* d_x, double* d_x_out, const double* d_lambda,
+                                             double* d_lambda_out, void* stream);
+int rpm_ipm_apply_constant_sensitivities(rpm_ipm* s, int n_par, const int* const_index, const double* dx, const double* dlambda,
+                                         const double* delta, const double* x, double* x_out, const double* lambda, double* lambda_out);
+int rpm_ipm_debug_constant_sensitivity_rhs(rpm_ipm* s, int n_par, const int* const_index, double* rhs);
 /* test hook (host pointers): exactly the launches that precede the iteration loop — warm = 0 the cold start (lambda, z_L, z_U
  * ignored), else the warm start above — then the state: v (n_instances x nv: x, then the slacks), zL, zU (n_instances x nv),
  * lambda (n_instances x m), mu and status (n_instances; status 0, or 5 after a non-finite input), all in the solver's (scaled)
@@ -825,6 +859,9 @@ int rpm_synchronize(rpm_engine* e);
  * all batched device-resident entry points and rpm_ipm_* then evaluate every instance with its own constants.  The
  * one-instance post-solve entry points keep using instance 0's. */
 int rpm_set_instance_constants(rpm_engine* e, int instance, const double* consts, int n);
+/* Every instance's constants in ONE blocking upload (a call of rpm_set_instance_constants uploads the whole array each time): what
+ * n_instances such calls leave, the one-instance entry points' copy of instance 0 included.  Same refusals. */
+int rpm_set_all_instance_constants(rpm_engine* e, const double* consts /* n_instances x n */, int n);
 int rpm_set_option(rpm_engine* e, const char* key, int value);
 int rpm_get_option(rpm_engine* e, const char* key, int* value);
 
@@ -936,6 +973,9 @@ int rpm_sweep_solve_warm(rpm_sweep* s, double* x, double* lambda, double* z_L, d
 int rpm_sweep_get_bound_multipliers(rpm_sweep* s, double* z_L, double* z_U);
 /* rpm_ipm_sensitivities of every share: dx B x n_par x n, dlambda B x n_par x m or NULL, delta_w and info B or NULL */
 int rpm_sweep_sensitivities(rpm_sweep* s, int n_par, const int* var_index, double* dx, double* dlambda, double* delta_w, int* info);
+/* rpm_ipm_constant_sensitivities of every share, laid out alike */
+int rpm_sweep_constant_sensitivities(rpm_sweep* s, int n_par, const int* const_index, double* dx, double* dlambda, double* delta_w,
+                                     int* info);
 /* rpm_shift_plan_batch / rpm_ipm_set_initial_states on every share side by side (host arrays, all B instances: dt B x n_phases,
  * state0 B x nx): what one engine holding all B instances computes, bit for bit */
 int rpm_sweep_shift_plan(rpm_sweep* s, const double* dt, const double* x, double* x_out, const double* lambda, double* lambda_out,

@@ -742,6 +742,19 @@ int rpm_set_instance_constants(rpm_engine* h, int instance, const double* consts
   return rpm::dev_update_instance_constants(e);
   RPM_GUARD_END(h->e)
 }
+// every instance's constants (n_instances x n) in one upload: what n_instances calls of rpm_set_instance_constants leave
+int rpm_set_all_instance_constants(rpm_engine* h, const double* consts, int n) {
+  if (!h || !consts) return RPM_E_INVALID;
+  RPM_GUARD_BEGIN
+  Engine& e = h->e;
+  if (n != int(e.consts.size())) return fail(e, RPM_E_INVALID, ("rpm_set_all_instance_constants: the problem functor takes " + std::to_string(e.consts.size()) + " constants").c_str());
+  if (e.shard_world > 1) return fail(e, RPM_E_UNSUPPORTED, "rpm_set_all_instance_constants: not with interval sharding");
+  if (n == 0) return RPM_OK;
+  e.inst_consts.assign(consts, consts + size_t(e.n_instances) * n);
+  std::copy(consts, consts + n, e.consts.begin());   // instance 0: what the one-instance (post-solve) entry points use
+  return rpm::dev_update_instance_constants(e);
+  RPM_GUARD_END(h->e)
+}
 
 // ---- options ----------------------------------------------------------------------------------
 int rpm_set_option(rpm_engine* h, const char* key, int value) {

@@ -189,4 +189,19 @@ struct IpmSensTable {
 int ipm_sens_table(const IpmPlan& p, int nnz_h, const int* hes_i, const int* hes_j, int n_par, const int* var_index, IpmSensTable* t,
                    std::string* why);
 
+// Solution sensitivities to the instances' constants (rpm_ipm_constant_sensitivities, rpm_ipm_sens.hip): the right-hand side of a
+// constant is minus the central difference of grad f + J' lambda on the rows of the free variables and of g on the constraint rows,
+// so its gather walks, per free variable, the Jacobian triplets of that variable's column.  The column table: entry u < n_free is
+// free variable var[u] at KKT position var_pos[u] with the triplets ent[ptr[u] .. ptr[u + 1]) — those of its column inside the
+// state-dependent block [NL] (triplet index < nnz_nl; the linear and the constant block do not depend on the constants), in
+// ascending triplet index — and their rows ent_row[]; row_pos[r] is the KKT position of constraint row r.  Free variables ascend.
+struct IpmConstTable {
+  std::vector<int> var, var_pos, ptr, ent, ent_row, row_pos;
+  int n_free() const { return int(var.size()); }
+};
+IpmConstTable ipm_const_table(const IpmPlan& p, int nnz_nl);   // a pure function of its arguments
+// The list of constants of such a call: RPM_OK, or RPM_E_INVALID with *why — a functor without constants (nconst = 0), a NULL list,
+// n_par outside 1 .. IPM_SENS_MAX_PAR, an index outside [0, nconst), a duplicate.  A pure function of its arguments.
+int ipm_const_list_check(int nconst, int n_par, const int* const_index, std::string* why);
+
 }  // namespace rpm

@@ -3,6 +3,8 @@
 // reduced system (13) — assembled and factored at the state the solver holds by the launchers of an iteration — against minus
 // column var_index[k] of the matrix's off-diagonal blocks; all columns of all instances go through ONE pass of the substitution
 // kernels (IpmDev::rhs_mult).  Three kernels of its own: the right-hand-side gather, the unpack and the predictor.  DESIGN.md f-2.
+// The same for the instances' constants (rpm_ipm_constant_sensitivities): the right-hand side of a constant is minus a central
+// difference of the engine's own evaluations at perturbed constants — two more kernels, the perturbed constants and their gather.
 #include <cstdint>
 #include <limits>
 #include <vector>
@@ -40,8 +42,54 @@ __global__ __launch_bounds__(256) void ipm_sens_rhs_kernel(IpmDev D, const int* 
   ws[(size_t(par[g]) * D.B + bi) * D.Nt + dst[g]] = -acc;
 }
 
+// ---- sensitivities to the instances' constants (rpm_ipm_constant_sensitivities): the right-hand side of constant k is minus the
+// central difference, over each instance's own step h = rho (1 + |c_k|), of grad f + J' lambda (free variables) and of g (rows).
+// The perturbed constants of every instance: cp / cm (B x nconst) are the constants the kernels read (consts, `stride` doubles
+// between instances, 0: shared) with entry k replaced by c_k + h / c_k - h; hbuf[b] = h.
+__global__ __launch_bounds__(256) void ipm_sens_perturb_kernel(int nconst, const double* __restrict__ consts, int stride, int k, double rho,
+                                                              double* __restrict__ cp, double* __restrict__ cm, double* __restrict__ hbuf) {
+  const int bi = blockIdx.y, j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= nconst) return;
+  const double* c = consts + size_t(bi) * stride;
+  const double h = rho * (1.0 + fabs(c[k]));
+  const double v = c[j];
+  cp[size_t(bi) * nconst + j] = j == k ? v + h : v;
+  cm[size_t(bi) * nconst + j] = j == k ? v - h : v;
+  if (j == k) hbuf[bi] = h;
+}
+
+// One thread per entry of the column table (IpmConstTable, rpm_ipm.hpp; tab: var, var_pos (n_free each), ptr (n_free + 1), ent,
+// ent_row (n_ent each), row_pos (m)), grid y = instance.  Free variable i: acc = grad+[i] - grad-[i], then for the [NL] triplets t of
+// column i in ascending order acc = acc + (J+[t] - J-[t]) * lambda[row(t)] (product, then sum), and ws = -(acc / (h + h)); row r:
+// ws = -((g+[r] - g-[r]) / (h + h)).  Written at (k, instance, position) of the zero-filled work space, as ipm_sens_rhs_kernel does.
+__global__ __launch_bounds__(256) void ipm_sens_const_rhs_kernel(IpmDev D, const int* __restrict__ tab, int n_free, int n_ent, int k,
+                                                                const double* __restrict__ grad_p, const double* __restrict__ grad_m,
+                                                                const double* __restrict__ g_p, const double* __restrict__ g_m,
+                                                                const double* __restrict__ jac_p, const double* __restrict__ jac_m,
+                                                                const double* __restrict__ hbuf, double* __restrict__ ws) {
+  const int bi = blockIdx.y, u = blockIdx.x * blockDim.x + threadIdx.x;
+  if (u >= n_free + D.m) return;
+  const int *var = tab, *var_pos = var + n_free, *ptr = var_pos + n_free, *ent = ptr + n_free + 1, *ent_row = ent + n_ent, *row_pos = ent_row + n_ent;
+  const double h = hbuf[bi], h2 = h + h;
+  double* w = ws + (size_t(k) * D.B + bi) * D.Nt;
+  if (u < n_free) {
+    const int i = var[u];
+    const double *jp = jac_p + size_t(bi) * D.sv, *jm = jac_m + size_t(bi) * D.sv, *lam = D.lam + size_t(bi) * D.m;
+    double acc = grad_p[size_t(bi) * D.n + i] - grad_m[size_t(bi) * D.n + i];
+    for (int q = ptr[u]; q < ptr[u + 1]; ++q) {
+      const int t = ent[q];
+      acc = acc + (jp[t] - jm[t]) * lam[ent_row[q]];
+    }
+    w[var_pos[u]] = -(acc / h2);
+  } else {
+    const int r = u - n_free;
+    w[row_pos[r]] = -((g_p[size_t(bi) * D.sg + r] - g_m[size_t(bi) * D.sg + r]) / h2);
+  }
+}
+
 // KKT order -> dx (B x n_par x n) and dlambda (B x n_par x m, or NULL): free variables and rows through pos, 1 at the column's own
-// variable, 0 at every other fixed one; an instance whose record says it was left out (status != 0) gets NaN.
+// variable (a column of a constant has none: idx -1), 0 at every other fixed one; an instance whose record says it was left out
+// (status != 0) gets NaN.
 __global__ __launch_bounds__(256) void ipm_sens_unpack_kernel(IpmDev D, SensPars P, const int* __restrict__ fixed,
                                                              const double* __restrict__ ws, double* __restrict__ dx,
                                                              double* __restrict__ dlam) {
@@ -156,6 +204,8 @@ int sens_room(rpm_ipm* h, T** p, size_t* cap, size_t count) {   // grown only; w
   return RPM_OK;
 }
 
+int sens_check_solver(rpm_ipm* h, const std::string& who, bool need_state);   // what does not depend on the list
+
 // every refusal of rpm_ipm_sensitivities[_dev] / rpm_ipm_debug_sensitivity_rhs, on the host, before anything is queued; *table: the
 // source table of the list (NULL: only checked)
 int sens_check(rpm_ipm* h, const std::string& who, int n_par, const int* var_index, bool need_state, IpmSensTable* table) {
@@ -163,6 +213,15 @@ int sens_check(rpm_ipm* h, const std::string& who, int n_par, const int* var_ind
   std::string why;
   if (int rc = ipm_sens_table(h->plan, h->lbfgs ? 0 : e.nnz_h, e.hes_i.data(), e.hes_j.data(), n_par, var_index, table, &why))
     return ipm_refuse(h, rc, who, why);
+  return sens_check_solver(h, who, need_state);
+}
+// the same for a list of constants (rpm_ipm_constant_sensitivities[_dev], rpm_ipm_debug_constant_sensitivity_rhs, the predictor)
+int const_check(rpm_ipm* h, const std::string& who, int n_par, const int* const_index, bool need_state) {
+  std::string why;
+  if (int rc = ipm_const_list_check(int(h->eng->e.consts.size()), n_par, const_index, &why)) return ipm_refuse(h, rc, who, why);
+  return sens_check_solver(h, who, need_state);
+}
+int sens_check_solver(rpm_ipm* h, const std::string& who, bool need_state) {
   if (h->lbfgs) return ipm_refuse(h, RPM_E_UNSUPPORTED, who, "hessian-approximation = limited-memory: a quasi-Newton Hessian gives no sensitivities");
   if (h->D.scal_on) return ipm_refuse(h, RPM_E_UNSUPPORTED, who, "not with nlp_scaling = 1");
   if (need_state && !h->hold.holds_state())
@@ -171,15 +230,20 @@ int sens_check(rpm_ipm* h, const std::string& who, int n_par, const int* var_ind
 }
 
 // the source table of the list on the device (kept while the list stays the same), the fixed pattern, the work space
+int sens_fixed_room(rpm_ipm* h) {
+  rpm_ipm::Sens& s = h->sens;
+  const IpmPlan& p = h->plan;
+  if (s.fixed) return RPM_OK;
+  size_t cap = 0;
+  if (int rc = sens_room(h, &s.fixed, &cap, size_t(p.n))) return rc;
+  IPM_TRY(h, hipMemcpy(s.fixed, p.fixed.data(), size_t(p.n) * sizeof(int), hipMemcpyHostToDevice));
+  return RPM_OK;
+}
 int sens_upload(rpm_ipm* h, int n_par, const int* var_index, const IpmSensTable& t) {
   rpm_ipm::Sens& s = h->sens;
   const IpmPlan& p = h->plan;
   int rc;
-  if (!s.fixed) {
-    size_t cap = 0;
-    if ((rc = sens_room(h, &s.fixed, &cap, size_t(p.n)))) return rc;
-    IPM_TRY(h, hipMemcpy(s.fixed, p.fixed.data(), size_t(p.n) * sizeof(int), hipMemcpyHostToDevice));
-  }
+  if ((rc = sens_fixed_room(h))) return rc;
   const std::vector<int> list(var_index, var_index + n_par);
   if (list != s.var_index || !s.table) {
     const size_t G = size_t(t.n_groups());
@@ -211,15 +275,20 @@ int sens_enter(rpm_ipm* h, const std::string& who, int n_par, const int* var_ind
 
 // steps 1 and 3: g, the Jacobian and the exact Hessian at the state, then the n_par right-hand sides of every instance into the
 // (zeroed) work space
-int sens_evaluate_and_gather(rpm_ipm* h, const IpmLoop& L, int n_par) {
+int sens_evaluate(rpm_ipm* h, const IpmLoop& L) {   // step 1: what the matrix is assembled from
   Engine& e = L.e;
   IpmDev& D = L.D;
-  const rpm_ipm::Sens& s = h->sens;
   int rc;
   dev_forget_persistent(e);   // this evaluation writes all of D.jac, the constant block included (as the first one of a solve does)
   ipm_launch_pack_x(D, L.st);
   if ((rc = dev_eval_cons(e, D.xe, D.g, D.jac, 3 | 4 | 16, L.st))) return ipm_eng_fail(h, rc);
-  if ((rc = L.exact_hessian())) return rc;
+  return L.exact_hessian();
+}
+int sens_evaluate_and_gather(rpm_ipm* h, const IpmLoop& L, int n_par) {
+  IpmDev& D = L.D;
+  const rpm_ipm::Sens& s = h->sens;
+  int rc;
+  if ((rc = sens_evaluate(h, L))) return rc;
   IPM_TRY(h, hipMemsetAsync(s.ws, 0, size_t(D.B) * size_t(n_par) * size_t(D.Nt) * sizeof(double), L.st));
   const int G = s.n_groups;
   if (G > 0) {
@@ -227,6 +296,88 @@ int sens_evaluate_and_gather(rpm_ipm* h, const IpmLoop& L, int n_par) {
     hipLaunchKernelGGL(ipm_sens_rhs_kernel, dim3(unsigned((G + 255) / 256), unsigned(D.B)), dim3(256), 0, L.st, D, ptr, par, dst, src, G, s.ws);
   }
   return launch_check(h, "ipm_sens_rhs_kernel");
+}
+
+// ---- the constants' route: the column table of the plan on the device (once per solver), the fixed pattern, the scratch of one
+// constant (grown only) and the work space
+int const_upload(rpm_ipm* h, int n_par) {
+  rpm_ipm::Sens& s = h->sens;
+  const IpmPlan& p = h->plan;
+  const Engine& e = h->eng->e;
+  const IpmDev& D = h->D;
+  int rc;
+  if ((rc = sens_fixed_room(h))) return rc;
+  if (!s.ctable) {
+    const IpmConstTable t = ipm_const_table(p, e.nnz_nl);
+    std::vector<int> flat;   // var, var_pos (n_free each), ptr (n_free + 1), ent, ent_row, row_pos (m)
+    for (const std::vector<int>* v : {&t.var, &t.var_pos, &t.ptr, &t.ent, &t.ent_row, &t.row_pos}) flat.insert(flat.end(), v->begin(), v->end());
+    size_t cap = 0;
+    if ((rc = sens_room(h, &s.ctable, &cap, flat.size()))) return rc;
+    IPM_TRY(h, hipMemcpy(s.ctable, flat.data(), flat.size() * sizeof(int), hipMemcpyHostToDevice));
+    s.c_free = t.n_free();
+    s.c_ent = int(t.ent.size());
+  }
+  const size_t B = size_t(D.B), nconst = e.consts.size(), ev = B * (size_t(D.n) + size_t(D.sg) + 1);
+  if ((rc = sens_room(h, &s.cpm, &s.cpm_cap, B * (2 * nconst + 1)))) return rc;
+  if ((rc = sens_room(h, &s.eval_p, &s.eval_p_cap, ev)) || (rc = sens_room(h, &s.eval_m, &s.eval_m_cap, ev))) return rc;
+  if ((rc = sens_room(h, &s.jac_p, &s.jac_p_cap, B * size_t(D.sv))) || (rc = sens_room(h, &s.jac_m, &s.jac_m_cap, B * size_t(D.sv)))) return rc;
+  return sens_room(h, &s.ws, &s.ws_cap, B * size_t(n_par) * size_t(p.Nt_alloc));
+}
+
+// What the entry points of the constants' route begin with, under the caller's DeviceRestore (sens_enter for a list of constants).
+int const_enter(rpm_ipm* h, const std::string& who, int n_par, const int* const_index, const void* out_ptr, const char* out_name) {
+  if (!out_ptr) return ipm_refuse(h, RPM_E_INVALID, who, const_index ? std::string(out_name) + " is NULL" : "const_index is NULL");
+  int rc = const_check(h, who, n_par, const_index, true);
+  if (rc) return rc;
+  if ((rc = dev_bind(h->eng->e))) return ipm_eng_fail(h, rc);
+  return const_upload(h, n_par);
+}
+
+// The engine's kernels read the constants through Device::kp, which every launcher copies into its launch: pointed at a scratch
+// copy while this lives, and put back — the pointer and its stride, by copy — when it goes, on every path.  The engine's own
+// constants are never written, and no launch reads a pointer that has been replaced since it was queued.
+struct ConstantsAt {
+  KParams& kp;
+  const double* const keep;
+  const int keep_stride;
+  explicit ConstantsAt(Engine& e) : kp(e.dev->kp), keep(e.dev->kp.consts), keep_stride(e.dev->kp.consts_stride) {}
+  void point(const double* c, int stride) { kp.consts = c; kp.consts_stride = stride; }
+  ~ConstantsAt() { point(keep, keep_stride); }
+};
+
+// The n_par right-hand sides of every instance into the (zeroed) work space, constant by constant: c+ and c-, the objective
+// gradient, g and the Jacobian at each through the engine's batched launchers, then the gather.
+int const_evaluate_and_gather(rpm_ipm* h, const IpmLoop& L, int n_par, const int* const_index) {
+  Engine& e = L.e;
+  IpmDev& D = L.D;
+  const rpm_ipm::Sens& s = h->sens;
+  hipStream_t st = L.st;
+  const size_t B = size_t(D.B), n = size_t(D.n);
+  const int nconst = int(e.consts.size());
+  double *cp = s.cpm, *cm = cp + B * size_t(nconst), *hbuf = cm + B * size_t(nconst);
+  double *grad[2] = {s.eval_p, s.eval_m}, *jac[2] = {s.jac_p, s.jac_m}, *g[2], *obj[2];
+  for (int side = 0; side < 2; ++side) {
+    g[side] = grad[side] + B * n;
+    obj[side] = g[side] + B * size_t(D.sg);
+    IPM_TRY(h, hipMemsetAsync(grad[side], 0, B * n * sizeof(double), st));   // (as the engine's own gradient array starts)
+  }
+  IPM_TRY(h, hipMemsetAsync(s.ws, 0, B * size_t(n_par) * size_t(D.Nt) * sizeof(double), st));
+  ipm_launch_pack_x(D, st);
+  ConstantsAt at(e);
+  const int entries = s.c_free + D.m;
+  int rc;
+  for (int k = 0; k < n_par; ++k) {
+    hipLaunchKernelGGL(ipm_sens_perturb_kernel, dim3(unsigned((nconst + 255) / 256), unsigned(D.B)), dim3(256), 0, st, nconst, at.keep,
+                       at.keep_stride, const_index[k], s.const_step, cp, cm, hbuf);
+    for (int side = 0; side < 2; ++side) {
+      at.point(side ? cm : cp, nconst);
+      if ((rc = dev_eval_obj(e, D.xe, obj[side], grad[side], st))) return ipm_eng_fail(h, rc);
+      if ((rc = dev_eval_cons(e, D.xe, g[side], jac[side], 3 | 4, st))) return ipm_eng_fail(h, rc);
+    }
+    hipLaunchKernelGGL(ipm_sens_const_rhs_kernel, dim3(unsigned((entries + 255) / 256), unsigned(D.B)), dim3(256), 0, st, D, s.ctable, s.c_free,
+                       s.c_ent, k, grad[0], grad[1], g[0], g[1], jac[0], jac[1], hbuf, s.ws);
+  }
+  return launch_check(h, "ipm_sens_const_rhs_kernel");
 }
 
 // rounds of refinement of a call: the option, or automatically 2 where the engine carries the exact Hessian of a problem with
@@ -297,13 +448,16 @@ int sens_refine_room(rpm_ipm* h, int n_par) {
 SensPars pars_of(int n_par, const int* var_index) {
   SensPars P{};
   P.n_par = n_par;
-  for (int k = 0; k < n_par; ++k) P.idx[k] = var_index[k];
+  for (int k = 0; k < n_par; ++k) P.idx[k] = var_index ? var_index[k] : -1;   // (NULL: columns of constants, no variable their own)
   return P;
 }
 
-// The whole of rpm_ipm_sensitivities_dev after its checks.  The solver's stream is idle on return, the instance records, the
+// The whole of rpm_ipm_sensitivities_dev after its checks — and, `constants`: of rpm_ipm_constant_sensitivities_dev, `var_index`
+// then being the list of constants: the perturbed evaluations and their gather come first, the evaluation the matrix is assembled
+// from after them, and no fixed variable is a column's own.  The solver's stream is idle on return, the instance records, the
 // counters and the statistics of the last solve are what they were.
-int sens_run(rpm_ipm* h, int n_par, const int* var_index, double* d_dx, double* d_dlambda, double* delta_w, int* info, void* stream) {
+int sens_run(rpm_ipm* h, int n_par, const int* var_index, double* d_dx, double* d_dlambda, double* delta_w, int* info, void* stream,
+             bool constants = false) {
   const IpmLoop L = ipm_loop(h);   // (nlp_scaling is off: sens_check)
   const int rounds = sens_rounds(h);
   IpmDev& D = L.D;
@@ -328,7 +482,9 @@ int sens_run(rpm_ipm* h, int n_par, const int* var_index, double* d_dx, double* 
   auto body = [&]() -> int {
     int rc;
     if ((rc = ipm_upload_records(h, live))) return rc;
-    if ((rc = sens_evaluate_and_gather(h, L, n_par))) return rc;
+    if (constants) {
+      if ((rc = const_evaluate_and_gather(h, L, n_par, var_index)) || (rc = sens_evaluate(h, L))) return rc;
+    } else if ((rc = sens_evaluate_and_gather(h, L, n_par))) return rc;
     if ((rc = L.factor_with_inertia_correction())) return rc;
     IpmDev Ds = D;   // the substitution kernels on the work space: n_par right-hand sides per instance, same factors
     Ds.rhs = h->sens.ws;
@@ -352,7 +508,7 @@ int sens_run(rpm_ipm* h, int n_par, const int* var_index, double* d_dx, double* 
       hipLaunchKernelGGL(ipm_sens_correct_kernel, dim3(unsigned((len + 255) / 256)), dim3(256), 0, st, (long long)len, sn.res, sn.ws);
     }
     hipLaunchKernelGGL(ipm_sens_unpack_kernel, dim3(unsigned((D.n + D.m + 255) / 256), unsigned(D.B), unsigned(n_par)), dim3(256), 0, st, D,
-                       pars_of(n_par, var_index), h->sens.fixed, h->sens.ws, d_dx, d_dlambda);
+                       pars_of(n_par, constants ? nullptr : var_index), h->sens.fixed, h->sens.ws, d_dx, d_dlambda);
     if ((rc = launch_check(h, "sensitivity substitution"))) return rc;
     IPM_TRY(h, hipMemcpyAsync(live.data(), D.inst, B * sizeof(IpmInst), hipMemcpyDeviceToHost, st));
     return RPM_OK;
@@ -384,8 +540,8 @@ struct ApplyArrays {
   bool with_lambda() const { return dlambda && lambda && lambda_out; }
 };
 
-int apply_check(rpm_ipm* h, const std::string& who, int n_par, const int* var_index, const ApplyArrays& a) {
-  if (int rc = sens_check(h, who, n_par, var_index, false, nullptr)) return rc;
+int apply_check(rpm_ipm* h, const std::string& who, int n_par, const int* var_index, const ApplyArrays& a, bool constants = false) {
+  if (int rc = constants ? const_check(h, who, n_par, var_index, false) : sens_check(h, who, n_par, var_index, false, nullptr)) return rc;
   if (!a.dx || !a.delta || !a.x || !a.x_out) return ipm_refuse(h, RPM_E_INVALID, who, "dx, delta, x or x_out is NULL");
   const size_t B = size_t(h->D.B), d8 = sizeof(double), P = size_t(n_par), n = size_t(h->plan.n), m = size_t(h->plan.m);
   const bool lam = a.with_lambda();
@@ -404,6 +560,8 @@ int apply_launch(rpm_ipm* h, int n_par, const ApplyArrays& a, hipStream_t stream
                      a.dx, a.dlambda, a.delta, a.x, a.x_out, a.lambda, a.lambda_out);
   return launch_check(h, "ipm_sens_apply_kernel");
 }
+
+int apply_host_form(rpm_ipm* h, int n_par, const ApplyArrays& a);   // (below the entry points)
 
 }  // namespace
 
@@ -475,8 +633,67 @@ int rpm_ipm_apply_sensitivities(rpm_ipm* h, int n_par, const int* var_index, con
                                 const double* x, double* x_out, const double* lambda, double* lambda_out) {
   if (!h) return RPM_E_INVALID;
   const ApplyArrays a{dx, dlambda, delta, x, x_out, lambda, lambda_out};
-  int rc = apply_check(h, "rpm_ipm_apply_sensitivities", n_par, var_index, a);
+  if (int rc = apply_check(h, "rpm_ipm_apply_sensitivities", n_par, var_index, a)) return rc;
+  return apply_host_form(h, n_par, a);
+}
+
+int rpm_ipm_constant_sensitivities_dev(rpm_ipm* h, int n_par, const int* const_index, double* d_dx, double* d_dlambda, double* delta_w,
+                                       int* info, void* stream) {
+  if (!h) return RPM_E_INVALID;
+  DeviceRestore restore;
+  if (int rc = const_enter(h, "rpm_ipm_constant_sensitivities", n_par, const_index, d_dx, "dx")) return rc;
+  return sens_run(h, n_par, const_index, d_dx, d_dlambda, delta_w, info, stream, true);
+}
+
+int rpm_ipm_constant_sensitivities(rpm_ipm* h, int n_par, const int* const_index, double* dx, double* dlambda, double* delta_w, int* info) {
+  if (!h) return RPM_E_INVALID;
+  DeviceRestore restore;
+  int rc = const_enter(h, "rpm_ipm_constant_sensitivities", n_par, const_index, dx, "dx");
   if (rc) return rc;
+  const size_t B = size_t(h->D.B), Pn = size_t(n_par) * h->plan.n, Pm = size_t(n_par) * h->plan.m;
+  if ((rc = sens_room(h, &h->sens.block, &h->sens.block_cap, B * (Pn + Pm)))) return rc;
+  double *d_dx = h->sens.block, *d_dl = dlambda ? d_dx + B * Pn : nullptr;
+  if ((rc = sens_run(h, n_par, const_index, d_dx, d_dl, delta_w, info, dev_stream(h->eng->e), true))) return rc;
+  IPM_TRY(h, hipMemcpy(dx, d_dx, B * Pn * sizeof(double), hipMemcpyDeviceToHost));
+  if (dlambda && Pm) IPM_TRY(h, hipMemcpy(dlambda, d_dl, B * Pm * sizeof(double), hipMemcpyDeviceToHost));
+  return RPM_OK;
+}
+
+int rpm_ipm_debug_constant_sensitivity_rhs(rpm_ipm* h, int n_par, const int* const_index, double* rhs) {
+  if (!h) return RPM_E_INVALID;
+  DeviceRestore restore;
+  int rc = const_enter(h, "rpm_ipm_debug_constant_sensitivity_rhs", n_par, const_index, rhs, "rhs");
+  if (rc) return rc;
+  if ((rc = const_evaluate_and_gather(h, ipm_loop(h), n_par, const_index))) return rc;
+  return ipm_download_unknown_order(h, h->sens.ws, size_t(n_par), rhs);
+}
+
+int rpm_ipm_apply_constant_sensitivities_dev(rpm_ipm* h, int n_par, const int* const_index, const double* d_dx, const double* d_dlambda,
+                                             const double* d_delta, const double* d_x, double* d_x_out, const double* d_lambda,
+                                             double* d_lambda_out, void* stream) {
+  if (!h) return RPM_E_INVALID;
+  const ApplyArrays a{d_dx, d_dlambda, d_delta, d_x, d_x_out, d_lambda, d_lambda_out};
+  if (int rc = apply_check(h, "rpm_ipm_apply_constant_sensitivities_dev", n_par, const_index, a, true)) return rc;
+  return apply_launch(h, n_par, a, static_cast<hipStream_t>(stream));
+}
+
+int rpm_ipm_apply_constant_sensitivities(rpm_ipm* h, int n_par, const int* const_index, const double* dx, const double* dlambda,
+                                         const double* delta, const double* x, double* x_out, const double* lambda, double* lambda_out) {
+  if (!h) return RPM_E_INVALID;
+  const ApplyArrays a{dx, dlambda, delta, x, x_out, lambda, lambda_out};
+  if (int rc = apply_check(h, "rpm_ipm_apply_constant_sensitivities", n_par, const_index, a, true)) return rc;
+  return apply_host_form(h, n_par, a);
+}
+
+}  // extern "C"
+
+namespace {
+
+// the host-pointer form of the predictor after its checks: arrays up, one launch, results down
+int apply_host_form(rpm_ipm* h, int n_par, const ApplyArrays& a) {
+  const double *dx = a.dx, *dlambda = a.dlambda, *delta = a.delta, *x = a.x, *lambda = a.lambda;
+  double *x_out = a.x_out, *lambda_out = a.lambda_out;
+  int rc;
   DeviceRestore restore;
   Engine& e = h->eng->e;
   if ((rc = dev_bind(e))) return ipm_eng_fail(h, rc);
@@ -505,4 +722,4 @@ int rpm_ipm_apply_sensitivities(rpm_ipm* h, int n_par, const int* var_index, con
   return RPM_OK;
 }
 
-}  // extern "C"
+}  // namespace

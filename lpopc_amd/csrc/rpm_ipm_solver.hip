@@ -266,6 +266,7 @@ int rpm_ipm_set_option(rpm_ipm* h, const char* key, double value) {
   else if (k == "bound_relax_factor") { if (!(value >= 0.0)) return ipm_refuse(h, RPM_E_INVALID, "", "bound_relax_factor must be >= 0"); o.bound_relax = value; }
   else if (k == "max_soc") o.max_soc = std::max(0, int(value));
   else if (k == "sens_refine") { if (!(value >= -1.0 && value <= 8.0)) return ipm_refuse(h, RPM_E_INVALID, "", "sens_refine: 0 .. 8 rounds, or -1 (automatic)"); h->sens.refine = int(value); }
+  else if (k == "sens_constant_step") { if (!(value > 0.0 && value <= 0.1)) return ipm_refuse(h, RPM_E_INVALID, "", "sens_constant_step: a relative step in (0, 0.1]"); h->sens.const_step = value; }
   else if (k == "sigma_cap") o.sigma_cap = value;      // experiment
   else if (k == "init_ls_multipliers") o.init_ls_mult = value != 0.0;
   else if (k == "nlp_scaling") { o.nlp_scaling = value != 0.0; h->D.scal_on = o.nlp_scaling; }

@@ -55,12 +55,23 @@ struct rpm_ipm {
     int n_rows = 0, n_ent = 0;
     double *rhs0 = nullptr, *res = nullptr;
     size_t rhs0_cap = 0, res_cap = 0;
+    // sensitivities to the instances' constants: option "sens_constant_step" (rho of h = rho (1 + |c_k|)), the column table of the
+    // plan (IpmConstTable, flat, once per solver), and the scratch of one constant, which serves every constant of a call in
+    // turn: the perturbed constants c+ | c- (B x nconst each) and the steps h (B), grad f | g at c+ and at c- (B x (n + sg)
+    // each, with a B-long tail the objective values land in), the Jacobian at c+ and at c- (B x sv each)
+    double const_step = 1e-5;
+    int *ctable = nullptr;
+    int c_free = 0, c_ent = 0;
+    double *cpm = nullptr, *eval_p = nullptr, *eval_m = nullptr, *jac_p = nullptr, *jac_m = nullptr;
+    size_t cpm_cap = 0, eval_p_cap = 0, eval_m_cap = 0, jac_p_cap = 0, jac_m_cap = 0;
   } sens;
   ~rpm_ipm() {
     if (attached && eng && eng->e.ipm_attached > 0) eng->e.ipm_attached -= 1;
     for (void* p : allocs) (void)hipFree(p);
     for (void* p : {static_cast<void*>(sens.ws), static_cast<void*>(sens.block), static_cast<void*>(sens.table), static_cast<void*>(sens.fixed),
-                    static_cast<void*>(sens.rows), static_cast<void*>(sens.rhs0), static_cast<void*>(sens.res)})
+                    static_cast<void*>(sens.rows), static_cast<void*>(sens.rhs0), static_cast<void*>(sens.res),
+                    static_cast<void*>(sens.ctable), static_cast<void*>(sens.cpm), static_cast<void*>(sens.eval_p),
+                    static_cast<void*>(sens.eval_m), static_cast<void*>(sens.jac_p), static_cast<void*>(sens.jac_m)})
       if (p) (void)hipFree(p);
     if (h_cnt) (void)hipHostFree(h_cnt);
     for (hipEvent_t e2 : ev)

@@ -1,7 +1,8 @@
 // rpm_ipm_tables.cpp — the index tables rpm_ipm_create uploads beside the plan (host side of row f-2, see rpm_ipm.hpp): the
 // factorisation's sub-problems, the long Jacobian columns, the ascending list of every structural slot (one-pass fill) and the
 // per-interval-block tables of the fill fused into kkt_factor_dense_kernel; and the source table of the sensitivity right-hand sides
-// (rpm_ipm_sens.hip), with the check of its parameter list.  Pure functions of the plan: no engine, no device.
+// (rpm_ipm_sens.hip), with the check of its parameter list, and the column table of the sensitivities to the constants, with the
+// check of theirs.  Pure functions of the plan: no engine, no device.
 #include <algorithm>
 #include <unordered_map>
 
@@ -162,6 +163,40 @@ int ipm_sens_table(const IpmPlan& p, int nnz_h, const int* hes_i, const int* hes
   }
   out.ptr.push_back(int(ents.size()));
   *t = std::move(out);
+  return RPM_OK;
+}
+
+IpmConstTable ipm_const_table(const IpmPlan& p, int nnz_nl) {
+  IpmConstTable t;
+  t.ptr.push_back(0);
+  for (int i = 0; i < p.n; ++i) {
+    if (p.fixed[size_t(i)]) continue;
+    t.var.push_back(i);
+    t.var_pos.push_back(p.pos[size_t(i)]);
+    for (int q = p.jt_ptr[size_t(i)]; q < p.jt_ptr[size_t(i) + 1]; ++q)   // (jt_*: the entries of a column in triplet order)
+      if (p.jt_ent[size_t(q)] < nnz_nl) {
+        t.ent.push_back(p.jt_ent[size_t(q)]);
+        t.ent_row.push_back(p.jt_row[size_t(q)]);
+      }
+    t.ptr.push_back(int(t.ent.size()));
+  }
+  for (int r = 0; r < p.m; ++r) t.row_pos.push_back(p.pos[size_t(p.nv + r)]);
+  return t;
+}
+
+int ipm_const_list_check(int nconst, int n_par, const int* const_index, std::string* why) {
+  auto refuse = [&](const std::string& msg) { if (why) *why = msg; return int(RPM_E_INVALID); };
+  if (nconst <= 0) return refuse("the problem functor takes no constants");
+  if (!const_index) return refuse("const_index is NULL");
+  if (n_par < 1 || n_par > IPM_SENS_MAX_PAR)
+    return refuse("n_par = " + std::to_string(n_par) + " is outside 1 .. " + std::to_string(IPM_SENS_MAX_PAR));
+  std::vector<int> par_of(size_t(nconst), -1);
+  for (int k = 0; k < n_par; ++k) {
+    const int j = const_index[k];
+    if (j < 0 || j >= nconst) return refuse("const_index[" + std::to_string(k) + "] = " + std::to_string(j) + " is outside the " + std::to_string(nconst) + " constants");
+    if (par_of[size_t(j)] >= 0) return refuse("constant " + std::to_string(j) + " is listed twice (const_index[" + std::to_string(par_of[size_t(j)]) + "] and [" + std::to_string(k) + "])");
+    par_of[size_t(j)] = k;
+  }
   return RPM_OK;
 }
 

@@ -198,6 +198,25 @@ int rpm_sweep_sensitivities(rpm_sweep* s, int n_par, const int* var_index, doubl
       [&](size_t r) { return rpm_ipm_last_error(s->ipm[r]); });
 }
 
+/* rpm_ipm_constant_sensitivities of every share, laid out as rpm_sweep_sensitivities lays its results out. */
+int rpm_sweep_constant_sensitivities(rpm_sweep* s, int n_par, const int* const_index, double* dx, double* dlambda, double* delta_w,
+                                     int* info) {
+  if (!s) return RPM_E_INVALID;
+  if (!const_index || !dx || n_par < 1) {
+    s->err = (!const_index || !dx) ? "rpm_sweep_constant_sensitivities: const_index or dx is NULL" : "rpm_sweep_constant_sensitivities: n_par must be at least 1";
+    return RPM_E_INVALID;
+  }
+  const size_t P = size_t(n_par);
+  return for_each_share(
+      s,
+      [&](size_t r) {
+        const size_t i0 = size_t(s->first[r]);
+        return rpm_ipm_constant_sensitivities(s->ipm[r], n_par, const_index, dx + i0 * P * s->n, dlambda ? dlambda + i0 * P * s->m : nullptr,
+                                              delta_w ? delta_w + i0 : nullptr, info ? info + i0 : nullptr);
+      },
+      [&](size_t r) { return rpm_ipm_last_error(s->ipm[r]); });
+}
+
 /* The mesh-error estimate of the whole sweep (rpm_solution_error_batch on every share, side by side).  x: B x n; instance_mask:
  * B or NULL; any result may be NULL: interval_error B x KT, rel_err_max RT, rel_err B x RT, nonfinite B.  rel_err_max is the
  * element-wise maximum of the shares' blocks (a maximum: what one engine holding all B instances returns, bit for bit); a share

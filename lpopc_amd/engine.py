@@ -51,6 +51,9 @@ ABI_SYMBOLS = [
     "rpm_ipm_debug_line_search", "rpm_ipm_debug_update",
     "rpm_ipm_initial_state_variables", "rpm_ipm_parameter_variables", "rpm_ipm_sensitivities_dev", "rpm_ipm_sensitivities", "rpm_ipm_apply_sensitivities_dev",
     "rpm_ipm_apply_sensitivities", "rpm_ipm_debug_sensitivity_rhs", "rpm_sweep_sensitivities",
+    "rpm_ipm_constant_sensitivities_dev", "rpm_ipm_constant_sensitivities", "rpm_ipm_apply_constant_sensitivities_dev",
+    "rpm_ipm_apply_constant_sensitivities", "rpm_ipm_debug_constant_sensitivity_rhs", "rpm_sweep_constant_sensitivities",
+    "rpm_set_all_instance_constants",
 ]
 
 
@@ -113,6 +116,7 @@ def lib(path=None):
     L.rpm_synchronize.argtypes = [vp]
     L.rpm_set_option.argtypes = [vp, C.c_char_p, C.c_int]
     L.rpm_set_instance_constants.argtypes = [vp, C.c_int, dp, C.c_int]
+    L.rpm_set_all_instance_constants.argtypes = [vp, dp, C.c_int]
     L.rpm_get_option.argtypes = [vp, C.c_char_p, ip]
     L.rpm_get_phase_sizes.argtypes = [vp, C.c_int, ip, ip, ip]
     L.rpm_get_phase_tables.argtypes = [vp, C.c_int, dp, dp, ip, ip, dp, dp, ip, ip, dp]
@@ -227,6 +231,12 @@ def lib(path=None):
     L.rpm_ipm_apply_sensitivities.argtypes = [vp, C.c_int, ip] + [dp] * 7
     L.rpm_ipm_debug_sensitivity_rhs.argtypes = [vp, C.c_int, ip, dp]
     L.rpm_sweep_sensitivities.argtypes = [vp, C.c_int, ip, dp, dp, dp, ip]
+    L.rpm_ipm_constant_sensitivities_dev.argtypes = [vp, C.c_int, ip, vp, vp, dp, ip, vp]
+    L.rpm_ipm_constant_sensitivities.argtypes = [vp, C.c_int, ip, dp, dp, dp, ip]
+    L.rpm_ipm_apply_constant_sensitivities_dev.argtypes = [vp, C.c_int, ip] + [vp] * 8
+    L.rpm_ipm_apply_constant_sensitivities.argtypes = [vp, C.c_int, ip] + [dp] * 7
+    L.rpm_ipm_debug_constant_sensitivity_rhs.argtypes = [vp, C.c_int, ip, dp]
+    L.rpm_sweep_constant_sensitivities.argtypes = [vp, C.c_int, ip, dp, dp, dp, ip]
     _LIBS[so] = L
     if so == _SO:
         _LIB = L
@@ -396,6 +406,13 @@ class NLPEngine:
         """Give one instance of a batched engine its own problem constants (parameter sweeps)."""
         c = np.ascontiguousarray(consts, dtype=np.float64)
         self._check(self._L.rpm_set_instance_constants(self._h, int(instance), _dp(c), int(c.size)))
+
+    def set_all_instance_constants(self, consts):
+        """Every instance's constants, (n_instances, nconst), in one upload: what set_instance_constants leaves instance by instance."""
+        c = np.ascontiguousarray(consts, dtype=np.float64)
+        if c.ndim != 2 or c.shape[0] != self.n_instances:
+            raise RpmError(RPM_E_INVALID, "consts must be (n_instances, nconst)")
+        self._check(self._L.rpm_set_all_instance_constants(self._h, _dp(c), int(c.shape[1])))
 
     # ---- TNLP surface, host buffers --------------------------------------------------------
     def get_nlp_info(self):
@@ -1118,7 +1135,7 @@ class BatchedIPM:
     def _var_index(var_index):
         return None if var_index is None else np.ascontiguousarray(var_index, dtype=np.int32).ravel()
 
-    def sensitivities(self, var_index, want_lambda=True):
+    def sensitivities(self, var_index, want_lambda=True, _fn=None):
         """First-order sensitivities of the solution the solver holds to the fixed variables `var_index` (P of them):
         dict(dx (B, P, n), dlambda (B, P, m) or None, delta_w (B), info (B): 0 computed, 1 computed with a regularised matrix,
         2 left out (NaN blocks))."""
@@ -1127,22 +1144,22 @@ class BatchedIPM:
         P = 0 if vi is None else vi.size
         out = {"dx": np.zeros((B, P, n)), "dlambda": np.zeros((B, P, m)) if want_lambda else None, "delta_w": np.zeros(B),
                "info": np.zeros(B, dtype=np.int32)}
-        self._chk(self._L.rpm_ipm_sensitivities(self._h, P, None if vi is None else _ip(vi), _dp(out["dx"]),
-                                                _dp(out["dlambda"]) if want_lambda else None, _dp(out["delta_w"]), _ip(out["info"])))
+        self._chk((_fn or self._L.rpm_ipm_sensitivities)(self._h, P, None if vi is None else _ip(vi), _dp(out["dx"]),
+                                                         _dp(out["dlambda"]) if want_lambda else None, _dp(out["delta_w"]), _ip(out["info"])))
         return out
 
-    def sensitivities_dev(self, var_index, d_dx, d_dlambda=None, stream=None):
+    def sensitivities_dev(self, var_index, d_dx, d_dlambda=None, stream=None, _fn=None):
         """The device-resident form on torch CUDA tensors (float64): d_dx (B, P, n), d_dlambda (B, P, m) or None, written when
         the call returns -> dict(delta_w, info)."""
         B = self._e.n_instances
         vi = self._var_index(var_index)
         out = {"delta_w": np.zeros(B), "info": np.zeros(B, dtype=np.int32)}
         ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        self._chk(self._L.rpm_ipm_sensitivities_dev(self._h, 0 if vi is None else vi.size, None if vi is None else _ip(vi), ptr(d_dx),
-                                                    ptr(d_dlambda), _dp(out["delta_w"]), _ip(out["info"]), NLPEngine._stream(stream)))
+        self._chk((_fn or self._L.rpm_ipm_sensitivities_dev)(self._h, 0 if vi is None else vi.size, None if vi is None else _ip(vi), ptr(d_dx),
+                                                             ptr(d_dlambda), _dp(out["delta_w"]), _ip(out["info"]), NLPEngine._stream(stream)))
         return out
 
-    def apply_sensitivities(self, var_index, dx, delta, x, dlambda=None, lam=None):
+    def apply_sensitivities(self, var_index, dx, delta, x, dlambda=None, lam=None, _fn=None):
         """The predictor x + sum_k dx[:, k] delta[:, k] (and lambda likewise when dlambda and lam are given), nothing clipped:
         -> x_out (B, n), or (x_out, lambda_out)."""
         B, n, m = self._e.n_instances, self._e.n, self._e.m
@@ -1152,25 +1169,50 @@ class BatchedIPM:
         x_out = np.zeros((B, n))
         lam_out = np.zeros((B, m)) if dlambda is not None and lam is not None else None
         opt = lambda a: None if a is None else _dp(a)
-        self._chk(self._L.rpm_ipm_apply_sensitivities(self._h, 0 if vi is None else vi.size, None if vi is None else _ip(vi), opt(dx),
-                                                      opt(dlambda), opt(delta), opt(x), _dp(x_out), opt(lam), opt(lam_out)))
+        self._chk((_fn or self._L.rpm_ipm_apply_sensitivities)(self._h, 0 if vi is None else vi.size, None if vi is None else _ip(vi), opt(dx),
+                                                               opt(dlambda), opt(delta), opt(x), _dp(x_out), opt(lam), opt(lam_out)))
         return x_out if lam_out is None else (x_out, lam_out)
 
-    def apply_sensitivities_dev(self, var_index, d_dx, d_delta, d_x, d_x_out, d_dlambda=None, d_lambda=None, d_lambda_out=None, stream=None):
+    def apply_sensitivities_dev(self, var_index, d_dx, d_delta, d_x, d_x_out, d_dlambda=None, d_lambda=None, d_lambda_out=None, stream=None,
+                                _fn=None):
         """One launch on `stream` (torch's current one by default) over torch CUDA tensors; capturable into a graph."""
         vi = self._var_index(var_index)
         ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        self._chk(self._L.rpm_ipm_apply_sensitivities_dev(self._h, 0 if vi is None else vi.size, None if vi is None else _ip(vi), ptr(d_dx),
-                                                          ptr(d_dlambda), ptr(d_delta), ptr(d_x), ptr(d_x_out), ptr(d_lambda),
-                                                          ptr(d_lambda_out), NLPEngine._stream(stream)))
+        self._chk((_fn or self._L.rpm_ipm_apply_sensitivities_dev)(self._h, 0 if vi is None else vi.size, None if vi is None else _ip(vi),
+                                                                   ptr(d_dx), ptr(d_dlambda), ptr(d_delta), ptr(d_x), ptr(d_x_out), ptr(d_lambda),
+                                                                   ptr(d_lambda_out), NLPEngine._stream(stream)))
 
-    def debug_sensitivity_rhs(self, var_index):
+    def debug_sensitivity_rhs(self, var_index, _fn=None):
         """Test hook: the right-hand sides of sensitivities() -> (B, P, kkt_order), unknown order (variables, slacks, multipliers)."""
         vi = self._var_index(var_index)
         P = 0 if vi is None else vi.size
         rhs = np.zeros((self._e.n_instances, P, self.info()["kkt_order"]))
-        self._chk(self._L.rpm_ipm_debug_sensitivity_rhs(self._h, P, None if vi is None else _ip(vi), _dp(rhs)))
+        self._chk((_fn or self._L.rpm_ipm_debug_sensitivity_rhs)(self._h, P, None if vi is None else _ip(vi), _dp(rhs)))
         return rhs
+
+    # ---- solution sensitivities to the instances' constants (rpm_ipm_constant_sensitivities, include/rpm_hip.h): the calls above
+    # with a list of constants (indices into the functor's constants) in place of the list of fixed variables
+
+    def constant_sensitivities(self, const_index, want_lambda=True):
+        """First-order sensitivities of the solution the solver holds to the constants `const_index` of every instance (its own,
+        set_instance_constants, or the shared ones): the dict of sensitivities(); dx is 0 on every fixed variable."""
+        return self.sensitivities(const_index, want_lambda, _fn=self._L.rpm_ipm_constant_sensitivities)
+
+    def constant_sensitivities_dev(self, const_index, d_dx, d_dlambda=None, stream=None):
+        return self.sensitivities_dev(const_index, d_dx, d_dlambda, stream, _fn=self._L.rpm_ipm_constant_sensitivities_dev)
+
+    def apply_constant_sensitivities(self, const_index, dx, delta, x, dlambda=None, lam=None):
+        """The predictor for moves `delta` (B, P) of the listed constants."""
+        return self.apply_sensitivities(const_index, dx, delta, x, dlambda, lam, _fn=self._L.rpm_ipm_apply_constant_sensitivities)
+
+    def apply_constant_sensitivities_dev(self, const_index, d_dx, d_delta, d_x, d_x_out, d_dlambda=None, d_lambda=None, d_lambda_out=None,
+                                         stream=None):
+        self.apply_sensitivities_dev(const_index, d_dx, d_delta, d_x, d_x_out, d_dlambda, d_lambda, d_lambda_out, stream,
+                                     _fn=self._L.rpm_ipm_apply_constant_sensitivities_dev)
+
+    def debug_constant_sensitivity_rhs(self, const_index):
+        """Test hook: the right-hand sides of constant_sensitivities() -> (B, P, kkt_order), unknown order."""
+        return self.debug_sensitivity_rhs(const_index, _fn=self._L.rpm_ipm_debug_constant_sensitivity_rhs)
 
     def debug_start(self, x0, lam0=None, z0=None, warm=True):
         """The state the iteration loop starts from (rpm_ipm_debug_start; no step is taken): dict(v (B, nv): x then the slacks,

@@ -199,15 +199,19 @@ class SweepGroup:
         self._check(self._L.rpm_sweep_get_bound_multipliers(self._h, _dp(zl), _dp(zu)))
         return zl, zu
 
-    def sensitivities(self, var_index, want_lambda=True):
+    def sensitivities(self, var_index, want_lambda=True, _fn=None):
         """rpm_sweep_sensitivities: as BatchedIPM.sensitivities, over all shares."""
         B = self.n_instances
         vi = np.ascontiguousarray(var_index, dtype=np.int32).ravel()
         out = {"dx": np.zeros((B, vi.size, self.n)), "dlambda": np.zeros((B, vi.size, self.m)) if want_lambda else None,
                "delta_w": np.zeros(B), "info": np.zeros(B, dtype=np.int32)}
-        self._check(self._L.rpm_sweep_sensitivities(self._h, vi.size, _ip(vi), _dp(out["dx"]), _dp(out["dlambda"]) if want_lambda else None,
-                                                    _dp(out["delta_w"]), _ip(out["info"])))
+        self._check((_fn or self._L.rpm_sweep_sensitivities)(self._h, vi.size, _ip(vi), _dp(out["dx"]),
+                                                             _dp(out["dlambda"]) if want_lambda else None, _dp(out["delta_w"]), _ip(out["info"])))
         return out
+
+    def constant_sensitivities(self, const_index, want_lambda=True):
+        """rpm_sweep_constant_sensitivities: as BatchedIPM.constant_sensitivities, over all shares."""
+        return self.sensitivities(const_index, want_lambda, _fn=self._L.rpm_sweep_constant_sensitivities)
 
     def stats(self):
         a, b, c = C.c_int(), C.c_int(), C.c_int()

@@ -7,7 +7,11 @@ cost and what they buy, each number beside the parent's path in the same run.  P
       measured states + warm solve + bound multipliers + shift from the shifted plan ("plain"), and with the advanced step — solve
       for the predicted state and take its sensitivities while the plant moves ("background"), then predictor + the same step
       ("foreground")
-Run on the GPU box:  python tools/measure_sensitivities.py [instances (a, b)] [instances (c)] [steps (c)]"""
+  (d) on the sweep of (a): the sensitivities to the three target constants and the mass (rpm_ipm_constant_sensitivities_dev) beside
+      those to the 12 initial states, and every instance's constants in one upload against one call per instance
+  (e) a receding-horizon step at 256 instances whose targets move by up to 0.05 per axis: new constants + warm solve from the old
+      plan ("plain"), and with the predictor x + S delta in between ("predictor"; its sensitivities are taken in the background)
+Run on the GPU box:  python tools/measure_sensitivities.py [instances (a, b, d)] [instances (c, e)] [steps (c, e)] [parts, e.g. de]"""
 import json
 import os
 import sys
@@ -24,7 +28,9 @@ from lpopc_amd.problem import Options
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 1024
 B_C = int(sys.argv[2]) if len(sys.argv) > 2 else 256
 STEPS = int(sys.argv[3]) if len(sys.argv) > 3 else 8
+PARTS = sys.argv[4] if len(sys.argv) > 4 else "abcde"
 K, NK = 8, 8
+CONSTS = np.array([7, 8, 9, 0], dtype=np.int32)      # quadrotor: the target position, the mass
 N1 = K * NK + 1
 X0_IDX = np.array([i * N1 for i in range(12)])
 o = Options()
@@ -94,7 +100,86 @@ def part_a_b():
         print(json.dumps({"part": "b", "with_lambda": with_lambda, "bytes": nbytes, "median_us": 1e3 * ms[reps // 2], "min_us": 1e3 * ms[0],
                           "GBs_at_median": nbytes / (ms[reps // 2] * 1e-3) / 1e9,
                           "note": "back-to-back launches on arrays of %.0f MB: re-reads may be served by the Infinity Cache" % (nbytes / 1e6)}))
+    if "d" in PARTS:
+        part_d(eng, ipm, sens_ms, solve_ms / max(1, st["iterations"]))
     ipm.close()
+    eng.close()
+
+
+def part_d(eng, ipm, sens_ms, iteration_ms):
+    n, m, Pc = eng.n, eng.m, len(CONSTS)
+    d_dx = torch.empty((B, Pc, n), dtype=torch.float64, device="cuda")
+    d_dl = torch.empty((B, Pc, m), dtype=torch.float64, device="cuda")
+    ipm.constant_sensitivities_dev(CONSTS, d_dx, d_dl)             # warm-up: table, scratch, work space
+    s, const_ms = timed(lambda: ipm.constant_sensitivities_dev(CONSTS, d_dx, d_dl))
+    _, one_ms = timed(lambda: ipm.constant_sensitivities_dev(CONSTS[:1], d_dx, d_dl))
+    consts = np.tile(np.array(problems.quadrotor(K, NK).GetOpimalProblemFuns().consts), (B, 1))
+    _, all_ms = timed(lambda: eng.set_all_instance_constants(consts))
+    _, loop_ms = timed(lambda: [eng.set_instance_constants(b, consts[b]) for b in range(B)], reps=1)
+    print(json.dumps({"part": "d", "instances": B, "constants": Pc, "constant_sensitivities_ms": const_ms,
+                      "constant_sensitivities_one_constant_ms": one_ms, "sensitivities_12_states_ms": sens_ms,
+                      "constant_sensitivities_in_iterations": const_ms / iteration_ms,
+                      "info_counts": np.bincount(s["info"], minlength=3).tolist(),
+                      "set_all_instance_constants_ms": all_ms, "set_instance_constants_loop_ms": loop_ms}))
+
+
+def part_e():
+    Bc = B_C
+    rng = np.random.RandomState(2)
+    targets = rng.uniform(-1.5, 1.5, size=(Bc, 3))
+    consts = np.tile(np.array(problems.quadrotor(K, NK).GetOpimalProblemFuns().consts), (Bc, 1))
+    consts[:, 7:10] = targets
+    eng = NLPEngine(problems.quadrotor(K, NK), o, n_instances=Bc, device=0)
+    n, m = eng.n, eng.m
+    ks = CONSTS[:3]
+    xl, xu, _, _ = eng.get_bounds_info()
+    XL, XU = np.tile(xl, (Bc, 1)), np.tile(xu, (Bc, 1))
+    XL[:, X0_IDX[:3]] = XU[:, X0_IDX[:3]] = rng.uniform(-0.3, 0.3, size=(Bc, 3))
+    x0 = np.tile(eng.get_starting_point()[:n], (Bc, 1))
+    moves = np.random.RandomState(11).uniform(-0.05, 0.05, size=(STEPS, Bc, 3))
+    for leg in ("plain", "predictor"):
+        s = BatchedIPM(eng, tol=1e-6)
+        s.set_all_bounds(XL, XU)
+        c = consts.copy()
+        eng.set_all_instance_constants(c)
+        sol = s.solve(x0)
+        z = s.bound_multipliers()
+        s.set_option("mu_init", 1e-4)
+        for k in ("warm_start_bound_push", "warm_start_bound_frac", "warm_start_slack_bound_push", "warm_start_slack_bound_frac"):
+            s.set_option(k, 1e-6)
+        s.set_option("warm_start_mult_bound_push", 1e-8)
+        rows = []
+        for step in range(STEPS):
+            row = {}
+            x, lam = sol["x"], sol["lambda"]
+            if leg == "predictor":
+                t0 = time.perf_counter()
+                sens = s.constant_sensitivities(ks)
+                row["background_ms"] = 1e3 * (time.perf_counter() - t0)
+                row["left_out"] = int((sens["info"] == 2).sum())
+            t0 = time.perf_counter()
+            c[:, 7:10] += moves[step]
+            eng.set_all_instance_constants(c)
+            if leg == "predictor":
+                x, lam = s.apply_constant_sensitivities(ks, sens["dx"], moves[step], x, sens["dlambda"], lam)
+            sol_new = s.solve(x, lam, z)
+            z = s.bound_multipliers()
+            row.update(foreground_ms=1e3 * (time.perf_counter() - t0), iterations_max=int(sol_new["iterations"].max()),
+                       iterations_mean=float(sol_new["iterations"].mean()), converged=int((sol_new["status"] == 0).sum()),
+                       start_miss=float(np.abs(sol_new["x"] - x).max()))
+            sol = sol_new
+            rows.append(row)
+        rows = rows[1:]
+        out = {"part": "e", "leg": leg, "instances": Bc, "steps": len(rows), "target_move_max": 0.05,
+               "foreground_ms_min_median_max": [float(f(np.array([q["foreground_ms"] for q in rows]))) for f in (np.min, np.median, np.max)],
+               "iterations_max_per_step": [q["iterations_max"] for q in rows],
+               "iterations_mean_per_step": [round(q["iterations_mean"], 2) for q in rows],
+               "start_to_solution_inf_max": max(q["start_miss"] for q in rows), "converged_min": min(q["converged"] for q in rows)}
+        if leg == "predictor":
+            out["background_ms_min_median_max"] = [float(f(np.array([q["background_ms"] for q in rows]))) for f in (np.min, np.median, np.max)]
+            out["left_out_max"] = max(q["left_out"] for q in rows)
+        print(json.dumps(out))
+        s.close()
     eng.close()
 
 
@@ -192,5 +277,9 @@ def part_c():
 
 
 if __name__ == "__main__":
-    part_a_b()
-    part_c()
+    if set("abd") & set(PARTS):
+        part_a_b()
+    if "c" in PARTS:
+        part_c()
+    if "e" in PARTS:
+        part_e()
