@@ -724,6 +724,11 @@ int rpm_ipm_debug_solve(rpm_ipm* s, const double* k_storage, const double* rhs, 
  * tells whether the layout can hold entry (ua, uc) */
 int rpm_ipm_debug_solve_dense(rpm_ipm* s, const double* k_dense, const double* rhs, double* sol, int* n_pos, int* n_neg);
 int rpm_ipm_debug_slot(rpm_ipm* s, int ua, int uc, long long* offset);
+/* test hook, read-only (host pointer, synchronous): the KKT storage of every instance as it stands, n_instances x storage doubles
+ * (rpm_ipm_get_info) — after rpm_ipm_debug_solve[_dense] or rpm_ipm_debug_pass(stage 3) the factors (d on the diagonal, L below it,
+ * L11^-1 below the diagonal of every 16 x 16 diagonal block), after a stage-2 pass the assembled matrix.  It changes no state and,
+ * like rpm_ipm_debug_slot, may come between any two calls. */
+int rpm_ipm_debug_storage(rpm_ipm* s, double* k_storage);
 /* test hooks of the limited-memory BFGS kernels (host pointers; RPM_E_UNSUPPORTED on a solver with the exact Hessian).  They run
  * the solver's own launchers on the caller's data:
  *   _step   one pass of the update as the solve loop runs it after the residual: x, glag_new = grad_x L(x, lambda), glag_old =

@@ -94,6 +94,7 @@ def bind_ipm_debug_pass(L):
     L.rpm_ipm_debug_pass.argtypes = [C.c_void_p, C.c_int] + [c_double_p] * len(IPM_PASS_OUTPUTS)
     L.rpm_ipm_debug_line_search.argtypes = [C.c_void_p, C.c_int, C.c_int, c_double_p, c_int_p] + [c_double_p] * len(IPM_LINE_SEARCH_OUTPUTS) + [c_int_p]
     L.rpm_ipm_debug_update.argtypes = [C.c_void_p] + [c_double_p] * 4 + [C.c_int] + [c_double_p] * (len(IPM_UPDATE_OUTPUTS) - 4)
+    L.rpm_ipm_debug_storage.argtypes = [C.c_void_p, c_double_p]      # read-only: the KKT storage as it stands
 
 
 def bind_rollout(L):

@@ -146,6 +146,15 @@ int rpm_ipm_debug_slot(rpm_ipm* h, int ua, int uc, long long* offset) {
   return RPM_OK;
 }
 
+/* test hook, read-only: D.K of every instance as it stands (B x storage doubles) — the factors after the factor hooks or a stage-3
+ * pass.  No launch, no change of what the solver holds. */
+int rpm_ipm_debug_storage(rpm_ipm* h, double* k_storage) {
+  if (!h || !k_storage) return RPM_E_INVALID;
+  IPM_TRY(h, hipStreamSynchronize(ipm_stream(h)));
+  IPM_TRY(h, hipMemcpy(k_storage, h->D.K, size_t(h->D.B) * size_t(h->plan.storage()) * sizeof(double), hipMemcpyDeviceToHost));
+  return RPM_OK;
+}
+
 /* KKT position of every unknown ([0,n) variables, then the slacks, then the m multipliers) — for tests and tools */
 int rpm_ipm_get_permutation(rpm_ipm* h, int* pos, int capacity) {
   if (!h || !pos || capacity < h->plan.Nt) return RPM_E_INVALID;

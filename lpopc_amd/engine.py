@@ -46,7 +46,7 @@ ABI_SYMBOLS = [
     "rpm_group_eval_h", "rpm_group_eval_pair_dev", "rpm_group_allgather_pair_dev",
     "rpm_sweep_create", "rpm_sweep_destroy", "rpm_sweep_last_error", "rpm_sweep_size", "rpm_sweep_engine", "rpm_sweep_solver", "rpm_sweep_share",
     "rpm_sweep_set_option", "rpm_sweep_set_bounds", "rpm_sweep_solve", "rpm_sweep_get_stats",
-    "rpm_ipm_get_stats", "rpm_ipm_get_subproblems", "rpm_ipm_get_trace", "rpm_ipm_get_restorations", "rpm_ipm_get_kernel_times", "rpm_ipm_solve", "rpm_ipm_solve_dev", "rpm_ipm_get_permutation", "rpm_ipm_debug_solve", "rpm_ipm_debug_solve_dense", "rpm_ipm_debug_slot",
+    "rpm_ipm_get_stats", "rpm_ipm_get_subproblems", "rpm_ipm_get_trace", "rpm_ipm_get_restorations", "rpm_ipm_get_kernel_times", "rpm_ipm_solve", "rpm_ipm_solve_dev", "rpm_ipm_get_permutation", "rpm_ipm_debug_solve", "rpm_ipm_debug_solve_dense", "rpm_ipm_debug_slot", "rpm_ipm_debug_storage",
     "rpm_ipm_debug_lbfgs_step", "rpm_ipm_debug_lbfgs_state", "rpm_ipm_debug_lbfgs_solve", "rpm_ipm_debug_pass",
     "rpm_ipm_debug_line_search", "rpm_ipm_debug_update",
     "rpm_ipm_initial_state_variables", "rpm_ipm_parameter_variables", "rpm_ipm_sensitivities_dev", "rpm_ipm_sensitivities", "rpm_ipm_apply_sensitivities_dev",
@@ -1046,6 +1046,13 @@ class BatchedIPM:
         off = C.c_longlong()
         self._chk(self._L.rpm_ipm_debug_slot(self._h, int(ua), int(uc), C.byref(off)))
         return off.value
+
+    def debug_storage(self):
+        """The KKT storage as it stands (rpm_ipm_debug_storage; read-only), (n_instances, storage_doubles): after debug_solve[_dense]
+        or debug_pass(3) the factors — d on the diagonal, L below, L11^-1 below the diagonal of every 16 x 16 diagonal block."""
+        k = np.zeros((self._e.n_instances, self.info()["storage_doubles"]))
+        self._chk(self._L.rpm_ipm_debug_storage(self._h, _dp(k)))
+        return k
 
     def debug_lbfgs_step(self, x, glag_new, glag_old, reset=False, mode=None, status=None):
         """One pass of the limited-memory update (rpm_ipm_debug_lbfgs_step): x, glag_new, glag_old (n_instances, n); mode, status

@@ -27,7 +27,8 @@ OPTS = dict(tol=1e-8, mu_init=0.1, kappa_eps=10.0, kappa_mu=0.2, theta_mu=1.5, t
             gamma_theta=1e-5, gamma_phi=1e-8, delta=1.0, s_theta=1.1, s_phi=2.3, gamma_alpha=0.05, delta_c=1e-9,
             max_iter=3000, acceptable_tol=1e-6, acceptable_iter=15, mu_strategy=1, mu_max_fact=1e3, mu_red_fact=0.9999,
             dual_inf_tol=1.0, constr_viol_tol=1e-4, compl_inf_tol=1e-4,
-            acc_dual_inf_tol=1e10, acc_constr_viol_tol=1e-2, acc_compl_inf_tol=1e-2)
+            acc_dual_inf_tol=1e10, acc_constr_viol_tol=1e-2, acc_compl_inf_tol=1e-2,
+            delta_w_first=1e-4, kw_inc_first=100.0)          # Algorithm IC's first rungs (IpmOpts; no option sets them)
 
 
 def single_tol(mag):

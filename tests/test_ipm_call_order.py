@@ -48,6 +48,7 @@ def test_call_order_on_a_live_solver(built):
     # their right-hand sides alone leave the direction alone
     direction()
     assert ipm.debug_sensitivity_rhs(params).shape == (2, len(params), nt)
+    assert ipm.debug_storage().shape == (2, ipm.info()["storage_doubles"])      # read-only, like rpm_ipm_debug_slot: no state changes
     ipm.debug_line_search()
 
     # trial points are no state to take sensitivities at; one update per line search
